@@ -33,10 +33,6 @@ import subprocess
 import sys
 import time
 
-# HIP spreads its streams over this many hardware queues (default 4); two streams that share a queue serialise, and the
-# two-stream legs below want theirs apart from the library's, torch's and the sharding layer's streams
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
-
 import numpy as np
 import torch
 
@@ -89,6 +85,29 @@ def recall_at_k(ids, gt, k):
 def outs(B, k, dev):
     return (torch.zeros((B, k), dtype=torch.int32, device=dev), torch.zeros((B, k), dtype=torch.float32, device=dev),
             torch.zeros((B,), dtype=torch.int32, device=dev))
+
+
+DUMP_BYTES = 60 << 20   # --dump-outputs: payload of all .npy files together (under the 64 MB the option promises)
+
+
+def dump_outputs(path, ids, dist, cnt):
+    """--dump-outputs DIR: the answers the timed path handed its caller in the last timed step, so that two builds can be compared
+    output for output on the same seeded inputs.  DIR/ids.npy (float64: every 32-bit id exactly), DIR/dist.npy (the distances as
+    computed), DIR/count.npy (float64) and DIR/rows.npy (float64: the query rows the three hold).  A batch larger than DUMP_BYTES
+    is cut to a fixed seeded sample of query rows; otherwise rows.npy is 0 .. B-1."""
+    ids = np.ascontiguousarray(ids).view(np.uint32).astype(np.float64)
+    dist = np.asarray(dist)
+    cnt = np.ascontiguousarray(cnt).view(np.uint32).astype(np.float64)
+    B = ids.shape[0]
+    rows = np.arange(B)
+    per_row = ids[:1].nbytes + dist[:1].nbytes + 8 + 8
+    if B * per_row > DUMP_BYTES:
+        rows = np.sort(np.random.default_rng(0).choice(B, DUMP_BYTES // per_row, replace=False))
+        ids, dist, cnt = ids[rows], dist[rows], cnt[rows]
+    os.makedirs(path, exist_ok=True)
+    for name, arr in (("ids", ids), ("dist", dist), ("count", cnt), ("rows", rows.astype(np.float64))):
+        np.save(os.path.join(path, name + ".npy"), arr)
+    log(f"[bench] outputs of the last timed step ({len(rows)} of {B} queries) -> {path}/{{ids,dist,count,rows}}.npy")
 
 
 def pmc_pass(counters, inner_args, tag, mode="--inner"):
@@ -173,7 +192,11 @@ def main():
                          "288 GB per GPU, 2 if not -- no GPU needed")
     ap.add_argument("--preset", default="", choices=["", "config4"],
                     help="config4 = BASELINE configs[3]: 12.5M x 768 cosine rows PER RANK (100M over 8 GPUs), clustered law (ii), 8192 queries")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write the answers of the last one (ids, distances, counts) as DIR/<name>.npy")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
     if a.shapes:  # side leg on its own: the reference's published benchmark shapes
         import kektordb_amd as K
         print(json.dumps(reference_shapes_leg(K, torch.device("cuda", 0))), flush=True)
@@ -340,6 +363,8 @@ def main():
         tt = torch.tensor([elapsed], dtype=torch.float64, device=dev if a.backend == "nccl" else "cpu")
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, out_ids.cpu().numpy(), out_dist.cpu().numpy(), out_cnt.cpu().numpy())
     recall = recall_at_k(out_ids.cpu().numpy().view(np.uint32), gt, k)
 
     # ---- roofline of the dominant kernel (hnsw_search_kernel): every launch of the timed region
@@ -715,8 +740,10 @@ def cluster_main(a):
         torch.cuda.synchronize(d)
     t0 = time.perf_counter()
     for _ in range(a.steps):
-        ids = cl.search_batch(Q, k, ef)[0]     # returns when the merged answers are in host memory
+        ids, dists, cnt = cl.search_batch(Q, k, ef)     # returns when the merged answers are in host memory
     elapsed = time.perf_counter() - t0
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, ids, dists, cnt)
     recall = recall_at_k(ids, gt, k)
     st = [s.launch_stats(min(a.steps, 64)) for s in shards]
     kernel_ms = float(np.mean([c["kernel_ms"] for c in st[0]]))

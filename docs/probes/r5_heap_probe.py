@@ -1,7 +1,6 @@
 """round 5: what the heap-order second pass costs per walk: batches made of TIED queries only (1, 16, 256, all), with and without
 KDB_SEARCH_HEAP_ORDER; kernel_ms of the launch pair (HIP events of the library around both passes)."""
 import os, sys, time
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bench as BN

@@ -1,7 +1,6 @@
 """round 5: how long ONE combined launch of G queries takes when nothing else runs (host pointers, lone caller) beside the
 kernel time of the same G queries through the device-pointer entry point: separates the group's own time from what concurrency adds."""
 import os, sys, time
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bench as BN

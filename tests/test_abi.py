@@ -50,12 +50,13 @@ def test_legacy_compute_symbols_exported(K):
         assert not [s for s in syms if s not in exported], (path, syms)
 
 
-def test_header_compiles_as_plain_c():
+def test_header_compiles_as_plain_c(tmp_path):
     src = '#include "kektor_hip.h"\nint main(void){kdb_index_desc d; (void)d; return sizeof(kdb_counters) == 48 ? 0 : 1;}\n'
+    exe = str(tmp_path / "kdb_hdr_test")
     p = subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), "-x", "c", "-", "-o",
-                        "/tmp/kdb_hdr_test"], input=src, text=True, capture_output=True)
+                        exe], input=src, text=True, capture_output=True)
     assert p.returncode == 0, p.stderr
-    assert subprocess.run(["/tmp/kdb_hdr_test"]).returncode == 0
+    assert subprocess.run([exe]).returncode == 0
 
 
 @pytest.mark.skipif(__import__("conftest").HAS_GPU, reason="CPU-only behaviour")

@@ -56,3 +56,44 @@ def test_the_bench_line_stays_machine_readable():
     fat = dict(full, reference_benchmark_shapes={"shapes": [{"shape": f"Shape-{i} cosine, M=16 efS={i}", "frac_of_hbm_peak": 0.1, "kernel_ms": 1.0} for i in range(400)]})
     rec2, line2 = bench.compact_record(fat)
     assert len(line2.encode()) <= 6000 and json.loads(line2)["roofline"]["frac"] == full["roofline"]["frac"]
+
+
+def test_steps_below_one_is_refused():
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0", "--dry-run"], capture_output=True, text=True,
+                       timeout=300)
+    assert p.returncode == 2 and "--steps" in p.stderr
+
+
+def test_dump_outputs_writes_what_the_caller_received(tmp_path):
+    """--dump-outputs: ids (uint32 bits, exact in float64), distances as computed, counts, and the query rows they belong to"""
+    import numpy as np
+    import bench
+    rng = np.random.default_rng(5)
+    B, k = 300, 10
+    ids = rng.integers(0, 2**32, (B, k), dtype=np.uint64).astype(np.uint32).view(np.int32)   # int32 bits, as the device buffers hold them
+    dist = rng.random((B, k), dtype=np.float32)
+    cnt = rng.integers(0, k + 1, B).astype(np.int32)
+    bench.dump_outputs(str(tmp_path / "out"), ids, dist, cnt)
+    got = {n: np.load(tmp_path / "out" / f"{n}.npy") for n in ("ids", "dist", "count", "rows")}
+    assert got["ids"].dtype == np.float64 and np.array_equal(got["ids"], ids.view(np.uint32).astype(np.float64))
+    assert got["dist"].dtype == np.float32 and np.array_equal(got["dist"], dist)
+    assert got["count"].dtype == np.float64 and np.array_equal(got["count"], cnt.astype(np.float64))
+    assert np.array_equal(got["rows"], np.arange(B, dtype=np.float64))
+
+
+def test_dump_outputs_samples_a_large_batch_the_same_way_every_time(tmp_path, monkeypatch):
+    import numpy as np
+    import bench
+    B, k = 5000, 10
+    monkeypatch.setattr(bench, "DUMP_BYTES", 100 * (k * 8 + k * 4 + 16))   # room for 100 query rows
+    ids = np.arange(B * k, dtype=np.uint32).reshape(B, k)
+    dist = np.arange(B * k, dtype=np.float32).reshape(B, k)
+    cnt = np.full(B, k, dtype=np.uint32)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), ids, dist, cnt)
+    ra, rb = (np.load(tmp_path / d / "rows.npy") for d in ("a", "b"))
+    assert len(ra) == 100 and np.array_equal(ra, rb) and np.all(np.diff(ra) > 0)
+    rows = ra.astype(np.int64)
+    assert np.array_equal(np.load(tmp_path / "a" / "ids.npy"), ids[rows].astype(np.float64))
+    assert np.array_equal(np.load(tmp_path / "a" / "dist.npy"), dist[rows])
+    assert sum(os.path.getsize(tmp_path / "a" / f"{n}.npy") for n in ("ids", "dist", "count", "rows")) < 100 * (k * 12 + 16) + 4 * 256

@@ -32,6 +32,9 @@ def _make_shard(O, X, base, cnt, metric, prec, seed):
 
 
 def _worker(rank, world, port, metric, out, prec=0):
+    # the ranks are CPU processes: the loader of kektordb_amd asks torch whether a GPU is there, which initialises the HIP
+    # runtime and opens the device -- on a GPU machine eight ranks beside the test runner would each hold the GPU open
+    torch.cuda.is_available = lambda: False
     sys.path.insert(0, ROOT)
     os.environ["MASTER_ADDR"] = "127.0.0.1"
     os.environ["MASTER_PORT"] = str(port)
