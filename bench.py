@@ -12,14 +12,21 @@ are already resident in HBM.  With N > 1 every rank owns an id-range shard of `-
 grows with N: weak scaling), the same B queries are searched on every shard and merged; `value` is the
 number of MERGED answers per second over the N x rows corpus.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with
-  roofline      HIP-event kernel time of hnsw_search_kernel against the algorithmic bytes of SURVEY 8d, and the
-                HBM-side traffic of the same kernel measured IN THIS RUN (a short rocprofv3 --pmc pass of this very
-                script, FETCH_SIZE / WRITE_SIZE, corrected as MI355X_MICROARCH.md prescribes);
+Prints ONE JSON line on rank 0.  A plain run does what the headline needs and no more: corpus
+and graph on the GPU, the exact scan that recall is measured against, the ef sweep on held-out queries, warm-up, the timed steps,
+--dump-outputs, the line -- with `roofline` from the HIP events the library recorded around the timed launches themselves.
+
+    python bench.py --full ...
+
+runs everything else as well, after the timed steps (about 3.5 minutes more), and writes the full record to bench_extras.json:
+  roofline      the HBM-side traffic of hnsw_search_kernel measured IN THIS RUN (short rocprofv3 --pmc passes of this very
+                script, FETCH_SIZE / WRITE_SIZE, a wide read counted at half its bytes on gfx950 corrected for) and the
+                bandwidth ceilings measured on this index's own rows;
   cpu_baseline  the CPU restatement oracle searching the SAME graph/rows/queries on the host cores;
 and, at N = 1, the extra legs the survey asks for (section 8d): batch sizes 1 / 64 / 1024 / 8192 / 32768 (one stream, and
 two streams whose launches overlap), the PCIe-inclusive rate of the host-pointer entry point, the exact flat scan
 (MFMA roofline, matrix-core busy fraction), the adversarial iid corpus, and a torch.matmul/topk check of the ground truth.
+--no-cpu, --no-extras, --no-pmc and --legs choose among these; they say nothing without --full.
 """
 from __future__ import annotations
 
@@ -167,12 +174,16 @@ def main():
     ap.add_argument("--recall", type=float, default=0.95)
     ap.add_argument("--efc", type=int, default=200)
     ap.add_argument("--build-batch", type=int, default=16384, help="nodes inserted per round of the GPU builder")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run everything beside the headline: the CPU baseline, the side legs (other batch "
+                         "sizes, corpora, configurations, the exact scan), the measured bandwidth ceilings and the rocprofv3 counter passes; "
+                         "the full record goes to bench_extras.json")
     ap.add_argument("--cpu-seconds", type=float, default=8.0)
     ap.add_argument("--cpu-threads", type=int, default=0, help="0 = all hardware threads")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="only the headline leg (no batch sweep, flat leg, iid corpus, PMC passes)")
-    ap.add_argument("--no-pmc", action="store_true", help="skip the rocprofv3 counter passes (roofline.traffic = null)")
-    ap.add_argument("--legs", default="", help="comma-separated names of the side legs to run (default: all), e.g. flat_scan_leg,corpus_iid")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: no side legs (no batch sweep, flat leg, iid corpus, PMC passes)")
+    ap.add_argument("--no-pmc", action="store_true", help="with --full: skip the rocprofv3 counter passes (roofline.traffic = null)")
+    ap.add_argument("--legs", default="", help="with --full: comma-separated names of the side legs to run (default: all), e.g. flat_scan_leg,corpus_iid")
     ap.add_argument("--flat-batch", type=int, default=8192, help="queries of the flat-scan leg")
     ap.add_argument("--backend", default="nccl", help="nccl (RCCL) or gloo (test rigs: several ranks on one GPU)")
     ap.add_argument("--direct", action="store_true", help=argparse.SUPPRESS)
@@ -197,6 +208,8 @@ def main():
     a = ap.parse_args()
     if a.steps < 1:
         ap.error("--steps must be at least 1")
+    if a.legs and not a.full:
+        ap.error("--legs chooses among the side legs of a --full run: add --full")
     if a.shapes:  # side leg on its own: the reference's published benchmark shapes
         import kektordb_amd as K
         print(json.dumps(reference_shapes_leg(K, torch.device("cuda", 0))), flush=True)
@@ -432,7 +445,7 @@ def main():
 
     # the same fraction against what THIS box delivers on the kernel's access pattern with nothing else running (SURVEY 8d asks
     # for a measured bandwidth beside the nominal peak): a uniform random whole-row gather and one streaming pass over the rows
-    if rank == 0:
+    if rank == 0 and a.full:
         try:
             gth_gbs, str_gbs = idx.probe_gather(6_000_000), idx.probe_stream()
             res["roofline"]["measured_ceilings"] = {
@@ -443,7 +456,7 @@ def main():
             res["roofline"]["frac_of_measured"] = round(achieved / gth_gbs, 4)
         except Exception as e:
             log(f"[bench] measured ceilings failed: {e!r}")
-    extras = rank == 0 and world == 1 and not a.no_extras
+    extras = a.full and rank == 0 and world == 1 and not a.no_extras
     if extras and X is not None:
         try:
             res["ground_truth_check"] = check_ground_truth(X, Q, gt, gt_o[1], k)
@@ -519,7 +532,7 @@ def main():
             log(f"[bench] reference-linked graph leg failed: {e!r}")
             res["reference_linked_graph"] = None
     # ---- CPU baseline: the restatement oracle on the SAME graph + rows + queries (rank 0, N = 1)
-    if rank == 0 and world == 1 and not a.no_cpu:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu:
         try:
             res["cpu_baseline"] = cpu_baseline(idx, Q, k, ef, n, dim, a)
         except Exception as e:  # never lose the GPU line
@@ -541,7 +554,7 @@ def main():
         dist.destroy_process_group()
     flush_all()
     if rank == 0:
-        emit(res)
+        emit(res, a.full)
 
 
 LINE_LIMIT = 6000   # bytes: the driver keeps a bounded tail of stdout; round 5's 20 KB line could not be parsed
@@ -555,9 +568,10 @@ def _g(d, *path, default=None):
     return d
 
 
-def compact_record(res):
+def compact_record(res, extras_file="bench_extras.json"):
     """The ONE machine-read JSON line: the contract's fields, the headline kernel's roofline, the CPU baseline and a small `legs`
-    object of scalars.  Everything else a run measured (every side leg in full) goes to bench_extras.json and to stderr."""
+    object of scalars.  Everything else a run measured (every side leg in full) goes to bench_extras.json and to stderr.
+    extras_file=None is the line of a plain run, which has neither legs nor such a file."""
     cfg = res.get("config") or {}
     rf = res.get("roofline") or {}
     cb = res.get("cpu_baseline")
@@ -608,8 +622,9 @@ def compact_record(res):
     put("c5_scan_frac", _g(res, "baseline_configs_2_and_4", "configs[4]", "roofline", "frac"))
     for b_ in ("1", "64", "1024"):
         put(f"batch{b_}_p50_ms", _g(res, "batch_sweep", b_, "single_call_latency_ms"))
-    out["legs"] = legs
-    out["extras_file"] = "bench_extras.json"
+    if extras_file:
+        out["legs"] = legs
+        out["extras_file"] = extras_file
     line = json.dumps(out, separators=(",", ":"))
     while len(line) > LINE_LIMIT and legs:   # never again a line the driver cannot read: drop legs from the end, keep the contract
         legs.pop(next(reversed(legs)))
@@ -617,18 +632,17 @@ def compact_record(res):
     return out, line
 
 
-def emit(res):
-    """full record -> bench_extras.json (next to bench.py, and under gpurun_out/ when that exists) + stderr; compact line -> stdout, last"""
+def emit(res, full_run):
+    """compact line -> stdout, last; before it the whole record -> stderr and, of a --full run, -> bench_extras.json next to bench.py"""
     full = json.dumps(res)
-    for d_ in (ROOT, os.path.join(ROOT, "gpurun_out")):
+    if full_run:
         try:
-            if os.path.isdir(d_):
-                with open(os.path.join(d_, "bench_extras.json"), "w") as f:
-                    f.write(full + "\n")
+            with open(os.path.join(ROOT, "bench_extras.json"), "w") as f:
+                f.write(full + "\n")
         except OSError as e:
-            log(f"[bench] could not write bench_extras.json in {d_}: {e!r}")
-    log("[bench] full record (bench_extras.json): " + full)
-    _, line = compact_record(res)
+            log(f"[bench] could not write bench_extras.json: {e!r}")
+    log("[bench] full record" + (" (bench_extras.json): " if full_run else ": ") + full)
+    _, line = compact_record(res, "bench_extras.json" if full_run else None)
     sys.stderr.flush()
     print(line, flush=True)
 
@@ -748,15 +762,18 @@ def cluster_main(a):
     st = [s.launch_stats(min(a.steps, 64)) for s in shards]
     kernel_ms = float(np.mean([c["kernel_ms"] for c in st[0]]))
     alg_bytes = float(np.mean([c["bytes"] for c in st[0]]))
-    # two callers in flight (the cluster keeps two lanes: call i+1 walks while call i exchanges / merges / copies)
+    # --full: two callers in flight (the cluster keeps two lanes: call i+1 walks while call i exchanges / merges / copies)
     def loop(m):
         for _ in range(m):
             cl.search_batch(Q, k, ef)
-    th = [threading.Thread(target=loop, args=(max(1, a.steps // 2),)) for _ in range(2)]
-    t0 = time.perf_counter()
-    [t.start() for t in th]
-    [t.join() for t in th]
-    t2 = (time.perf_counter() - t0) / (2 * max(1, a.steps // 2))
+    two_callers = None
+    if a.full:
+        th = [threading.Thread(target=loop, args=(max(1, a.steps // 2),)) for _ in range(2)]
+        t0 = time.perf_counter()
+        [t.start() for t in th]
+        [t.join() for t in th]
+        t2 = (time.perf_counter() - t0) / (2 * max(1, a.steps // 2))
+        two_callers = {"ms_per_batch": round(t2 * 1e3, 4), "qps": round(B / t2, 1)}
     res = {
         "metric": "QPS at recall@10>=0.95, 1Mx768 cosine k=10",
         "value": round(B * a.steps / elapsed, 1),
@@ -767,7 +784,7 @@ def cluster_main(a):
         "route": "single process, kdb_cluster_create / kdb_sharded_search_batch",
         "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(elapsed / a.steps * 1e3, 4), "higher_is_better": True,
         "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic", "recall_at_10": round(recall, 4),
-        "two_callers_in_flight": {"ms_per_batch": round(t2 * 1e3, 4), "qps": round(B / t2, 1)},
+        "two_callers_in_flight": two_callers,
         "config": {
             "workload": f"{G} id-range shards of {n}x{dim} cosine k={k} (corpus {G * n} rows), batched-query HNSW per shard + RCCL all-gather of the "
                         f"per-shard top-k + merge (M=16, efConstruction={a.efc}, efSearch={ef}, batch {B} queries/step)",

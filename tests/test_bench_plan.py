@@ -58,6 +58,31 @@ def test_the_bench_line_stays_machine_readable():
     assert len(line2.encode()) <= 6000 and json.loads(line2)["roofline"]["frac"] == full["roofline"]["frac"]
 
 
+def test_the_line_of_a_plain_run_carries_the_contract_and_no_legs():
+    """a run without --full measured no side leg and wrote no bench_extras.json: its line says neither"""
+    import bench
+    full = json.load(open(os.path.join(ROOT, "profiles", "bench_r05h.json")))
+    plain = {k: v for k, v in full.items() if k in ("metric", "value", "unit", "n_gpus", "rccl_ranks_seen", "steps", "warmup", "ms_per_step",
+                                                    "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "recall_at_10", "config",
+                                                    "roofline")}
+    rec, line = bench.compact_record(plain, None)
+    back = json.loads(line)
+    assert "legs" not in back and "extras_file" not in back and "cpu_baseline" not in back
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "recall_at_10"):
+        assert back[key] == full[key], key
+    assert back["roofline"]["frac"] == full["roofline"]["frac"]
+
+
+def test_full_is_an_option_and_legs_needs_it():
+    rc, plan, err = _plan("--gpus", "1", "--steps", "5", "--warmup", "2", "--full")
+    assert rc == 0 and plan["fits"], (plan, err)
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--legs", "heap_order", "--dry-run"], capture_output=True, text=True,
+                       timeout=300)
+    assert p.returncode == 2 and "--full" in p.stderr
+    rc, plan, err = _plan("--full", "--legs", "heap_order")
+    assert rc == 0, err
+
+
 def test_steps_below_one_is_refused():
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0", "--dry-run"], capture_output=True, text=True,
                        timeout=300)

@@ -54,6 +54,52 @@ def test_bench_cluster_two_shards_one_process():
     assert line["config"]["total_rows"] == 40000
 
 
+PLAIN = ["--gpus", "1", "--rows", "20000", "--dim", "64", "--batch", "512", "--steps", "3", "--warmup", "1", "--efc", "60", "--build-batch", "2048"]
+
+
+def _extras_stamp():
+    try:
+        return os.stat(os.path.join(ROOT, "bench_extras.json")).st_mtime_ns
+    except FileNotFoundError:
+        return None
+
+
+def test_a_plain_run_measures_the_headline_and_nothing_else():
+    """`bench.py --gpus 1 --steps N --warmup W` with no --full: the contract's fields and the roofline of the timed launches' own HIP
+    events; no CPU baseline, no side leg, no measured ceiling, no counter pass, no bench_extras.json"""
+    before = _extras_stamp()
+    p, line = _run(PLAIN)
+    assert p.returncode == 0, p.stderr[-2000:]
+    assert line is not None, p.stdout[-2000:]
+    assert line["metric"].startswith("QPS at recall@10") and line["unit"] == "queries/s" and line["higher_is_better"] is True
+    assert line["dtype"] == "f32" and line["n_gpus"] == 1 and line["steps"] == 3 and line["warmup"] == 1
+    assert line["ms_per_step"] > 0 and line["value"] == pytest.approx(512 / (line["ms_per_step"] * 1e-3), rel=1e-3)
+    assert line["recall_at_10"] >= 0.9 and line["roofline"]["kernel_ms"] > 0
+    for moved in ("cpu_baseline", "legs", "extras_file"):
+        assert moved not in line, moved
+    assert line["roofline"]["traffic"] is None and "frac_of_measured" not in line["roofline"]
+    assert "pcie_inclusive_qps" not in line["config"]
+    assert "cpu baseline" not in p.stderr and "pmc pass" not in p.stderr
+    assert _extras_stamp() == before
+
+
+def test_full_runs_what_a_plain_run_leaves_out():
+    """--full (here: one side leg, no counter passes, a short CPU baseline): the same headline fields, and beside them the CPU baseline,
+    the leg, the measured ceilings and the full record in bench_extras.json"""
+    p, line = _run(PLAIN + ["--full", "--legs", "pcie_inclusive", "--no-pmc", "--cpu-seconds", "0.2"])
+    assert p.returncode == 0, p.stderr[-2000:]
+    assert line is not None, p.stdout[-2000:]
+    assert line["value"] > 0 and line["ms_per_step"] > 0 and line["recall_at_10"] >= 0.9
+    assert line["cpu_baseline"]["value"] > 0 and line["cpu_baseline"]["kind"] == "port"
+    assert line["roofline"]["frac_of_measured"] > 0
+    assert line["config"]["pcie_inclusive_qps"] > 0
+    assert line["extras_file"] == "bench_extras.json"
+    full = json.load(open(os.path.join(ROOT, "bench_extras.json")))
+    assert full["value"] == line["value"] and full["pcie_inclusive"]["512"]["qps"] == line["config"]["pcie_inclusive_qps"]
+    assert full["ground_truth_check"]["id_agreement_with_torch_topk"] > 0.99
+    assert full["roofline"]["measured_ceilings"]["streaming_read_GBps"] > 0
+
+
 def test_bench_reference_benchmark_shapes():
     """`bench.py --shapes`: the reference's published benchmarks (GloVe-100/200/300 cosine, SIFT-1M L2 at the published M /
     efConstruction / efSearch) on synthetic rows of those shapes -- built on the GPU, searched, recall measured against the exact
