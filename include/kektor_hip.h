@@ -22,6 +22,8 @@
  *   kdb_index_mark_deleted  Node.Deleted soft delete (hnsw_index.go:2303)
  *   kdb_index_build         addBatchInternal (hnsw_index.go:1479-2088), phases 1-4, on the GPU (fast linking)
  *   kdb_index_add_batch     the same phases with the reference's own linking: lists equal the restated batch insert's
+ *   kdb_index_refine        GraphOptimizer.Refine / RunTurboRefine (pkg/core/hnsw/optimizer.go:288-560, :679-719): every
+ *                           selected node re-linked against the graph as the call found it
  *   kdb_merge_topk          the merge step of the id-range shard (no reference
  *                           counterpart -- the reference is single process)
  *   kdb_sharded_search_batch  the same path over every GPU of a node from ONE process: fan-out,
@@ -333,6 +335,36 @@ KDB_API int kdb_index_build(kdb_index *idx, uint32_t count, const kdb_build_para
 #define KDB_ADD_REFERENCE_LINKS 1u /* (the only linking this entry point has; accepted for symmetry with kdb_build_params.flags) */
 KDB_API int kdb_index_add_batch(kdb_index *idx, uint32_t first_id, uint32_t n, const uint8_t *levels, uint32_t ef_construction,
                                 uint32_t flags);
+
+/* GraphOptimizer.Refine (pkg/core/hnsw/optimizer.go:288-464; MaintenanceRun("refine"), RunTurboRefine :679-719) on the device:
+ * the neighbour lists of the selected nodes are computed again against the graph AS THE CALL FOUND IT and replace the stored
+ * ones.  ids == NULL: every live node 1..count (what Refine() does as written: its collection loop, :340-346, ignores the
+ * cursor range); otherwise n ids in host memory -- 0 or an id above count: KDB_ERR_INVALID, nothing touched; deleted ids are
+ * skipped (:341); an id named twice is refined once.  Per node x and level l <= level(x), computeNewConnections (:466-560):
+ *   1. searchLayer(stored row of x, the index's entry point, ef, l) started ON level l (no descent), visited set per layer;
+ *      deleted nodes are traversed, never returned; int8: the packed row with its stored norm (0 -> 1);
+ *   2. the current neighbours of x at l that the walk did not return, exist and are not deleted, with their node-to-node distance;
+ *   3. without x itself;   4. sorted by (distance, id) -- the reference's sort.Slice leaves equal distances undefined; this is
+ *      the tie rule of kdb_index_add_batch;   5. selectNeighbors(.., mMax0 at level 0, m above) replaces the list (possibly empty).
+ * Links are one-directional: no reverse requests.  Entry point, maxLevel, levels and deleted bits do not change.
+ * SNAPSHOT: the new lists are staged in device scratch and committed by one kernel after every selected node has been
+ * searched and selected (phase 1 / phase 2 of the reference, :354-461), so a node never sees another node's new list and the
+ * result does not depend on chunk_nodes.  Everything is allocated up front: a failure before the commit leaves the graph as
+ * it was.  Vacuum's reconnectNode loop (:200-221) is sequential -- each repair walks lists earlier repairs rewrote -- and is
+ * NOT mirrored; a host that wants repair after deletes calls this with the ids of the nodes that hold a dead link, or with
+ * every node.  float32 / float16 / int8, ef up to 512, mMax0 <= 64.  A writer like kdb_index_add_batch.                   */
+typedef struct {
+    uint32_t ef_construction; /* 0 = the index's; 1..512 */
+    uint32_t flags;           /* 0 */
+    uint32_t chunk_nodes;     /* nodes searched per scratch chunk (bounds the candidate arrays); 0 = library default (65536) */
+} kdb_refine_params;
+typedef struct {
+    uint64_t nodes_refined;      /* live nodes selected, each counted once */
+    uint64_t lists_written;      /* (node, level) lists replaced */
+    uint64_t lists_changed;      /* ... of which at least one stored word differs from before */
+    uint64_t dead_links_dropped; /* entries of the replaced lists that named a deleted node (or no node) */
+} kdb_refine_stats;
+KDB_API int kdb_index_refine(kdb_index *idx, const uint32_t *ids, uint32_t n, const kdb_refine_params *params, kdb_refine_stats *out);
 
 /* TEST HOOK -- selectNeighbors (hnsw_index.go:2629-2701) exactly as the GPU builder runs it (build_select_kernel's
  * workgroup routine), on caller-supplied candidate lists: list t holds cand_cnt[t] <= stride <= 576 entries at

@@ -105,6 +105,18 @@ class Index {
         kdb_build_params p{batch, 0, seed, 0, 0};
         check(kdb_index_build(h_, count, &p), "build");
     }
+    // GraphOptimizer.Refine (optimizer.go:288-464) on the device: the lists of `ids` (empty: every live node) against the graph as it is
+    kdb_refine_stats Refine(const std::vector<uint32_t> &ids = {}, uint32_t efConstruction = 0, uint32_t chunkNodes = 0) {
+        kdb_refine_params p{efConstruction, 0, chunkNodes};
+        kdb_refine_stats st{};
+        check(kdb_index_refine(h_, ids.empty() ? nullptr : ids.data(), (uint32_t)ids.size(), &p, &st), "refine");
+        return st;
+    }
+    kdb_refine_stats RunTurboRefine() { // optimizer.go:679-719: the whole graph, then SetNeedsRefine(false) (:716)
+        kdb_refine_stats st = Refine();
+        needsRefine_ = false;
+        return st;
+    }
     // incremental refresh of the mirror after writers touched a few nodes (see kdb_index_append_nodes)
     void AppendNodes(uint32_t firstID, const std::vector<uint8_t> &levels) {
         check(kdb_index_append_nodes(h_, firstID, (uint32_t)levels.size(), levels.data()), "append_nodes");

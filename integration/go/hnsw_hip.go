@@ -266,6 +266,27 @@ func (m *gpuMirror) uploadGraph(h *Index, nodes []*Node, count uint32) error {
 	return nil
 }
 
+// refineHIP: what GraphOptimizer.RunTurboRefine / MaintenanceRun("refine") call under the tag (optimizer.go:288-464, :679-719):
+// every live node of the mirror is re-linked on the device against the graph as the call finds it (ids == nil), or only
+// `ids` -- e.g. the nodes that hold a link to a deleted node, the repair a host wants after deletes (Vacuum's sequential
+// reconnectNode loop is not mirrored).  The host then reads the lists back (kdb_index_download_graph) into Node.Connections,
+// or keeps searching on the device.  RunTurboRefine ends with h.SetNeedsRefine(false) as before (:716).
+func (m *gpuMirror) refineHIP(h *Index, ids []uint32) (C.kdb_refine_stats, error) {
+	var st C.kdb_refine_stats
+	if err := m.refresh(h); err != nil {
+		return st, err
+	}
+	var p *C.uint32_t
+	if len(ids) > 0 {
+		p = (*C.uint32_t)(unsafe.Pointer(&ids[0]))
+	}
+	params := C.kdb_refine_params{ef_construction: C.uint32_t(h.efConstruction)}
+	if rc := C.kdb_index_refine(m.h, p, C.uint32_t(len(ids)), &params, &st); rc != 0 {
+		return st, hipErr("kdb_index_refine")
+	}
+	return st, nil
+}
+
 func (m *gpuMirror) destroy() {
 	m.mu.Lock()
 	defer m.mu.Unlock()

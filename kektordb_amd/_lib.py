@@ -25,7 +25,7 @@ ABI_SYMBOLS = [
     "kdb_distance_batch_dev", "kdb_index_build", "kdb_merge_topk", "kdb_merge_topk_dev", "kdb_merge_topk_packed_dev", "kdb_search_batch_multi_dev", "kdb_index_append_nodes", "kdb_index_patch_adjacency", "kdb_index_set_entry", "kdb_flat_scan_groups_dev", "kdb_get_counters", "kdb_get_launch_stats",
     "kdb_index_sync", "kdb_index_set_launch_timing", "kdb_test_select_neighbors", "kdb_cluster_create", "kdb_cluster_destroy", "kdb_cluster_info",
     "kdb_sharded_search_batch", "kdb_sharded_flat_scan_batch", "kdb_index_compress", "kdb_index_get_quantizer", "kdb_index_add_batch", "kdb_merge_topk_packed_f64_dev",
-    "kdb_cluster_comm_info", "kdb_cluster_debug_fail_next", "kdb_index_reserve", "kdb_index_drop_f16_shadow", "kdb_probe_gather", "kdb_probe_stream", "kdb_probe_poison_lds", "kdb_index_caller_stats", "kdb_merge_topk_f64",
+    "kdb_cluster_comm_info", "kdb_cluster_debug_fail_next", "kdb_index_reserve", "kdb_index_drop_f16_shadow", "kdb_probe_gather", "kdb_probe_stream", "kdb_probe_poison_lds", "kdb_index_caller_stats", "kdb_merge_topk_f64", "kdb_index_refine",
 ]
 
 
@@ -53,6 +53,15 @@ class Counters(C.Structure):
 class BuildParams(C.Structure):
     _fields_ = [("batch", C.c_uint32), ("ef_construction", C.c_uint32), ("seed", C.c_uint64),
                 ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class RefineParams(C.Structure):
+    _fields_ = [("ef_construction", C.c_uint32), ("flags", C.c_uint32), ("chunk_nodes", C.c_uint32)]
+
+
+class RefineStats(C.Structure):
+    _fields_ = [("nodes_refined", C.c_uint64), ("lists_written", C.c_uint64), ("lists_changed", C.c_uint64),
+                ("dead_links_dropped", C.c_uint64)]
 
 
 def build_library(force: bool = False) -> str:
@@ -114,6 +123,7 @@ def load():
     L.kdb_distance_batch_dev.argtypes = [vp, vp, u32, vp, u32, u32, vp, vp]
     L.kdb_index_build.argtypes = [vp, u32, C.POINTER(BuildParams)]
     L.kdb_index_add_batch.argtypes = [vp, u32, u32, vp, u32, u32]
+    L.kdb_index_refine.argtypes = [vp, vp, u32, C.POINTER(RefineParams), C.POINTER(RefineStats)]
     L.kdb_merge_topk.argtypes = [u32, u32, u32, u32, u32, vp, vp, vp, vp, vp, vp, vp]
     L.kdb_merge_topk_f64.argtypes = [u32, u32, u32, vp, vp, vp, vp, vp, vp, vp]
     L.kdb_merge_topk_dev.argtypes = [vp, u32, u32, u32, vp, vp, vp, vp, vp, vp, vp, vp]

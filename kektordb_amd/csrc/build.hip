@@ -81,13 +81,9 @@ struct BuildViewT {
     uint32_t n_tasks;
 };
 
-// ---- phase 1 ------------------------------------------------------------------------------------
-template <int METRIC, int BS, int PREC>
-__global__ void __launch_bounds__(64)
-build_search_kernel(KdbView v, BuildViewT<typename BKey<PREC>::T> bv, uint32_t beam_cap, uint32_t nr_cap, uint32_t *visited_pool, uint32_t *work) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    constexpr bool I8 = PREC == KDB_PREC_I8;
-    WaveLds s;
+// the LDS of one walking wave (build_search_kernel, refine_search_kernel): query row | beam (BS == 0) | traversal-only list | hop scratch | marks
+template <int BS, bool I8>
+__device__ __forceinline__ void build_search_carve(unsigned char *smem, const KdbView &v, uint32_t beam_cap, uint32_t nr_cap, WaveLds &s) {
     size_t off = 0;
     s.q = reinterpret_cast<float *>(smem + off);
     off += I8 ? (size_t)v.ld : (size_t)v.ld * 4; // int8: the packed row itself (ld is a multiple of 16)
@@ -128,6 +124,38 @@ build_search_kernel(KdbView v, BuildViewT<typename BKey<PREC>::T> bv, uint32_t b
     s.nb_lo = I8 ? reinterpret_cast<uint32_t *>(smem + off) : nullptr; // int8: low words of the 64-bit distance keys
     if (I8) off += 64 * 4;
     s.marks = reinterpret_cast<uint32_t *>(smem + off);
+}
+
+// a node's own stored row becomes the query of its walk (one wave); returns the norm the int8 distance takes with it
+template <int PREC>
+__device__ __forceinline__ float build_load_own_row(const KdbView &v, const WaveLds &s, uint32_t node, int lane) {
+    constexpr bool I8 = PREC == KDB_PREC_I8;
+    float qnorm = 1.f;
+    if constexpr (I8) { // the node's own int8 row is the query (:1805-1813); its norm as distFn takes it (:2411-2418: 0 -> 1)
+        const uint4 *src = reinterpret_cast<const uint4 *>(reinterpret_cast<const int8_t *>(v.rows) + (size_t)node * v.ld);
+        uint4 *dst = reinterpret_cast<uint4 *>(s.q);
+        for (uint32_t i = (uint32_t)lane; i < (v.ld >> 4); i += 64) dst[i] = src[i];
+        qnorm = v.norms[node];
+        if (qnorm == 0.f) qnorm = 1.f;
+    } else if (PREC == KDB_PREC_F16) { // the node's own f16 row, widened (exactly) to the f32 query the search keeps in LDS
+        const uint16_t *src = reinterpret_cast<const uint16_t *>(v.rows) + (size_t)node * v.ld;
+        for (uint32_t i = (uint32_t)lane; i < v.ld; i += 64) s.q[i] = (float)__builtin_bit_cast(_Float16, src[i]);
+    } else {
+        const float4 *src = reinterpret_cast<const float4 *>(reinterpret_cast<const float *>(v.rows) + (size_t)node * v.ld);
+        float4 *dst = reinterpret_cast<float4 *>(s.q);
+        for (uint32_t i = (uint32_t)lane; i < (v.ld >> 2); i += 64) dst[i] = src[i];
+    }
+    return qnorm;
+}
+
+// ---- phase 1 ------------------------------------------------------------------------------------
+template <int METRIC, int BS, int PREC>
+__global__ void __launch_bounds__(64)
+build_search_kernel(KdbView v, BuildViewT<typename BKey<PREC>::T> bv, uint32_t beam_cap, uint32_t nr_cap, uint32_t *visited_pool, uint32_t *work) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    constexpr bool I8 = PREC == KDB_PREC_I8;
+    WaveLds s;
+    build_search_carve<BS, I8>(smem, v, beam_cap, nr_cap, s);
     const int lane = kdb_lane();
     VisBitset vis;
     vis.bits = visited_pool + (size_t)blockIdx.x * v.vis_words;
@@ -141,21 +169,7 @@ build_search_kernel(KdbView v, BuildViewT<typename BKey<PREC>::T> bv, uint32_t b
         const uint32_t node = bv.first + bi;
         const int L = (int)v.levels[node];
         vis.begin_query();
-        float qnorm = 1.f;
-        if constexpr (I8) { // the node's own int8 row is the query (:1805-1813); its norm as distFn takes it (:2411-2418: 0 -> 1)
-            const uint4 *src = reinterpret_cast<const uint4 *>(reinterpret_cast<const int8_t *>(v.rows) + (size_t)node * v.ld);
-            uint4 *dst = reinterpret_cast<uint4 *>(s.q);
-            for (uint32_t i = (uint32_t)lane; i < (v.ld >> 4); i += 64) dst[i] = src[i];
-            qnorm = v.norms[node];
-            if (qnorm == 0.f) qnorm = 1.f;
-        } else if (PREC == KDB_PREC_F16) { // the node's own f16 row, widened (exactly) to the f32 query the search keeps in LDS
-            const uint16_t *src = reinterpret_cast<const uint16_t *>(v.rows) + (size_t)node * v.ld;
-            for (uint32_t i = (uint32_t)lane; i < v.ld; i += 64) s.q[i] = (float)__builtin_bit_cast(_Float16, src[i]);
-        } else {
-            const float4 *src = reinterpret_cast<const float4 *>(reinterpret_cast<const float *>(v.rows) + (size_t)node * v.ld);
-            float4 *dst = reinterpret_cast<float4 *>(s.q);
-            for (uint32_t i = (uint32_t)lane; i < (v.ld >> 2); i += 64) dst[i] = src[i];
-        }
+        const float qnorm = build_load_own_row<PREC>(v, s, node, lane);
         __threadfence_block();
         wave_lds_fence();
         typename std::conditional<BS == 0, LdsBeamT<I8>, RegBeam<(BS == 0 ? 1 : BS), I8>>::type b;
@@ -1412,6 +1426,328 @@ int add_batch_ref_impl(kdb_index *idx, uint32_t first, uint32_t nb, const uint8_
     return KDB_OK;
 }
 
+// =====================================================================================================================
+// Refine (kdb_index_refine): GraphOptimizer.Refine / computeNewConnections (pkg/core/hnsw/optimizer.go:288-560) for a set of
+// nodes against the graph AS THE CALL FOUND IT.  Per selected node x and level l <= level(x):
+//   searchLayer(row of x, entry point, ef, l) from the entry point ON level l, no descent (:490); the current neighbours of x
+//   that the walk did not return, exist and are not deleted are appended with their node-to-node distance (:497-522); x itself
+//   is dropped (:524-536); the rest is sorted -- sort.Slice leaves equal distances undefined, restated as (distance, id), the
+//   rule of the reference linking above -- and pruned by selectNeighbors (:549).  Links are one-directional.
+// Phase 1 of the reference computes every list before phase 2 commits any (:354-461): here the new lists are staged in HBM and
+// one kernel copies them into the adjacency after the last node has been searched and selected.  Only the candidate arrays are
+// chunked (refine_impl), so the result cannot depend on the chunk size.
+// =====================================================================================================================
+template <typename KT>
+struct RefineViewT {
+    const uint32_t *nodes;   // [n_nodes] the selected nodes: live, every id once
+    const uint32_t *task_of; // [n_nodes + 1] first task of a node; level l of nodes[i] is task task_of[i] + l
+    const uint32_t *owner;   // [n_tasks] index into nodes
+    uint32_t *cand_id;       // [chunk tasks * efc] candidates of the chunk in flight
+    KT *cand_key;
+    uint32_t *cand_cnt;      // [chunk tasks]
+    uint32_t *stage_id;      // [n_tasks * mMax0] the new lists, staged until every node is done
+    uint32_t *stage_cnt;     // [n_tasks]
+    uint32_t efc;
+    uint32_t c0, cn;         // the chunk: nodes [c0, c0 + cn)
+    uint32_t t0;             // its first task
+    uint32_t n_tasks;
+};
+
+// one wave per node of the chunk; every level restarts at the entry point with a visited set of its own
+template <int METRIC, int BS, int PREC>
+__global__ void __launch_bounds__(64)
+refine_search_kernel(KdbView v, RefineViewT<typename BKey<PREC>::T> rv, uint32_t beam_cap, uint32_t nr_cap, uint32_t *visited_pool, uint32_t *work) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    constexpr bool I8 = PREC == KDB_PREC_I8;
+    WaveLds s;
+    build_search_carve<BS, I8>(smem, v, beam_cap, nr_cap, s);
+    const int lane = kdb_lane();
+    VisBitset vis;
+    vis.bits = visited_pool + (size_t)blockIdx.x * v.vis_words;
+    vis.words = v.vis_words;
+    vis.marks = s.marks;
+    for (;;) {
+        uint32_t bi = 0;
+        if (lane == 0) bi = atomicAdd(work, 1u);
+        bi = __shfl(bi, 0, 64);
+        if (bi >= rv.cn) break;
+        const uint32_t ni = rv.c0 + bi;
+        const uint32_t node = rv.nodes[ni];
+        const uint32_t t_first = rv.task_of[ni], n_lev = rv.task_of[ni + 1] - t_first;
+        vis.begin_query();
+        const float qnorm = build_load_own_row<PREC>(v, s, node, lane); // the row as stored: not normalised again
+        __threadfence_block();
+        wave_lds_fence();
+        typename std::conditional<BS == 0, LdsBeamT<I8>, RegBeam<(BS == 0 ? 1 : BS), I8>>::type b;
+        b.bind(s);
+        b.tied = 0u;
+        QCtr ctr{};
+        // upper levels first: a layer above 0 un-marks what it marked (VisBitset::end_layer), level 0 starts from a clean set
+        for (int l = (int)n_lev - 1; l >= 0; l--) {
+            search_layer<PREC, METRIC, 0>(v, s, b, vis, nullptr, v.entry, l, rv.efc, qnorm, ctr, EpKnown());
+            const size_t at = (size_t)(t_first - rv.t0 + (uint32_t)l) * rv.efc;
+            uint32_t nc;
+            if constexpr (I8) nc = b.write_results(rv.efc, rv.cand_id + at, nullptr, false, rv.cand_key + at);
+            else nc = b.write_results(rv.efc, rv.cand_id + at, rv.cand_key + at, false);
+            if (lane == 0) rv.cand_cnt[t_first - rv.t0 + (uint32_t)l] = nc;
+        }
+    }
+}
+
+constexpr uint32_t RF_TQ_OFF = 2048; // words of the row tile kept for the unsorted union; the node's own row follows
+static_assert((size_t)PR_MAXC * (sizeof(double) + 4) <= (size_t)RF_TQ_OFF * 4, "the union must fit in front of the row");
+constexpr uint32_t RF_MAX_ROW_BYTES = (uint32_t)((PR_BLK + PR_MAXSEL) * PR_STRIDE - RF_TQ_OFF) * 4u;
+
+// one workgroup per (node, level) of the chunk: candidates + surviving current links -> sorted -> selectNeighbors -> staging
+template <int METRIC, int PREC>
+__global__ void __launch_bounds__(256)
+refine_select_kernel(KdbView v, RefineViewT<typename BKey<PREC>::T> rv) {
+    using KT = typename BKey<PREC>::T;
+    constexpr bool I8 = PREC == KDB_PREC_I8;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    PruneLdsT<KT> p;
+    prune_carve(smem, p);
+    const uint32_t tid = threadIdx.x, lane = tid & 63u;
+    const uint32_t tl = blockIdx.x, task = rv.t0 + tl;
+    const uint32_t oi = rv.owner[task], node = rv.nodes[oi], level = task - rv.task_of[oi];
+    const uint32_t maxm = level == 0 ? v.deg0 : v.deg_up;
+    const uint32_t *adj = level == 0 ? v.adj0 + (size_t)node * v.deg0 : v.adj_up + ((size_t)v.up_idx[node] + (level - 1u)) * v.deg_up;
+    const uint32_t n = rv.cand_cnt[tl];
+    // until select_neighbors_wg runs its tiles are free: the union lives in the row tile, the merge's small arrays in m1
+    KT *u_key = reinterpret_cast<KT *>(p.rows);                     // [PR_MAXC]
+    uint32_t *u_id = reinterpret_cast<uint32_t *>(u_key + PR_MAXC); // [PR_MAXC]
+    float *tq = p.rows + RF_TQ_OFF;                                 // the node's row as the query of the extra distances
+    uint32_t *w_cur = reinterpret_cast<uint32_t *>(p.m1);           // [64] the current list
+    uint32_t *w_in = w_cur + 64;                                    // [64] 1: the walk returned it
+    uint32_t *w_ex = w_cur + 128;                                   // [128] the neighbours to append (64 used)
+    float *w_d = reinterpret_cast<float *>(w_cur + 256);            // [64] their keys
+    uint32_t *w_lo = w_cur + 320;                                   // [64] int8: low words
+    uint32_t &sh_ne = p.misc[2], &sh_self = p.misc[3];
+    for (uint32_t i = tid; i < n; i += 256) {
+        u_id[i] = rv.cand_id[(size_t)tl * rv.efc + i];
+        u_key[i] = rv.cand_key[(size_t)tl * rv.efc + i];
+    }
+    if (tid < 64) {
+        w_cur[tid] = tid < maxm ? adj[tid] : 0u;
+        w_in[tid] = 0u;
+        w_ex[tid] = 0u;
+        w_ex[64 + tid] = 0u;
+    }
+    if (tid == 0) {
+        sh_ne = 0u;
+        sh_self = 0u;
+    }
+    __syncthreads();
+    { // "alreadyIn" (:506-513): four threads per current neighbour, a quarter of the candidates each
+        const uint32_t nb = w_cur[lane];
+        if (nb) {
+            bool hit = false;
+            for (uint32_t i = tid >> 6; i < n; i += 4) hit = hit || (u_id[i] == nb);
+            if (hit) w_in[lane] = 1u;
+        }
+    }
+    __syncthreads();
+    if (tid < 64) { // the neighbours to append, in list order: they exist and are not deleted (:516-517)
+        const uint32_t nb = w_cur[tid];
+        bool keep = nb != 0u && nb <= v.count && !w_in[tid] && !((v.deleted[nb >> 5] >> (nb & 31u)) & 1u);
+        if (keep) // (a list that names a node twice: the first mention is in the union by the time the second is looked at)
+            for (uint32_t j = 0; j < tid; j++)
+                if (w_cur[j] == nb) {
+                    keep = false;
+                    break;
+                }
+        const unsigned long long mk = __ballot(keep);
+        if (keep) w_ex[kdb_mbcnt(mk)] = nb;
+        if (tid == 0) sh_ne = (uint32_t)__builtin_popcountll(mk);
+    }
+    __syncthreads();
+    const uint32_t ne = sh_ne;
+    if (ne) { // distanceBetweenNodes(x, neighbour) (:518): the node's stored row is the query, 16 lanes per row
+        float qnorm = 1.f;
+        if (I8) {
+            const uint4 *src = reinterpret_cast<const uint4 *>(reinterpret_cast<const int8_t *>(v.rows) + (size_t)node * v.ld);
+            for (uint32_t i = tid; i < (v.ld >> 4); i += 256) reinterpret_cast<uint4 *>(tq)[i] = src[i];
+            qnorm = v.norms[node]; // (a zero norm on either side: distance 1, see rl_commit_body)
+            if (qnorm == 0.f) qnorm = 1.f;
+        } else if (PREC == KDB_PREC_F16) {
+            const uint16_t *src = reinterpret_cast<const uint16_t *>(v.rows) + (size_t)node * v.ld;
+            for (uint32_t i = tid; i < v.ld; i += 256) tq[i] = (float)__builtin_bit_cast(_Float16, src[i]);
+        } else {
+            const float4 *src = reinterpret_cast<const float4 *>(reinterpret_cast<const float *>(v.rows) + (size_t)node * v.ld);
+            for (uint32_t i = tid; i < (v.ld >> 2); i += 256) reinterpret_cast<float4 *>(tq)[i] = src[i];
+        }
+        __syncthreads();
+        if (tid < 64) {
+            WaveLds s{};
+            s.q = tq;
+            s.nb_id = w_ex;
+            s.nb_d = w_d;
+            s.nb_lo = I8 ? w_lo : nullptr;
+            compute_dists<PREC, METRIC, 0>(v, s, ne, qnorm);
+            wave_lds_fence();
+            if (tid < ne) {
+                u_id[n + tid] = w_ex[tid];
+                if constexpr (I8) u_key[n + tid] = kdb_i8_key_double(w_d[tid], w_lo[tid]);
+                else u_key[n + tid] = w_d[tid];
+            }
+        }
+        __syncthreads();
+    }
+    // without x itself (:526), ascending by (distance, id): every entry counts the entries before it
+    const uint32_t nu = n + ne;
+    for (uint32_t i = tid; i < nu; i += 256) {
+        const uint32_t id = u_id[i];
+        if (id == node) {
+            atomicAdd(&sh_self, 1u);
+            continue;
+        }
+        const KT k = u_key[i];
+        uint32_t rank = 0;
+        for (uint32_t j = 0; j < nu; j++) {
+            const uint32_t idj = u_id[j];
+            rank += (idj != node && key_before(u_key[j], idj, k, id)) ? 1u : 0u;
+        }
+        p.c_id[rank] = id;
+        p.c_key[rank] = k;
+    }
+    __syncthreads();
+    const uint32_t nv = nu - sh_self; // (from here on the tiles the union lived in are select_neighbors_wg's again)
+    select_neighbors_wg<METRIC, PREC>(v, p, nv, maxm);
+    const uint32_t nsel = p.misc[0];
+    if (tid < nsel) rv.stage_id[(size_t)task * v.deg0 + tid] = p.s_id[tid];
+    if (tid == 0) rv.stage_cnt[task] = nsel;
+}
+
+// the staged lists replace the stored ones, tails zero-filled; one wave per (node, level).  out[0]: lists whose words changed,
+// out[1]: links of the old lists that named a deleted (or no) node
+template <typename KT>
+__global__ void __launch_bounds__(256)
+refine_commit_kernel(KdbView v, RefineViewT<KT> rv, uint32_t *adj0, uint32_t *adj_up, unsigned long long *out) {
+    __shared__ uint32_t sh[2];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u;
+    if (tid < 2) sh[tid] = 0u;
+    __syncthreads();
+    const uint32_t task = blockIdx.x * 4u + (tid >> 6);
+    if (task < rv.n_tasks) {
+        const uint32_t oi = rv.owner[task], node = rv.nodes[oi], level = task - rv.task_of[oi];
+        const uint32_t maxm = level == 0 ? v.deg0 : v.deg_up;
+        uint32_t *adj = level == 0 ? adj0 + (size_t)node * v.deg0 : adj_up + ((size_t)v.up_idx[node] + (level - 1u)) * v.deg_up;
+        const uint32_t cnt = rv.stage_cnt[task];
+        const uint32_t old = lane < maxm ? adj[lane] : 0u;
+        const uint32_t nw = lane < cnt ? rv.stage_id[(size_t)task * v.deg0 + lane] : 0u;
+        const bool dead = old != 0u && (old > v.count || ((v.deleted[old >> 5] >> (old & 31u)) & 1u));
+        const bool changed = __ballot(old != nw) != 0ull;
+        const uint32_t n_dead = (uint32_t)__builtin_popcountll(__ballot(dead));
+        if (lane < maxm) adj[lane] = nw;
+        if (lane == 0) {
+            if (changed) atomicAdd(&sh[0], 1u);
+            if (n_dead) atomicAdd(&sh[1], n_dead);
+        }
+    }
+    __syncthreads();
+    if (tid < 2 && sh[tid]) atomicAdd(&out[tid], (unsigned long long)sh[tid]);
+}
+
+// nodes: live, unique, 1..count.  Every allocation and attribute call comes first; the adjacency is written by the last kernel only.
+template <int METRIC, int PREC>
+int refine_impl(kdb_index *idx, const std::vector<uint32_t> &nodes, uint32_t efc, uint32_t chunk_nodes, kdb_refine_stats *out) {
+    using KT = typename BKey<PREC>::T;
+    constexpr size_t KB = sizeof(KT);
+    hipStream_t s = idx->stream;
+    const uint32_t nn = (uint32_t)nodes.size();
+    std::vector<uint32_t> task_of((size_t)nn + 1), owner;
+    owner.reserve((size_t)nn + nn / 8 + 16);
+    for (uint32_t i = 0; i < nn; i++) {
+        task_of[i] = (uint32_t)owner.size();
+        int lv = (int)idx->h_levels[nodes[i]];
+        if (lv > idx->max_level) lv = idx->max_level;
+        owner.insert(owner.end(), (size_t)lv + 1, i);
+    }
+    if (owner.size() > 0xfffffff0ull) {
+        kdb_set_error("refine: too many (node, level) lists for one call");
+        return KDB_ERR_UNSUPPORTED;
+    }
+    const uint32_t n_tasks = (uint32_t)owner.size();
+    task_of[nn] = n_tasks;
+    if (chunk_nodes == 0) chunk_nodes = 65536u;
+    if (chunk_nodes > nn) chunk_nodes = nn;
+    uint32_t chunk_tasks = 0;
+    for (uint32_t c0 = 0; c0 < nn; c0 += chunk_nodes) {
+        const uint32_t c1 = nn - c0 < chunk_nodes ? nn : c0 + chunk_nodes;
+        chunk_tasks = std::max(chunk_tasks, task_of[c1] - task_of[c0]);
+    }
+    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    size_t off = 0;
+    auto take = [&](size_t bytes) { size_t o = off; off += al(bytes); return o; };
+    const size_t o_ckey = take((size_t)chunk_tasks * efc * KB), o_cid = take((size_t)chunk_tasks * efc * 4), o_ccnt = take((size_t)chunk_tasks * 4);
+    const size_t o_nodes = take((size_t)nn * 4), o_taskof = take(((size_t)nn + 1) * 4), o_owner = take((size_t)n_tasks * 4);
+    const size_t o_stage = take((size_t)n_tasks * idx->deg0 * 4), o_scnt = take((size_t)n_tasks * 4), o_out = take(256);
+    if (idx->build_bytes < off) {
+        if (idx->d_build) KDB_HIP(hipFree(idx->d_build));
+        idx->d_build = nullptr;
+        idx->build_bytes = 0;
+        KDB_HIP(hipMalloc(&idx->d_build, off));
+        idx->build_bytes = off;
+    }
+    const uint32_t beam_cap = ((efc + 64 + 1) + 63) / 64 * 64;
+    const int bs = kdb_beam_slots(efc) == 0 ? 0 : kdb_beam_slots(efc) < 2 ? 2 : kdb_beam_slots(efc);
+    const uint32_t nr_cap = ((idx->n_deleted < 2047u ? idx->n_deleted : 2047u) + 1u + 3u) & ~3u; // traversal-only candidates (deleted nodes)
+    const size_t lds_search = (PREC == KDB_PREC_I8 ? (size_t)idx->ld + 64 * 12 : (size_t)idx->ld * 4 + 64 * 8) + KDB_UP_MARK_CAP * 4 +
+                              (bs == 0 ? (size_t)beam_cap * (PREC == KDB_PREC_I8 ? 12 : 8) : 0) + (size_t)nr_cap * (PREC == KDB_PREC_I8 ? 12 : 8);
+    const size_t lds_prune = prune_lds_bytes<KT>();
+    auto ksearch = bs == 0 ? refine_search_kernel<METRIC, 0, PREC> : bs == 2 ? refine_search_kernel<METRIC, 2, PREC> : refine_search_kernel<METRIC, 4, PREC>;
+    auto kselect = refine_select_kernel<METRIC, PREC>;
+    if (lds_search > 64 * 1024) KDB_HIP(hipFuncSetAttribute((const void *)ksearch, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_search));
+    if (lds_prune > 64 * 1024) KDB_HIP(hipFuncSetAttribute((const void *)kselect, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_prune));
+    const uint32_t slots_vis = (uint32_t)idx->n_cu * (uint32_t)occupancy_blocks(ksearch, 64, lds_search);
+    int rc = kdb_ensure_visited(idx, slots_vis, s);
+    if (rc) return rc;
+    unsigned char *w = reinterpret_cast<unsigned char *>(idx->d_build);
+    RefineViewT<KT> rv{};
+    rv.nodes = reinterpret_cast<uint32_t *>(w + o_nodes);
+    rv.task_of = reinterpret_cast<uint32_t *>(w + o_taskof);
+    rv.owner = reinterpret_cast<uint32_t *>(w + o_owner);
+    rv.cand_id = reinterpret_cast<uint32_t *>(w + o_cid);
+    rv.cand_key = reinterpret_cast<KT *>(w + o_ckey);
+    rv.cand_cnt = reinterpret_cast<uint32_t *>(w + o_ccnt);
+    rv.stage_id = reinterpret_cast<uint32_t *>(w + o_stage);
+    rv.stage_cnt = reinterpret_cast<uint32_t *>(w + o_scnt);
+    rv.efc = efc;
+    rv.n_tasks = n_tasks;
+    unsigned long long *d_out = reinterpret_cast<unsigned long long *>(w + o_out);
+    KDB_HIP(hipMemcpyAsync(w + o_nodes, nodes.data(), (size_t)nn * 4, hipMemcpyHostToDevice, s));
+    KDB_HIP(hipMemcpyAsync(w + o_taskof, task_of.data(), ((size_t)nn + 1) * 4, hipMemcpyHostToDevice, s));
+    KDB_HIP(hipMemcpyAsync(w + o_owner, owner.data(), (size_t)n_tasks * 4, hipMemcpyHostToDevice, s));
+    KDB_HIP(hipMemsetAsync(d_out, 0, 256, s));
+    const KdbView v = kdb_make_view(idx);
+    // ---- every node searches and selects against the graph as it is: nothing below writes an adjacency word ...
+    for (uint32_t c0 = 0; c0 < nn; c0 += chunk_nodes) {
+        rv.c0 = c0;
+        rv.cn = nn - c0 < chunk_nodes ? nn - c0 : chunk_nodes;
+        rv.t0 = task_of[c0];
+        const uint32_t ct = task_of[c0 + rv.cn] - rv.t0;
+        KDB_HIP(hipMemsetAsync(rv.cand_cnt, 0, (size_t)ct * 4, s));
+        KDB_HIP(hipMemsetAsync(idx->d_work, 0, 4, s));
+        hipLaunchKernelGGL(ksearch, dim3(slots_vis < rv.cn ? slots_vis : rv.cn), dim3(64), lds_search, s, v, rv, beam_cap, nr_cap, idx->d_visited, idx->d_work);
+        KDB_HIP(hipGetLastError());
+        hipLaunchKernelGGL(kselect, dim3(ct), dim3(256), lds_prune, s, v, rv);
+        KDB_HIP(hipGetLastError());
+    }
+    KDB_HIP(hipStreamSynchronize(s)); // (a fault of a walk shows here, before the graph is touched)
+    // ---- ... and one kernel commits
+    hipLaunchKernelGGL((refine_commit_kernel<KT>), dim3((n_tasks + 3u) / 4u), dim3(256), 0, s, v, rv, idx->d_adj0, idx->d_adj_up, d_out);
+    KDB_HIP(hipGetLastError());
+    unsigned long long h_out[2] = {0, 0};
+    KDB_HIP(hipMemcpyAsync(h_out, d_out, 16, hipMemcpyDeviceToHost, s));
+    KDB_HIP(hipStreamSynchronize(s));
+    out->nodes_refined = nn;
+    out->lists_written = n_tasks;
+    out->lists_changed = h_out[0];
+    out->dead_links_dropped = h_out[1];
+    return KDB_OK;
+}
+
+
 } // namespace
 
 // d_keys: float keys for float32 / float16 indexes, DOUBLE distances for int8 indexes (the reference's float64)
@@ -1488,4 +1824,49 @@ int kdb_add_batch_ref(kdb_index *idx, uint32_t first_id, uint32_t n, const uint8
     if (idx->desc.precision == KDB_PREC_I8) return add_batch_ref_impl<KDB_METRIC_COSINE, KDB_PREC_I8>(idx, first_id, n, levels, efc);
     return idx->desc.metric == KDB_METRIC_COSINE ? add_batch_ref_impl<KDB_METRIC_COSINE, KDB_PREC_F32>(idx, first_id, n, levels, efc)
                                                  : add_batch_ref_impl<KDB_METRIC_L2, KDB_PREC_F32>(idx, first_id, n, levels, efc);
+}
+
+// GraphOptimizer.Refine (optimizer.go:288-464) for the nodes `ids` (null: every node 1..count), deleted ones skipped (:341)
+int kdb_refine_graph(kdb_index *idx, const uint32_t *ids, uint32_t n, uint32_t ef_construction, uint32_t chunk_nodes, kdb_refine_stats *out) {
+    const uint32_t efc = ef_construction ? ef_construction : idx->desc.ef_construction;
+    kdb_refine_stats st{};
+    if (!idx->has_graph || idx->max_level < 0 || idx->entry == 0 || idx->h_levels.size() != (size_t)idx->count + 1) {
+        kdb_set_error("refine: the index holds no graph");
+        return KDB_ERR_STATE;
+    }
+    if (efc < 1 || efc > KDB_MAX_EFC || idx->deg0 > PR_MAXSEL || (size_t)idx->ld * (idx->desc.precision == KDB_PREC_I8 ? 1 : 4) > RF_MAX_ROW_BYTES) {
+        kdb_set_error("refine: ef_construction in 1..%u, mMax0 <= %d, rows of at most %u bytes", KDB_MAX_EFC, PR_MAXSEL, RF_MAX_ROW_BYTES);
+        return KDB_ERR_UNSUPPORTED;
+    }
+    if (ids)
+        for (uint32_t i = 0; i < n; i++)
+            if (ids[i] == 0 || ids[i] > idx->count) {
+                kdb_set_error("refine: ids[%u] = %u outside 1..%u", i, ids[i], idx->count);
+                return KDB_ERR_INVALID;
+            }
+    KDB_HIP(hipDeviceSynchronize()); // walks of callers' streams may still read the lists this call rewrites
+    const size_t dw = ((size_t)idx->count >> 5) + 1;
+    std::vector<uint32_t> del(dw, 0u);
+    if (idx->n_deleted) KDB_HIP(hipMemcpy(del.data(), idx->d_deleted, dw * 4, hipMemcpyDeviceToHost));
+    std::vector<uint32_t> seen(ids ? dw : 0, 0u), nodes;
+    const uint32_t total = ids ? n : idx->count;
+    nodes.reserve(total);
+    for (uint32_t i = 0; i < total; i++) {
+        const uint32_t x = ids ? ids[i] : i + 1u;
+        if ((del[x >> 5] >> (x & 31u)) & 1u) continue;
+        if (ids) { // a node named twice is refined once: both results would come from the same snapshot
+            if ((seen[x >> 5] >> (x & 31u)) & 1u) continue;
+            seen[x >> 5] |= 1u << (x & 31u);
+        }
+        nodes.push_back(x);
+    }
+    int rc = KDB_OK;
+    if (!nodes.empty()) {
+        if (idx->desc.precision == KDB_PREC_F16) rc = refine_impl<KDB_METRIC_L2, KDB_PREC_F16>(idx, nodes, efc, chunk_nodes, &st);
+        else if (idx->desc.precision == KDB_PREC_I8) rc = refine_impl<KDB_METRIC_COSINE, KDB_PREC_I8>(idx, nodes, efc, chunk_nodes, &st);
+        else rc = idx->desc.metric == KDB_METRIC_COSINE ? refine_impl<KDB_METRIC_COSINE, KDB_PREC_F32>(idx, nodes, efc, chunk_nodes, &st)
+                                                        : refine_impl<KDB_METRIC_L2, KDB_PREC_F32>(idx, nodes, efc, chunk_nodes, &st);
+    }
+    if (rc == KDB_OK && out) *out = st;
+    return rc;
 }

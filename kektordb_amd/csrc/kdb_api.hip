@@ -1954,6 +1954,20 @@ extern "C" int kdb_index_add_batch(kdb_index *idx, uint32_t first_id, uint32_t n
     return kdb_add_batch_ref(idx, first_id, n, levels, ef_construction);
 }
 
+extern "C" int kdb_index_refine(kdb_index *idx, const uint32_t *ids, uint32_t n, const kdb_refine_params *params, kdb_refine_stats *out) {
+    KDB_CHECK_IDX(idx);
+    if (params && params->flags) {
+        kdb_set_error("refine: unknown flag");
+        return KDB_ERR_INVALID;
+    }
+    KdbWriteLock wl(idx); // excludes host-pointer calls in flight
+    idx->graph_epoch++;
+    KDB_HIP(hipSetDevice(idx->device));
+    KdbLaneGuard lane(idx, idx->stream);
+    if (lane.rc) return lane.rc;
+    return kdb_refine_graph(idx, ids, n, params ? params->ef_construction : 0u, params ? params->chunk_nodes : 0u, out);
+}
+
 // test hook (see kektor_hip.h): host buffers in, selections out
 extern "C" int kdb_test_select_neighbors(kdb_index *idx, uint32_t n_lists, uint32_t stride, const uint32_t *cand_ids,
                                          const void *cand_keys, const uint32_t *cand_cnt, uint32_t maxm, uint32_t *out_ids,

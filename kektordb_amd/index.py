@@ -215,6 +215,24 @@ class HipIndex:
         lv = np.ascontiguousarray(levels, dtype=np.uint8)
         check(self.L.kdb_index_add_batch(self.h, int(first_id), lv.size, _ptr(lv), int(ef_construction), 1), "kdb_index_add_batch")
 
+    def refine(self, ids=None, ef_construction: int = 0, chunk_nodes: int = 0) -> dict:
+        """GraphOptimizer.Refine (optimizer.go:288-464) on the device (kdb_index_refine): the lists of `ids` (None: every live
+        node) are computed again against the graph as it is and committed together; -> the call's statistics"""
+        self._live()
+        a = None if ids is None else np.ascontiguousarray(ids, dtype=np.uint32)
+        p = _lib.RefineParams(int(ef_construction), 0, int(chunk_nodes))
+        st = _lib.RefineStats()
+        check(self.L.kdb_index_refine(self.h, _ptr(a), 0 if a is None else a.size, C.byref(p), C.byref(st)), "kdb_index_refine")
+        return {"nodes_refined": int(st.nodes_refined), "lists_written": int(st.lists_written),
+                "lists_changed": int(st.lists_changed), "dead_links_dropped": int(st.dead_links_dropped)}
+
+    def RunTurboRefine(self) -> dict:
+        """RunTurboRefine (optimizer.go:679-719): the whole graph with the index's efConstruction, then needs_refine is
+        cleared (:716)"""
+        st = self.refine()
+        self.needs_refine = False
+        return st
+
     def test_select_neighbors(self, cand_ids, cand_keys, cand_cnt, maxm: int):
         """TEST HOOK: the GPU builder's selectNeighbors on caller-supplied lists ([n_lists, stride] ids / ascending keys;
         keys are float32 ordering keys, or -- int8 indexes -- the float64 distances)"""
