@@ -24,6 +24,8 @@
  *   kdb_index_add_batch     the same phases with the reference's own linking: lists equal the restated batch insert's
  *   kdb_index_refine        GraphOptimizer.Refine / RunTurboRefine (pkg/core/hnsw/optimizer.go:288-560, :679-719): every
  *                           selected node re-linked against the graph as the call found it
+ *   kdb_index_vacuum        GraphOptimizer.Vacuum (optimizer.go:133-277): nodes with links to deleted nodes found and re-linked,
+ *                           the entry point re-elected, the deleted nodes' lists and rows cleared
  *   kdb_merge_topk          the merge step of the id-range shard (no reference
  *                           counterpart -- the reference is single process)
  *   kdb_sharded_search_batch  the same path over every GPU of a node from ONE process: fan-out,
@@ -351,8 +353,9 @@ KDB_API int kdb_index_add_batch(kdb_index *idx, uint32_t first_id, uint32_t n, c
  * searched and selected (phase 1 / phase 2 of the reference, :354-461), so a node never sees another node's new list and the
  * result does not depend on chunk_nodes.  Everything is allocated up front: a failure before the commit leaves the graph as
  * it was.  Vacuum's reconnectNode loop (:200-221) is sequential -- each repair walks lists earlier repairs rewrote -- and is
- * NOT mirrored; a host that wants repair after deletes calls this with the ids of the nodes that hold a dead link, or with
- * every node.  float32 / float16 / int8, ef up to 512, mMax0 <= 64.  A writer like kdb_index_add_batch.                   */
+ * NOT mirrored; a host that wants repair after deletes calls kdb_index_vacuum, which finds the nodes that hold a dead link
+ * on the device (kdb_index_dead_link_scan hands out their ids) and re-links them this way.
+ * float32 / float16 / int8, ef up to 512, mMax0 <= 64.  A writer like kdb_index_add_batch.                                 */
 typedef struct {
     uint32_t ef_construction; /* 0 = the index's; 1..512 */
     uint32_t flags;           /* 0 */
@@ -365,6 +368,59 @@ typedef struct {
     uint64_t dead_links_dropped; /* entries of the replaced lists that named a deleted node (or no node) */
 } kdb_refine_stats;
 KDB_API int kdb_index_refine(kdb_index *idx, const uint32_t *ids, uint32_t n, const kdb_refine_params *params, kdb_refine_stats *out);
+
+/* GraphOptimizer.Vacuum (pkg/core/hnsw/optimizer.go:133-277; MaintenanceRun("vacuum"), hnsw_index.go:976) on the device: what
+ * kdb_index_mark_deleted left behind is repaired and cleared.  A writer like kdb_index_refine (same lock, same device-wide wait).
+ *   1. D = the ids 1..count whose deleted bit is set when the call starts (deletedSet, :143-148).  D empty (:151), no graph or
+ *      entry 0: KDB_OK, ALL-ZERO statistics (entry and max_level fields too), nothing touched.
+ *   2. R = every live node with a dead link on one of its levels 0..min(level(x), maxLevel), ascending (:165-193).  A dead link
+ *      is a non-zero adjacency word that names an id of D or an id outside 1..count -- what kdb_refine_stats.dead_links_dropped
+ *      counts; the zero words behind a list's end are padding.  One streaming kernel over the adjacency writes a flag bitmap.
+ *   3. Every node of R is re-linked exactly as kdb_index_refine(ids = R) does it, SNAPSHOT semantics included: under a writer's
+ *      lock ignoreSet equals the deleted bits, and reconnectNode (:565-674) is step for step computeNewConnections (:466-560).
+ *      The reference's loop (:200-221) commits each node before the next one walks; that ORDER IS NOT MIRRORED, for the reason
+ *      given above for Refine: every repair would walk lists earlier repairs rewrote, one node at a time.  The walks start at
+ *      the entry point as the call found it, dead or not.
+ *   4. Entry point (:232-250), after the commit: a live entry is never changed.  A deleted one is replaced by the LOWEST LIVE ID
+ *      and maxLevel becomes THAT node's level (the reference's rule as written: on a graph of any size it almost always elects
+ *      a level-0 node and so gives the upper layers up).  KDB_VACUUM_ELECT_TOP_LEVEL: the live node of the highest level
+ *      instead, the lowest id among equals, maxLevel = that level.  No live node: entry 0, maxLevel -1 -- from then on the
+ *      index answers like one whose uploaded graph has max_level -1.
+ *   5. Cleanup (:256-273), for every id of D: its lists on every level become empty (zero words), its stored row and its row of
+ *      the half-precision ranking copy (if there is one) are zeroed.  Its deleted bit STAYS SET: that is the mirror's "no node
+ *      here" (nodes[id] = nil) -- the exact scan keeps skipping the row, kdb_index_refine / kdb_index_add_batch keep treating
+ *      the id as not linkable.  Levels, count, capacity, the int8 norms and the number of deleted nodes do not change; ids are
+ *      not reused and no memory is given back (nodeCounter never goes back in the reference either).
+ * Failure: the census is read-only and its scratch is allocated before it; the repair's workspace (its size depends on |R|) is
+ * allocated before the first repair launch; a failure before the commit kernel leaves the graph as it was.  Commit, cleanup and
+ * the entry / maxLevel update follow the last check with no allocation in between, and entry / maxLevel change only after the
+ * final synchronisation succeeded.  A second call right after the first changes no adjacency word, no row and no header field
+ * (nodes_repaired 0).  ef_construction outside 1..512: KDB_ERR_UNSUPPORTED, nothing touched.                               */
+#define KDB_VACUUM_ELECT_TOP_LEVEL 1u
+typedef struct {
+    uint32_t ef_construction; /* 0 = the index's; 1..512 */
+    uint32_t flags;           /* KDB_VACUUM_ELECT_TOP_LEVEL */
+    uint32_t chunk_nodes;     /* as kdb_refine_params */
+} kdb_vacuum_params;
+typedef struct {
+    uint64_t dead_nodes;         /* |D| */
+    uint64_t nodes_repaired;     /* |R| */
+    uint64_t lists_written;      /* (node, level) lists replaced */
+    uint64_t lists_changed;      /* ... of which at least one stored word differs from before */
+    uint64_t dead_links_dropped; /* as kdb_refine_stats, for R */
+    uint64_t dead_links_found;   /* counted by the scan: equals dead_links_dropped (the nodes that hold dead links are the nodes repaired) */
+    uint32_t entry;              /* entry after the call */
+    int32_t  max_level;          /* max_level after the call */
+    uint32_t entry_changed;      /* 1: the entry the call found was deleted and has been replaced */
+    uint32_t reserved;
+} kdb_vacuum_stats;
+KDB_API int kdb_index_vacuum(kdb_index *idx, const kdb_vacuum_params *params, kdb_vacuum_stats *out);
+
+/* Read-only: the census that step 2 makes.  Ascending ids of R into out_ids (host, `cap` entries; NULL = counts
+ * only); *n_nodes = |R| whatever cap is; *n_dead_links = total dead links in live nodes' lists; *n_dead = |D|.  The numbers a
+ * host's maintenance policy (RunCycle's thresholds, optimizer.go) needs without downloading the graph.  No graph: all zero.  */
+KDB_API int kdb_index_dead_link_scan(kdb_index *idx, uint32_t *out_ids, uint32_t cap, uint32_t *n_nodes, uint64_t *n_dead_links,
+                                     uint64_t *n_dead);
 
 /* TEST HOOK -- selectNeighbors (hnsw_index.go:2629-2701) exactly as the GPU builder runs it (build_select_kernel's
  * workgroup routine), on caller-supplied candidate lists: list t holds cand_cnt[t] <= stride <= 576 entries at

@@ -117,6 +117,32 @@ class Index {
         needsRefine_ = false;
         return st;
     }
+    // GraphOptimizer.Vacuum (optimizer.go:133-277) on the device: nodes with links to deleted nodes re-linked as Refine does it, a
+    // deleted entry point replaced (electTopLevel: by the live node of the highest level, not the lowest live id), deleted nodes cleared
+    kdb_vacuum_stats Vacuum(uint32_t efConstruction = 0, bool electTopLevel = false, uint32_t chunkNodes = 0) {
+        kdb_vacuum_params p{efConstruction, electTopLevel ? (uint32_t)KDB_VACUUM_ELECT_TOP_LEVEL : 0u, chunkNodes};
+        kdb_vacuum_stats st{};
+        check(kdb_index_vacuum(h_, &p, &st), "vacuum");
+        return st;
+    }
+    // the census Vacuum makes (optimizer.go:165-193), read-only: the live nodes that hold a dead link, ascending
+    struct DeadLinks {
+        std::vector<uint32_t> ids;
+        uint64_t deadLinks = 0, deadNodes = 0;
+    };
+    DeadLinks DeadLinkScan() {
+        DeadLinks r;
+        uint32_t n = 0;
+        check(kdb_index_dead_link_scan(h_, nullptr, 0, &n, &r.deadLinks, &r.deadNodes), "dead_link_scan");
+        r.ids.resize(n);
+        if (n) check(kdb_index_dead_link_scan(h_, r.ids.data(), n, &n, &r.deadLinks, &r.deadNodes), "dead_link_scan");
+        return r;
+    }
+    bool MaintenanceRun(const std::string &task) { // hnsw_index.go:976: "vacuum" | "refine"
+        if (task == "vacuum") return Vacuum().dead_nodes > 0;
+        if (task == "refine") return Refine().nodes_refined > 0;
+        throw std::invalid_argument("unknown maintenance task " + task);
+    }
     // incremental refresh of the mirror after writers touched a few nodes (see kdb_index_append_nodes)
     void AppendNodes(uint32_t firstID, const std::vector<uint8_t> &levels) {
         check(kdb_index_append_nodes(h_, firstID, (uint32_t)levels.size(), levels.data()), "append_nodes");

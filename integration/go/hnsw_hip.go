@@ -268,8 +268,7 @@ func (m *gpuMirror) uploadGraph(h *Index, nodes []*Node, count uint32) error {
 
 // refineHIP: what GraphOptimizer.RunTurboRefine / MaintenanceRun("refine") call under the tag (optimizer.go:288-464, :679-719):
 // every live node of the mirror is re-linked on the device against the graph as the call finds it (ids == nil), or only
-// `ids` -- e.g. the nodes that hold a link to a deleted node, the repair a host wants after deletes (Vacuum's sequential
-// reconnectNode loop is not mirrored).  The host then reads the lists back (kdb_index_download_graph) into Node.Connections,
+// `ids` (repair after deletes is vacuumHIP below, which finds the nodes that hold a link to a deleted node itself).  The host then reads the lists back (kdb_index_download_graph) into Node.Connections,
 // or keeps searching on the device.  RunTurboRefine ends with h.SetNeedsRefine(false) as before (:716).
 func (m *gpuMirror) refineHIP(h *Index, ids []uint32) (C.kdb_refine_stats, error) {
 	var st C.kdb_refine_stats
@@ -285,6 +284,46 @@ func (m *gpuMirror) refineHIP(h *Index, ids []uint32) (C.kdb_refine_stats, error
 		return st, hipErr("kdb_index_refine")
 	}
 	return st, nil
+}
+
+// vacuumHIP: what MaintenanceRun("vacuum") calls under the tag (optimizer.go:133-277): the nodes that hold a link to a deleted
+// node are found ON the device, re-linked as refineHIP does it (a snapshot: reconnectNode's one-by-one order is not mirrored),
+// a deleted entry point is replaced and the deleted nodes' lists and rows are cleared.  electTopLevel: the new entry is the
+// live node of the highest level instead of the reference's lowest live id.  The host then takes entry / maxLevel from the
+// statistics and reads the lists back (kdb_index_download_graph), or keeps searching on the device.
+func (m *gpuMirror) vacuumHIP(h *Index, electTopLevel bool) (C.kdb_vacuum_stats, error) {
+	var st C.kdb_vacuum_stats
+	if err := m.refresh(h); err != nil {
+		return st, err
+	}
+	params := C.kdb_vacuum_params{ef_construction: C.uint32_t(h.efConstruction)}
+	if electTopLevel {
+		params.flags = C.KDB_VACUUM_ELECT_TOP_LEVEL
+	}
+	if rc := C.kdb_index_vacuum(m.h, &params, &st); rc != 0 {
+		return st, hipErr("kdb_index_vacuum")
+	}
+	return st, nil
+}
+
+// deadLinkScanHIP: the numbers RunCycle's vacuum threshold needs, without downloading the graph: the live nodes that hold a
+// dead link (ascending), the dead links, the deleted nodes.
+func (m *gpuMirror) deadLinkScanHIP(h *Index) (ids []uint32, deadLinks, deadNodes uint64, err error) {
+	if err = m.refresh(h); err != nil {
+		return
+	}
+	var n C.uint32_t
+	var dl, dn C.uint64_t
+	if rc := C.kdb_index_dead_link_scan(m.h, nil, 0, &n, &dl, &dn); rc != 0 {
+		return nil, 0, 0, hipErr("kdb_index_dead_link_scan")
+	}
+	ids = make([]uint32, int(n))
+	if n > 0 {
+		if rc := C.kdb_index_dead_link_scan(m.h, (*C.uint32_t)(unsafe.Pointer(&ids[0])), n, &n, &dl, &dn); rc != 0 {
+			return nil, 0, 0, hipErr("kdb_index_dead_link_scan")
+		}
+	}
+	return ids, uint64(dl), uint64(dn), nil
 }
 
 func (m *gpuMirror) destroy() {

@@ -1747,6 +1747,117 @@ int refine_impl(kdb_index *idx, const std::vector<uint32_t> &nodes, uint32_t efc
     return KDB_OK;
 }
 
+// =====================================================================================================================
+// Vacuum (kdb_index_vacuum, kdb_index_dead_link_scan): GraphOptimizer.Vacuum (pkg/core/hnsw/optimizer.go:133-277).  The
+// census (:165-193) and the physical cleanup (:256-273) are the two kernels below; the repair (:200-221, reconnectNode
+// :565-674) is refine_impl over the census' nodes, the entry point (:232-250) is elected on the host (kdb_vacuum_graph).
+// =====================================================================================================================
+// The census: one wave per word of the flag bitmap = 32 consecutive ids, so every word has one writer and the result is a
+// bitmap, not a list appended to in arrival order.  A lane takes one adjacency word; groups of `1 << lg` lanes (the first power
+// of two that holds deg0, at least 16) share a node, 64 >> lg nodes per pass, and the ballot of the pass is folded into the
+// nodes' bits.  Dead link = a non-zero word that names no node (nb - 1 >= count) or a deleted one; the zero words behind a list's
+// end are padding.  Deleted nodes are skipped: their lists are cleared, not repaired.  Levels above max_level are not looked
+// at -- refine_impl does not write them either.  out[0] += the dead links of the live nodes.
+__global__ void __launch_bounds__(256)
+vacuum_scan_kernel(KdbView v, uint32_t up_slots, uint32_t lg, uint32_t *flags, unsigned long long *out) {
+    __shared__ uint32_t sh_dead;
+    const uint32_t tid = threadIdx.x, lane = tid & 63u;
+    if (tid == 0) sh_dead = 0u;
+    __syncthreads();
+    const uint32_t w = blockIdx.x * 4u + (tid >> 6);
+    uint32_t mine = 0u; // dead links this lane saw
+    if (w <= (v.count >> 5)) {
+        const uint32_t base = w << 5, last = v.count - base; // base <= count
+        uint32_t live = ~v.deleted[w];
+        if (w == 0) live &= ~1u;                           // id 0 is no node
+        if (last < 31u) live &= (2u << last) - 1u;         // ids above count are no nodes
+        uint32_t flag = 0u;
+        const uint32_t gs = 1u << lg, sub = lane >> lg, j = lane & (gs - 1u), per = 64u >> lg;
+        const unsigned long long gmask = gs == 64u ? ~0ull : (1ull << gs) - 1ull;
+        for (uint32_t i = 0; i < 32u; i += per) {
+            const uint32_t bit = i + sub;
+            uint32_t nb = 0u;
+            if (((live >> bit) & 1u) && j < v.deg0) nb = v.adj0[(size_t)(base + bit) * v.deg0 + j];
+            const bool dead = nb != 0u && (nb - 1u >= v.count || ((v.deleted[nb >> 5] >> (nb & 31u)) & 1u));
+            const unsigned long long m = __ballot(dead);
+            mine += dead ? 1u : 0u;
+            for (uint32_t g = 0; g < per; g++)
+                if ((m >> (g << lg)) & gmask) flag |= 1u << (i + g);
+        }
+        // the upper lists of a node are consecutive slots of the pool: levels 1..lv in one run of lv * deg_up words
+        uint32_t lv = 0u;
+        if (lane < 32u && ((live >> lane) & 1u)) {
+            lv = v.levels[base + lane];
+            if ((int)lv > v.max_level) lv = (uint32_t)v.max_level;
+        }
+        unsigned long long up = __ballot(lv > 0u);
+        while (up) {
+            const int b = __builtin_ctzll(up);
+            up &= up - 1ull;
+            uint32_t nl = (uint32_t)__shfl((int)lv, b, 64);
+            const uint32_t slot = v.up_idx[base + (uint32_t)b];
+            if (slot >= up_slots) nl = 0u;
+            else if (nl > up_slots - slot) nl = up_slots - slot;
+            const uint32_t *lists = v.adj_up + (size_t)slot * v.deg_up;
+            uint32_t here = 0u;
+            for (uint32_t e = lane; e < nl * v.deg_up; e += 64u) {
+                const uint32_t nb = lists[e];
+                if (nb != 0u && (nb - 1u >= v.count || ((v.deleted[nb >> 5] >> (nb & 31u)) & 1u))) here++;
+            }
+            mine += here;
+            if (__ballot(here != 0u)) flag |= 1u << b;
+        }
+        if (lane == 0) flags[w] = flag;
+    }
+    for (int o = 32; o > 0; o >>= 1) mine += (uint32_t)__shfl_xor((int)mine, o, 64);
+    if (lane == 0 && mine) atomicAdd(&sh_dead, mine);
+    __syncthreads();
+    if (tid == 0 && sh_dead) atomicAdd(out, (unsigned long long)sh_dead);
+}
+
+// The cleanup: one wave per id; a deleted id loses its lists on every level it owns (zero words = empty), its stored row and its
+// row of the half-precision ranking copy (rows16 null: there is none).  Its deleted bit stays: that is the mirror's "no node here".
+__global__ void __launch_bounds__(256)
+vacuum_clear_kernel(KdbView v, uint32_t up_slots, uint32_t *adj0, uint32_t *adj_up, unsigned char *rows, uint32_t row_bytes, uint16_t *rows16, uint32_t ld16) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t node = blockIdx.x * 4u + (threadIdx.x >> 6) + 1u;
+    if (node > v.count) return;
+    if (!((v.deleted[node >> 5] >> (node & 31u)) & 1u)) return;
+    if (lane < v.deg0) adj0[(size_t)node * v.deg0 + lane] = 0u;
+    uint32_t nl = v.levels[node];
+    const uint32_t slot = v.up_idx[node];
+    if (nl && slot >= up_slots) nl = 0u;
+    else if (nl > up_slots - slot) nl = up_slots - slot;
+    for (uint32_t e = lane; e < nl * v.deg_up; e += 64u) adj_up[(size_t)slot * v.deg_up + e] = 0u;
+    const uint4 z = make_uint4(0u, 0u, 0u, 0u);
+    uint4 *r = reinterpret_cast<uint4 *>(rows + (size_t)node * row_bytes); // ld is a multiple of 16 elements: whole 16-byte words
+    for (uint32_t i = lane; i < (row_bytes >> 4); i += 64u) r[i] = z;
+    if (rows16) {
+        uint4 *h = reinterpret_cast<uint4 *>(rows16 + (size_t)node * ld16); // ld16: whole 128-byte slabs
+        for (uint32_t i = lane; i < (ld16 >> 3); i += 64u) h[i] = z;
+    }
+}
+
+// the census into scratch: flag bitmap ((count >> 5) + 1 words) | one 64-bit counter.  Enqueued on s, not waited for.
+int vacuum_scan_launch(kdb_index *idx, hipStream_t s, uint32_t **d_flags, unsigned long long **d_links) {
+    const size_t fw = ((size_t)idx->count >> 5) + 1, fb = (fw * 4 + 255) & ~(size_t)255;
+    int rc = kdb_ensure_scratch(idx, fb + 256);
+    if (rc) return rc;
+    *d_flags = reinterpret_cast<uint32_t *>(idx->d_scratch);
+    *d_links = reinterpret_cast<unsigned long long *>(reinterpret_cast<unsigned char *>(idx->d_scratch) + fb);
+    KDB_HIP(hipMemsetAsync(*d_links, 0, 8, s));
+    uint32_t lg = 4;
+    while ((1u << lg) < idx->deg0) lg++;
+    hipLaunchKernelGGL(vacuum_scan_kernel, dim3((uint32_t)((fw + 3) / 4)), dim3(256), 0, s, kdb_make_view(idx), (uint32_t)idx->up_slots, lg, *d_flags, *d_links);
+    KDB_HIP(hipGetLastError());
+    return KDB_OK;
+}
+
+// ascending ids of the set bits of a census bitmap
+void vacuum_ids_of(const std::vector<uint32_t> &flags, std::vector<uint32_t> &ids) {
+    for (size_t w = 0; w < flags.size(); w++)
+        for (uint32_t f = flags[w]; f; f &= f - 1u) ids.push_back((uint32_t)(w << 5) + (uint32_t)__builtin_ctz(f));
+}
 
 } // namespace
 
@@ -1826,6 +1937,23 @@ int kdb_add_batch_ref(kdb_index *idx, uint32_t first_id, uint32_t n, const uint8
                                                  : add_batch_ref_impl<KDB_METRIC_L2, KDB_PREC_F32>(idx, first_id, n, levels, efc);
 }
 
+// what Refine and Vacuum's repair share: the limits of the three refine kernels ...
+static int refine_limits(const kdb_index *idx, uint32_t efc, const char *who) {
+    if (efc < 1 || efc > KDB_MAX_EFC || idx->deg0 > PR_MAXSEL || (size_t)idx->ld * (idx->desc.precision == KDB_PREC_I8 ? 1 : 4) > RF_MAX_ROW_BYTES) {
+        kdb_set_error("%s: ef_construction in 1..%u, mMax0 <= %d, rows of at most %u bytes", who, KDB_MAX_EFC, PR_MAXSEL, RF_MAX_ROW_BYTES);
+        return KDB_ERR_UNSUPPORTED;
+    }
+    return KDB_OK;
+}
+
+// ... and the dispatch on metric and precision (nodes: live, unique, 1..count, not empty)
+static int refine_dispatch(kdb_index *idx, const std::vector<uint32_t> &nodes, uint32_t efc, uint32_t chunk_nodes, kdb_refine_stats *st) {
+    if (idx->desc.precision == KDB_PREC_F16) return refine_impl<KDB_METRIC_L2, KDB_PREC_F16>(idx, nodes, efc, chunk_nodes, st);
+    if (idx->desc.precision == KDB_PREC_I8) return refine_impl<KDB_METRIC_COSINE, KDB_PREC_I8>(idx, nodes, efc, chunk_nodes, st);
+    return idx->desc.metric == KDB_METRIC_COSINE ? refine_impl<KDB_METRIC_COSINE, KDB_PREC_F32>(idx, nodes, efc, chunk_nodes, st)
+                                                 : refine_impl<KDB_METRIC_L2, KDB_PREC_F32>(idx, nodes, efc, chunk_nodes, st);
+}
+
 // GraphOptimizer.Refine (optimizer.go:288-464) for the nodes `ids` (null: every node 1..count), deleted ones skipped (:341)
 int kdb_refine_graph(kdb_index *idx, const uint32_t *ids, uint32_t n, uint32_t ef_construction, uint32_t chunk_nodes, kdb_refine_stats *out) {
     const uint32_t efc = ef_construction ? ef_construction : idx->desc.ef_construction;
@@ -1834,10 +1962,8 @@ int kdb_refine_graph(kdb_index *idx, const uint32_t *ids, uint32_t n, uint32_t e
         kdb_set_error("refine: the index holds no graph");
         return KDB_ERR_STATE;
     }
-    if (efc < 1 || efc > KDB_MAX_EFC || idx->deg0 > PR_MAXSEL || (size_t)idx->ld * (idx->desc.precision == KDB_PREC_I8 ? 1 : 4) > RF_MAX_ROW_BYTES) {
-        kdb_set_error("refine: ef_construction in 1..%u, mMax0 <= %d, rows of at most %u bytes", KDB_MAX_EFC, PR_MAXSEL, RF_MAX_ROW_BYTES);
-        return KDB_ERR_UNSUPPORTED;
-    }
+    int rc = refine_limits(idx, efc, "refine");
+    if (rc) return rc;
     if (ids)
         for (uint32_t i = 0; i < n; i++)
             if (ids[i] == 0 || ids[i] > idx->count) {
@@ -1860,13 +1986,120 @@ int kdb_refine_graph(kdb_index *idx, const uint32_t *ids, uint32_t n, uint32_t e
         }
         nodes.push_back(x);
     }
-    int rc = KDB_OK;
-    if (!nodes.empty()) {
-        if (idx->desc.precision == KDB_PREC_F16) rc = refine_impl<KDB_METRIC_L2, KDB_PREC_F16>(idx, nodes, efc, chunk_nodes, &st);
-        else if (idx->desc.precision == KDB_PREC_I8) rc = refine_impl<KDB_METRIC_COSINE, KDB_PREC_I8>(idx, nodes, efc, chunk_nodes, &st);
-        else rc = idx->desc.metric == KDB_METRIC_COSINE ? refine_impl<KDB_METRIC_COSINE, KDB_PREC_F32>(idx, nodes, efc, chunk_nodes, &st)
-                                                        : refine_impl<KDB_METRIC_L2, KDB_PREC_F32>(idx, nodes, efc, chunk_nodes, &st);
-    }
+    if (!nodes.empty()) rc = refine_dispatch(idx, nodes, efc, chunk_nodes, &st);
     if (rc == KDB_OK && out) *out = st;
     return rc;
+}
+
+// the census of Vacuum (optimizer.go:165-193) read back: the deleted bits, the flagged nodes in ascending order, the dead links
+static int vacuum_census(kdb_index *idx, std::vector<uint32_t> &del, std::vector<uint32_t> &nodes, uint64_t *n_links, uint64_t *n_dead) {
+    hipStream_t s = idx->stream;
+    const size_t dw = ((size_t)idx->count >> 5) + 1;
+    uint32_t *d_flags = nullptr;
+    unsigned long long *d_links = nullptr, links = 0;
+    int rc = vacuum_scan_launch(idx, s, &d_flags, &d_links);
+    if (rc) return rc;
+    std::vector<uint32_t> flags(dw, 0u);
+    del.assign(dw, 0u);
+    KDB_HIP(hipMemcpyAsync(flags.data(), d_flags, dw * 4, hipMemcpyDeviceToHost, s));
+    KDB_HIP(hipMemcpyAsync(&links, d_links, 8, hipMemcpyDeviceToHost, s));
+    KDB_HIP(hipMemcpyAsync(del.data(), idx->d_deleted, dw * 4, hipMemcpyDeviceToHost, s));
+    KDB_HIP(hipStreamSynchronize(s));
+    del[0] &= ~1u; // ids 1..count only
+    if ((idx->count & 31u) != 31u) del[dw - 1] &= (2u << (idx->count & 31u)) - 1u;
+    uint64_t nd = 0;
+    for (uint32_t w : del) nd += (uint64_t)__builtin_popcount(w);
+    nodes.clear();
+    vacuum_ids_of(flags, nodes);
+    *n_links = links;
+    *n_dead = nd;
+    return KDB_OK;
+}
+
+static bool vacuum_has_graph(const kdb_index *idx) {
+    return idx->has_graph && idx->max_level >= 0 && idx->entry != 0 && idx->count != 0 && idx->h_levels.size() == (size_t)idx->count + 1;
+}
+
+// kdb_index_dead_link_scan: the census alone, nothing written
+int kdb_dead_link_scan_graph(kdb_index *idx, uint32_t *out_ids, uint32_t cap, uint32_t *n_nodes, uint64_t *n_dead_links, uint64_t *n_dead) {
+    std::vector<uint32_t> del, nodes;
+    uint64_t links = 0, nd = 0;
+    if (vacuum_has_graph(idx)) {
+        int rc = vacuum_census(idx, del, nodes, &links, &nd);
+        if (rc) return rc;
+    }
+    if (out_ids)
+        for (size_t i = 0; i < nodes.size() && i < cap; i++) out_ids[i] = nodes[i];
+    if (n_nodes) *n_nodes = (uint32_t)nodes.size();
+    if (n_dead_links) *n_dead_links = links;
+    if (n_dead) *n_dead = nd;
+    return KDB_OK;
+}
+
+// GraphOptimizer.Vacuum (optimizer.go:133-277): census, repair = refine_impl over the census' nodes (snapshot; the reference's
+// one-by-one order is not mirrored, see kektor_hip.h), entry point, cleanup.  The census is read-only and its scratch comes
+// first; the repair's workspace depends on |R| and is allocated by refine_impl before ITS first launch; from refine_impl's last
+// check on (commit, cleanup, host fields) nothing is allocated, and the host fields change after the final synchronisation.
+int kdb_vacuum_graph(kdb_index *idx, uint32_t ef_construction, uint32_t flags, uint32_t chunk_nodes, kdb_vacuum_stats *out) {
+    const uint32_t efc = ef_construction ? ef_construction : idx->desc.ef_construction;
+    kdb_vacuum_stats st{};
+    int rc = refine_limits(idx, efc, "vacuum");
+    if (rc) return rc;
+    if (!vacuum_has_graph(idx) || idx->n_deleted == 0) { // nothing to do (:151): all-zero statistics
+        if (out) *out = st;
+        return KDB_OK;
+    }
+    KDB_HIP(hipDeviceSynchronize()); // walks of callers' streams may still read the lists this call rewrites
+    std::vector<uint32_t> del, nodes;
+    uint64_t links = 0, nd = 0;
+    rc = vacuum_census(idx, del, nodes, &links, &nd);
+    if (rc) return rc;
+    if (nd == 0) {
+        if (out) *out = st;
+        return KDB_OK;
+    }
+    st.dead_nodes = nd;
+    st.dead_links_found = links;
+    st.nodes_repaired = nodes.size();
+    // the entry point, from what the host already holds (:232-250): only a deleted entry is replaced
+    auto dead = [&](uint32_t x) { return ((del[x >> 5] >> (x & 31u)) & 1u) != 0u; };
+    uint32_t entry = idx->entry;
+    int32_t max_level = idx->max_level;
+    if (dead(entry)) {
+        entry = 0;
+        max_level = -1;
+        for (uint32_t x = 1; x <= idx->count; x++) {
+            if (dead(x)) continue;
+            const int32_t lv = (int32_t)idx->h_levels[x];
+            if (!(flags & KDB_VACUUM_ELECT_TOP_LEVEL)) { // the reference's rule: the first live node it meets, with ITS level
+                entry = x;
+                max_level = lv;
+                break;
+            }
+            if (lv > max_level) { // the live node of the highest level, the lowest id among equals
+                entry = x;
+                max_level = lv;
+            }
+        }
+        st.entry_changed = 1;
+    }
+    if (!nodes.empty()) { // the walks start at the entry point as the call found it, dead or not
+        kdb_refine_stats rs{};
+        rc = refine_dispatch(idx, nodes, efc, chunk_nodes, &rs);
+        if (rc) return rc;
+        st.lists_written = rs.lists_written;
+        st.lists_changed = rs.lists_changed;
+        st.dead_links_dropped = rs.dead_links_dropped;
+    }
+    hipStream_t s = idx->stream;
+    hipLaunchKernelGGL(vacuum_clear_kernel, dim3((idx->count + 3u) / 4u), dim3(256), 0, s, kdb_make_view(idx), (uint32_t)idx->up_slots, idx->d_adj0, idx->d_adj_up,
+                       reinterpret_cast<unsigned char *>(idx->d_rows), (uint32_t)((size_t)idx->ld * idx->elem), idx->d_rows16, idx->ld16);
+    KDB_HIP(hipGetLastError());
+    KDB_HIP(hipStreamSynchronize(s));
+    idx->entry = entry; // (no live node left: entry 0, max_level -1 -- an index whose graph is empty)
+    idx->max_level = max_level;
+    st.entry = entry;
+    st.max_level = max_level;
+    if (out) *out = st;
+    return KDB_OK;
 }

@@ -1968,6 +1968,29 @@ extern "C" int kdb_index_refine(kdb_index *idx, const uint32_t *ids, uint32_t n,
     return kdb_refine_graph(idx, ids, n, params ? params->ef_construction : 0u, params ? params->chunk_nodes : 0u, out);
 }
 
+extern "C" int kdb_index_vacuum(kdb_index *idx, const kdb_vacuum_params *params, kdb_vacuum_stats *out) {
+    KDB_CHECK_IDX(idx);
+    if (params && (params->flags & ~KDB_VACUUM_ELECT_TOP_LEVEL)) {
+        kdb_set_error("vacuum: unknown flag");
+        return KDB_ERR_INVALID;
+    }
+    KdbWriteLock wl(idx); // excludes host-pointer calls in flight
+    idx->graph_epoch++;
+    KDB_HIP(hipSetDevice(idx->device));
+    KdbLaneGuard lane(idx, idx->stream);
+    if (lane.rc) return lane.rc;
+    return kdb_vacuum_graph(idx, params ? params->ef_construction : 0u, params ? params->flags : 0u, params ? params->chunk_nodes : 0u, out);
+}
+
+extern "C" int kdb_index_dead_link_scan(kdb_index *idx, uint32_t *out_ids, uint32_t cap, uint32_t *n_nodes, uint64_t *n_dead_links, uint64_t *n_dead) {
+    KDB_CHECK_IDX(idx);
+    KdbWriteLock wl(idx); // writes nothing, but shares the index's stream and scratch with the writers
+    KDB_HIP(hipSetDevice(idx->device));
+    KdbLaneGuard lane(idx, idx->stream);
+    if (lane.rc) return lane.rc;
+    return kdb_dead_link_scan_graph(idx, out_ids, cap, n_nodes, n_dead_links, n_dead);
+}
+
 // test hook (see kektor_hip.h): host buffers in, selections out
 extern "C" int kdb_test_select_neighbors(kdb_index *idx, uint32_t n_lists, uint32_t stride, const uint32_t *cand_ids,
                                          const void *cand_keys, const uint32_t *cand_cnt, uint32_t maxm, uint32_t *out_ids,

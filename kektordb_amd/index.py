@@ -25,6 +25,7 @@ SEARCH_PREPARED = 2
 SEARCH_DIST_F64 = 8  # int8 indexes: distances come back as the reference's float64 (KDB_SEARCH_DIST_F64)
 SEARCH_TIE_FLAG = 16    # KDB_SEARCH_TIE_FLAG: bit 31 of out_count marks a walk that met equal distances
 SEARCH_HEAP_ORDER = 32  # KDB_SEARCH_HEAP_ORDER: such walks are repeated with the reference's two heaps
+VACUUM_ELECT_TOP_LEVEL = 1  # KDB_VACUUM_ELECT_TOP_LEVEL
 COUNT_TIED = 0x80000000
 COUNT_MASK = 0x7fffffff
 
@@ -232,6 +233,38 @@ class HipIndex:
         st = self.refine()
         self.needs_refine = False
         return st
+
+    def dead_link_scan(self, cap: Optional[int] = None):
+        """the census of Vacuum (optimizer.go:165-193) on the device, read-only (kdb_index_dead_link_scan): -> (ascending ids of
+        the live nodes that hold a link to a deleted node, dead links in live nodes' lists, deleted nodes); cap: at most that
+        many ids are handed out (None: all of them)"""
+        self._live()
+        n, links, dead = C.c_uint32(), C.c_uint64(), C.c_uint64()
+        if cap is None:
+            check(self.L.kdb_index_dead_link_scan(self.h, None, 0, C.byref(n), C.byref(links), C.byref(dead)), "kdb_index_dead_link_scan")
+            cap = n.value
+        ids = np.zeros(max(int(cap), 1), dtype=np.uint32)
+        check(self.L.kdb_index_dead_link_scan(self.h, _ptr(ids), int(cap), C.byref(n), C.byref(links), C.byref(dead)), "kdb_index_dead_link_scan")
+        self.last_scan_nodes = int(n.value)                     # |R| whatever cap was
+        return ids[:min(int(cap), n.value)], int(links.value), int(dead.value)
+
+    def vacuum(self, ef_construction: int = 0, elect_top_level: bool = False, chunk_nodes: int = 0) -> dict:
+        """GraphOptimizer.Vacuum (optimizer.go:133-277) on the device (kdb_index_vacuum): the live nodes that hold a link to a
+        deleted node are re-linked as refine does it, a deleted entry point is replaced (the lowest live id, or with
+        elect_top_level the live node of the highest level), the deleted nodes' lists and rows are cleared; -> the statistics"""
+        self._live()
+        p = _lib.VacuumParams(int(ef_construction), VACUUM_ELECT_TOP_LEVEL if elect_top_level else 0, int(chunk_nodes))
+        st = _lib.VacuumStats()
+        check(self.L.kdb_index_vacuum(self.h, C.byref(p), C.byref(st)), "kdb_index_vacuum")
+        return {f: int(getattr(st, f)) for f, _ in _lib.VacuumStats._fields_ if f != "reserved"}
+
+    def MaintenanceRun(self, task: str) -> bool:
+        """MaintenanceRun (hnsw_index.go:976): "vacuum" -> Vacuum (true when there was a deleted node), "refine" -> Refine"""
+        if task == "vacuum":
+            return self.vacuum()["dead_nodes"] > 0
+        if task == "refine":
+            return self.refine()["nodes_refined"] > 0
+        raise ValueError(f"unknown maintenance task {task!r}")
 
     def test_select_neighbors(self, cand_ids, cand_keys, cand_cnt, maxm: int):
         """TEST HOOK: the GPU builder's selectNeighbors on caller-supplied lists ([n_lists, stride] ids / ascending keys;
