@@ -307,8 +307,17 @@ KDB_API int kdb_distance_batch_dev(kdb_index *idx, const float *d_queries, uint3
  * |v|, found exactly by a radix select), Quantize and the stored norms for every row; float16: RNE conversion.  The new
  * index keeps the float32 index's GRAPH (ids, links, deleted bits) unless KDB_COMPRESS_REBUILD_GRAPH asks the GPU builder
  * to re-insert every row with the new precision's distances (float16 squared L2; int8: the float64 cosine distance over
- * the quantised rows and stored norms), which is what the reference's AddBatch loop does (core.go:1236-1283).  The
- * source is left as it is; the caller owns *out (kdb_index_destroy).                                               */
+ * the quantised rows and stored norms), which is what the reference's AddBatch loop does (core.go:1236-1283).
+ * Deleted nodes (the reference collects the vectors with IterateRaw, which skips them):
+ *   - Train: the training set is the live rows (deleted bit clear) of 1..count in ascending id order; totalVectors, the
+ *     10 000 threshold, targetSize, step and the break of quantizer.go:49-94 apply to that list.  No live row:
+ *     KDB_ERR_STATE, as for an empty index (core.go:1168-1170), for both precisions;
+ *   - rows: every row 1..count is converted or quantised and keeps its id, deleted or not (the mirror does not renumber);
+ *   - deleted bits: both modes carry the source's deleted bits and their count into the new index, with or without a
+ *     graph.  With KDB_COMPRESS_REBUILD_GRAPH the builder inserts every id 1..count and the deleted ones are marked
+ *     deleted again afterwards -- the reference's state between Delete and Vacuum: walks may pass through them, no search
+ *     or scan returns them, kdb_index_dead_link_scan counts them and kdb_index_vacuum removes them.
+ * The source is left as it is; the caller owns *out (kdb_index_destroy).                                           */
 #define KDB_COMPRESS_REBUILD_GRAPH 1u
 KDB_API int kdb_index_compress(kdb_index *src, uint32_t precision, uint32_t flags, kdb_index **out);
 KDB_API int kdb_index_get_quantizer(kdb_index *idx, float *abs_max);

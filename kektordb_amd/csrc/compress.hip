@@ -5,10 +5,17 @@
 // rows), create a new index of the new precision, train its quantizer on ALL of them (Quantizer.Train,
 // pkg/core/distance/quantizer.go:49-135: strided sample above 10 000 vectors, 99.9th percentile of |v|), and re-insert the
 // vectors with AddBatch in chunks of 5000 (:1236-1283), i.e. the graph is rebuilt with the new precision's distances.
+// IterateRaw (hnsw_index.go:2817-2838) skips nil and Deleted nodes: the reference trains on, and re-inserts, the LIVE vectors.
 // Here:
-//   * Train on the device: the sample's |v| are gathered into scratch and the order statistic floor(0.999 N) is found
+//   * Train on the device over the live rows (deleted bit clear) of 1..count in ascending id order -- the 10 000 threshold,
+//     targetSize, step and the break count positions of THAT list; the host reads the deleted bits, picks the at most 25 000
+//     training ids and uploads them; their |v| are gathered into scratch and the order statistic floor(0.999 N) is found
 //     EXACTLY by a radix select over the float bit patterns (non-negative floats order like unsigned integers): four passes
-//     of an 8-bit histogram -- no sort;
+//     of an 8-bit histogram -- no sort.  No live row: KDB_ERR_STATE, as for an empty index (core.go:1168-1170);
+//   * every row 1..count is converted, deleted or not, and keeps its id (the mirror does not renumber); the deleted bits and
+//     their count go to the new index in BOTH graph modes: a rebuilt graph holds every id (the builder inserts 1..count and
+//     starts from no deletions) and the deleted ones are marked again afterwards -- the reference's own state between Delete
+//     and Vacuum: walks pass through them and never return them, kdb_index_vacuum removes them;
 //   * Quantize (quantizer.go:150-176: v / AbsMax * 127, clipped to +-127, rounded half away from zero) and the stored norms
 //     (computeInt8Norm: sqrt of the exact integer sum of squares, as f32) for every row, one wave per 4 rows;
 //   * float16: RNE conversion (float16.Fromfloat32);
@@ -24,13 +31,13 @@
 
 namespace {
 
-// |v| of the sampled rows, dense [nsel][dim]
-__global__ void abs_sample_kernel(const float *__restrict__ rows, uint32_t ld, uint32_t dim, uint32_t first_id, uint32_t step,
-                                  uint32_t nsel, float *__restrict__ out) {
+// |v| of the training rows, dense [nsel][dim]: row r of the sample is the stored row ids[r]
+__global__ void abs_sample_kernel(const float *__restrict__ rows, uint32_t ld, uint32_t dim, const uint32_t *__restrict__ ids, uint32_t nsel,
+                                  float *__restrict__ out) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= (size_t)nsel * dim) return;
     const uint32_t r = (uint32_t)(i / dim), c = (uint32_t)(i % dim);
-    out[i] = fabsf(rows[((size_t)first_id + (size_t)r * step) * ld + c]);
+    out[i] = fabsf(rows[(size_t)ids[r] * ld + c]);
 }
 
 // histogram of byte (x >> shift) & 255 over the values whose higher bits equal `prefix`
@@ -118,6 +125,17 @@ extern "C" int kdb_index_compress(kdb_index *src, uint32_t precision, uint32_t f
     hipStream_t s = dst->stream;
     const uint32_t n = src->count, dim = src->desc.dim;
     const float *rows = reinterpret_cast<const float *>(src->d_rows);
+    // ---- what the reference compresses: IterateRaw (hnsw_index.go:2817-2838) hands out the LIVE vectors in ascending id order
+    const size_t del_words = ((((size_t)src->cap + 1 + 31) / 32) + 3) & ~(size_t)3;
+    std::vector<uint32_t> del(((size_t)n >> 5) + 1, 0u), live;
+    if (src->n_deleted) KDB_TRYC(hipMemcpy(del.data(), src->d_deleted, del.size() * 4, hipMemcpyDeviceToHost));
+    live.reserve(n);
+    for (uint32_t x = 1; x <= n; x++)
+        if (!((del[x >> 5] >> (x & 31u)) & 1u)) live.push_back(x);
+    if (live.empty()) {
+        kdb_set_error("compress: every node of the index is deleted: nothing to compress (core.go:1168-1170)");
+        return fail(KDB_ERR_STATE);
+    }
     if (precision == KDB_PREC_F16) {
         rc = kdb_launch_rows_to_f16(rows, reinterpret_cast<uint16_t *>(dst->d_rows), src->ld, src->ld, 1, n, s);
         if (rc) return fail(rc);
@@ -126,36 +144,43 @@ extern "C" int kdb_index_compress(kdb_index *src, uint32_t precision, uint32_t f
         rc = kdb_launch_row_norms(v, dst->d_norms, 1, n, nullptr, s); // ||x||^2 of the float16 rows (ranking key of the L2 scan)
         if (rc) return fail(rc);
     } else {
-        // ---- Quantizer.Train (quantizer.go:49-135)
-        uint32_t nsel = n, step = 1;
+        // ---- Quantizer.Train (quantizer.go:49-135) over the live rows: totalVectors, the threshold, targetSize, step and the break
+        //      all count positions of that list, not ids
+        const uint32_t total = (uint32_t)live.size();
         const uint32_t HardCap = 25000, MinThreshold = 10000;
-        if (n > MinThreshold) {
-            uint32_t target = n / 10;
+        if (total > MinThreshold) {
+            uint32_t target = total / 10;
             if (target > HardCap) target = HardCap;
             if (target < MinThreshold) target = MinThreshold;
-            step = n / target;
+            uint32_t step = total / target;
             if (step < 1) step = 1;
-            nsel = 0;
-            for (uint32_t i = 0; i < n; i += step) {
-                nsel++;
+            uint32_t nsel = 0;
+            for (uint32_t i = 0; i < total; i += step) {
+                live[nsel++] = live[i]; // (nsel <= i: the sample is compacted in place)
                 if (nsel >= target) break;
             }
+            live.resize(nsel);
         }
+        const uint32_t nsel = (uint32_t)live.size(); // the ids of the training set, ascending
         const size_t N = (size_t)nsel * dim;
         float *d_vals = nullptr;
-        uint32_t *d_hist = nullptr;
-        KDB_TRYC(hipMalloc(&d_vals, N * 4));
-        if (hipMalloc(&d_hist, 1024) != hipSuccess) {
-            (void)hipFree(d_vals);
-            kdb_set_error("compress: out of memory");
-            return fail(KDB_ERR_OOM);
-        }
+        uint32_t *d_hist = nullptr, *d_sel = nullptr;
         auto done = [&](int code) {
             (void)hipFree(d_vals);
             (void)hipFree(d_hist);
+            (void)hipFree(d_sel);
             return code ? fail(code) : KDB_OK;
         };
-        hipLaunchKernelGGL(abs_sample_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, rows, src->ld, dim, 1u, step, nsel, d_vals);
+        if (hipMalloc(&d_vals, N * 4) != hipSuccess || hipMalloc(&d_hist, 1024) != hipSuccess || hipMalloc(&d_sel, (size_t)nsel * 4) != hipSuccess) {
+            (void)hipGetLastError();
+            kdb_set_error("compress: out of memory");
+            return done(KDB_ERR_OOM);
+        }
+        if (hipMemcpyAsync(d_sel, live.data(), (size_t)nsel * 4, hipMemcpyHostToDevice, s) != hipSuccess) {
+            kdb_set_error("compress: upload of the training ids failed");
+            return done(KDB_ERR_HIP);
+        }
+        hipLaunchKernelGGL(abs_sample_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, rows, src->ld, dim, d_sel, nsel, d_vals);
         size_t want = (size_t)((double)N * 0.999); // quantileIndex, clamped as :115-121
         if (want >= N) want = N - 1;
         uint32_t prefix = 0;
@@ -197,7 +222,6 @@ extern "C" int kdb_index_compress(kdb_index *src, uint32_t precision, uint32_t f
         KDB_TRYC(hipMemcpyAsync(dst->d_adj0, src->d_adj0, n1 * src->deg0 * 4, hipMemcpyDeviceToDevice, s));
         KDB_TRYC(hipMemcpyAsync(dst->d_up_idx, src->d_up_idx, n1 * 4, hipMemcpyDeviceToDevice, s));
         KDB_TRYC(hipMemcpyAsync(dst->d_levels, src->d_levels, n1, hipMemcpyDeviceToDevice, s));
-        KDB_TRYC(hipMemcpyAsync(dst->d_deleted, src->d_deleted, ((((n1 + 31) / 32) + 3) & ~(size_t)3) * 4, hipMemcpyDeviceToDevice, s));
         const size_t up_words = src->up_slots * src->deg_up + 4;
         KDB_TRYC(hipMalloc(&dst->d_adj_up, up_words * 4));
         KDB_TRYC(hipMemsetAsync(dst->d_adj_up, 0, up_words * 4, s));
@@ -209,11 +233,9 @@ extern "C" int kdb_index_compress(kdb_index *src, uint32_t precision, uint32_t f
         dst->h_up_idx = src->h_up_idx;
         dst->entry = src->entry;
         dst->max_level = src->max_level;
-        dst->n_deleted = src->n_deleted;
         dst->has_graph = true;
     }
     KDB_TRYC(hipStreamSynchronize(s));
-#undef KDB_TRYC
     if (flags & KDB_COMPRESS_REBUILD_GRAPH) { // re-insertion with the new precision's distances, on the GPU
         kdb_build_params bp{};
         bp.seed = 1;
@@ -224,6 +246,14 @@ extern "C" int kdb_index_compress(kdb_index *src, uint32_t precision, uint32_t f
         }
         if (rc) return fail(rc);
     }
+    // ---- the deleted bits, whatever became of the graph (the builder starts from none: a rebuilt graph holds every id, and the
+    //      deleted ones are marked again -- the reference's own state between Delete and Vacuum)
+    if (src->n_deleted) {
+        KDB_TRYC(hipMemcpyAsync(dst->d_deleted, src->d_deleted, del_words * 4, hipMemcpyDeviceToDevice, s));
+        KDB_TRYC(hipStreamSynchronize(s));
+        dst->n_deleted = src->n_deleted;
+    }
+#undef KDB_TRYC
     *out = dst;
     return KDB_OK;
 }
