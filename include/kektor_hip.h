@@ -140,13 +140,21 @@ typedef struct {
     uint32_t ef_construction; /* 0 -> 200 */
     uint32_t capacity;   /* largest internal id the index may hold */
     int32_t device_id;   /* HIP device ordinal */
-    uint32_t reserved;   /* flags: KDB_INDEX_NO_F16_SHADOW */
+    uint32_t reserved;   /* flags: KDB_INDEX_NO_F16_SHADOW | KDB_INDEX_NO_WALK_PLANES */
 } kdb_index_desc;
 /* float32 indexes that are scanned exactly keep a second copy of the rows as halfs (+50 % row memory), made by the
  * FIRST kdb_flat_scan_* call (an index that is only walked never allocates it): the exact scan RANKS on it (half the
  * HBM bytes for small batches, the f16 MFMA for large ones) inside a rigorous error band and settles on the float32
  * rows, so answers are unchanged.  Set this bit to do without the copy for good.                               */
 #define KDB_INDEX_NO_F16_SHADOW 1u
+/* float32 cosine indexes of 768 columns that are walked in large batches at ef <= 256 (the one-wave kernel: more queries
+ * than the latency modes take) keep the rows once more as two 16-bit planes -- the high and the low halves of every float --
+ * and one float32 error bound per row: +100 % row memory while they exist (12.5M x 768: 38 GB of rows + 19 + 19 GB of
+ * planes), made by the FIRST such walk (small batches, L2 and quantised indexes never allocate them).  A hop whose beam is
+ * full reads the high plane first and fetches the low plane only of the candidates it cannot prove too far; the proof is
+ * rigorous and survivors are evaluated on the reassembled float32 values, so answers, distances and counters are unchanged.
+ * Set this bit to do without the planes for good.                                                                        */
+#define KDB_INDEX_NO_WALK_PLANES 2u
 
 /* Per-level CSR adjacency.  offsets[l] has count+2 entries: node i's neighbours at level l are
  * neighbors[l][offsets[l][i] .. offsets[l][i+1]) (empty when levels[i] < l).  Lists keep the
@@ -200,6 +208,9 @@ KDB_API int kdb_index_reserve(kdb_index *idx, uint32_t new_capacity);
 /* Give back the half-precision ranking copy of a float32 index (see KDB_INDEX_NO_F16_SHADOW); the next exact scan makes it
  * again unless refuse_for_good != 0.                                                                                        */
 KDB_API int kdb_index_drop_f16_shadow(kdb_index *idx, int refuse_for_good);
+/* Give back the walk planes (see KDB_INDEX_NO_WALK_PLANES); the next large-batch walk makes them again unless
+ * refuse_for_good != 0.                                                                                                    */
+KDB_API int kdb_index_drop_walk_planes(kdb_index *idx, int refuse_for_good);
 
 /* Incremental refresh of the mirror after writers (Add / AddBatch / optimizer) touched a FEW nodes, instead of a full
  * kdb_index_upload_graph:

@@ -26,7 +26,7 @@ ABI_SYMBOLS = [
     "kdb_index_sync", "kdb_index_set_launch_timing", "kdb_test_select_neighbors", "kdb_cluster_create", "kdb_cluster_destroy", "kdb_cluster_info",
     "kdb_sharded_search_batch", "kdb_sharded_flat_scan_batch", "kdb_index_compress", "kdb_index_get_quantizer", "kdb_index_add_batch", "kdb_merge_topk_packed_f64_dev",
     "kdb_cluster_comm_info", "kdb_cluster_debug_fail_next", "kdb_index_reserve", "kdb_index_drop_f16_shadow", "kdb_probe_gather", "kdb_probe_stream", "kdb_probe_poison_lds", "kdb_index_caller_stats", "kdb_merge_topk_f64", "kdb_index_refine",
-    "kdb_index_vacuum", "kdb_index_dead_link_scan",
+    "kdb_index_vacuum", "kdb_index_dead_link_scan", "kdb_index_drop_walk_planes",
 ]
 
 
@@ -161,6 +161,7 @@ def load():
     L.kdb_probe_poison_lds.argtypes = [vp, u32]
     L.kdb_index_reserve.argtypes = [vp, u32]
     L.kdb_index_drop_f16_shadow.argtypes = [vp, C.c_int]
+    L.kdb_index_drop_walk_planes.argtypes = [vp, C.c_int]
     L.kdb_cluster_comm_info.argtypes = [vp, C.POINTER(u32), C.POINTER(u32)]
     L.kdb_cluster_debug_fail_next.argtypes = [vp, u32]
     _lib = L

@@ -1816,9 +1816,11 @@ vacuum_scan_kernel(KdbView v, uint32_t up_slots, uint32_t lg, uint32_t *flags, u
 }
 
 // The cleanup: one wave per id; a deleted id loses its lists on every level it owns (zero words = empty), its stored row and its
-// row of the half-precision ranking copy (rows16 null: there is none).  Its deleted bit stays: that is the mirror's "no node here".
+// row of the half-precision ranking copy (rows16 null: there is none) and of the walk planes (walk_hi null: there are none; a zero
+// row's planes are zero and its bound is 0).  Its deleted bit stays: that is the mirror's "no node here".
 __global__ void __launch_bounds__(256)
-vacuum_clear_kernel(KdbView v, uint32_t up_slots, uint32_t *adj0, uint32_t *adj_up, unsigned char *rows, uint32_t row_bytes, uint16_t *rows16, uint32_t ld16) {
+vacuum_clear_kernel(KdbView v, uint32_t up_slots, uint32_t *adj0, uint32_t *adj_up, unsigned char *rows, uint32_t row_bytes, uint16_t *rows16, uint32_t ld16,
+                    uint16_t *walk_hi, uint16_t *walk_lo, float *walk_err) {
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t node = blockIdx.x * 4u + (threadIdx.x >> 6) + 1u;
     if (node > v.count) return;
@@ -1835,6 +1837,11 @@ vacuum_clear_kernel(KdbView v, uint32_t up_slots, uint32_t *adj0, uint32_t *adj_
     if (rows16) {
         uint4 *h = reinterpret_cast<uint4 *>(rows16 + (size_t)node * ld16); // ld16: whole 128-byte slabs
         for (uint32_t i = lane; i < (ld16 >> 3); i += 64u) h[i] = z;
+    }
+    if (walk_hi) {
+        uint4 *h = reinterpret_cast<uint4 *>(walk_hi + (size_t)node * v.ld), *l = reinterpret_cast<uint4 *>(walk_lo + (size_t)node * v.ld);
+        for (uint32_t i = lane; i < (v.ld >> 3); i += 64u) h[i] = l[i] = z; // (ld: a multiple of 128 halves)
+        if (lane == 0u) walk_err[node] = 0.f;
     }
 }
 
@@ -2093,7 +2100,8 @@ int kdb_vacuum_graph(kdb_index *idx, uint32_t ef_construction, uint32_t flags, u
     }
     hipStream_t s = idx->stream;
     hipLaunchKernelGGL(vacuum_clear_kernel, dim3((idx->count + 3u) / 4u), dim3(256), 0, s, kdb_make_view(idx), (uint32_t)idx->up_slots, idx->d_adj0, idx->d_adj_up,
-                       reinterpret_cast<unsigned char *>(idx->d_rows), (uint32_t)((size_t)idx->ld * idx->elem), idx->d_rows16, idx->ld16);
+                       reinterpret_cast<unsigned char *>(idx->d_rows), (uint32_t)((size_t)idx->ld * idx->elem), idx->d_rows16, idx->ld16,
+                       idx->d_walk_hi, idx->d_walk_lo, idx->d_walk_err);
     KDB_HIP(hipGetLastError());
     KDB_HIP(hipStreamSynchronize(s));
     idx->entry = entry; // (no live node left: entry 0, max_level -1 -- an index whose graph is empty)

@@ -349,7 +349,8 @@ extern "C" int kdb_index_create(const kdb_index_desc *desc, kdb_index **out) {
     idx->ev1 = idx->ring_ev1[0];
     KDB_TRY(hipMalloc(&idx->d_rows, n1 * idx->ld * idx->elem));
     KDB_TRY(hipMemsetAsync(idx->d_rows, 0, (size_t)idx->ld * idx->elem, idx->stream)); // row 0
-    // (the half-precision ranking copy of float32 rows is made by the first exact scan that can use it: ensure_rows16)
+    // (the half-precision ranking copy of float32 rows is made by the first exact scan that can use it: ensure_rows16; the walk
+    // planes by the first large-batch walk: kdb_ensure_walk_planes -- both convert row 0 with the rest)
     KDB_TRY(hipMalloc(&idx->d_norms, n1 * 4));
     KDB_TRY(hipMemsetAsync(idx->d_norms, 0, n1 * 4, idx->stream));
     KDB_TRY(hipMalloc(&idx->d_adj0, n1 * idx->deg0 * 4));
@@ -388,7 +389,8 @@ extern "C" void kdb_index_destroy(kdb_index *idx) {
     (void)hipDeviceSynchronize(); // callers' streams may still run kernels of this index
     lane_store(idx);
     void *bufs[] = {idx->d_rows,  idx->d_norms,   idx->d_adj0,    idx->d_adj_up, idx->d_up_idx, idx->d_levels,
-                    idx->d_deleted, idx->d_ctr, idx->d_iobuf, idx->d_build, idx->d_rows16, idx->d_adj_up_slot};
+                    idx->d_deleted, idx->d_ctr, idx->d_iobuf, idx->d_build, idx->d_rows16, idx->d_adj_up_slot,
+                    idx->d_walk_hi, idx->d_walk_lo, idx->d_walk_err};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     for (kdb_lane &l : idx->lanes) {
@@ -436,6 +438,10 @@ static int upload_rows_impl(kdb_index *idx, uint32_t first_id, uint32_t n, const
     // f16-ranked cosine scan: the reference normalises cosine rows at insert, the mirror does not assume it)
     if (idx->d_rows16) { // ranking copy of the new rows
         int rc = kdb_launch_rows_to_f16(reinterpret_cast<const float *>(idx->d_rows), idx->d_rows16, idx->ld, idx->ld16, first_id, n, idx->stream);
+        if (rc) return rc;
+    }
+    if (idx->d_walk_hi) { // walk planes of the new rows
+        int rc = kdb_launch_walk_planes(reinterpret_cast<const float *>(idx->d_rows), idx->d_walk_hi, idx->d_walk_lo, idx->d_walk_err, idx->ld, first_id, n, idx->stream);
         if (rc) return rc;
     }
     const bool want_norms = idx->desc.precision != KDB_PREC_I8 &&
@@ -546,8 +552,13 @@ extern "C" int kdb_index_reserve(kdb_index *idx, uint32_t new_capacity) {
         size_t old_bytes, new_bytes;
     };
     void *rows16 = idx->d_rows16;
+    const size_t wp = idx->d_walk_hi ? 1 : 0; // the walk planes move with the rows (the new rows are zero: zero planes, bound 0)
+    void *walk_hi = idx->d_walk_hi, *walk_lo = idx->d_walk_lo, *walk_err = idx->d_walk_err;
     Arr arrs[] = {{&idx->d_rows, o1 * row_b, n1 * row_b},
                   {&rows16, idx->d_rows16 ? o1 * idx->ld16 * 2 : 0, idx->d_rows16 ? n1 * idx->ld16 * 2 : 0},
+                  {&walk_hi, wp * o1 * idx->ld * 2, wp * n1 * idx->ld * 2},
+                  {&walk_lo, wp * o1 * idx->ld * 2, wp * n1 * idx->ld * 2},
+                  {&walk_err, wp * o1 * 4, wp * n1 * 4},
                   {reinterpret_cast<void **>(&idx->d_norms), o1 * 4, n1 * 4},
                   {reinterpret_cast<void **>(&idx->d_adj0), o1 * idx->deg0 * 4, n1 * idx->deg0 * 4},
                   {reinterpret_cast<void **>(&idx->d_up_idx), o1 * 4, n1 * 4},
@@ -578,6 +589,9 @@ extern "C" int kdb_index_reserve(kdb_index *idx, uint32_t new_capacity) {
         *arrs[i].p = fresh[i];
     }
     idx->d_rows16 = reinterpret_cast<uint16_t *>(rows16);
+    idx->d_walk_hi = reinterpret_cast<uint16_t *>(walk_hi);
+    idx->d_walk_lo = reinterpret_cast<uint16_t *>(walk_lo);
+    idx->d_walk_err = reinterpret_cast<float *>(walk_err);
     // scratch whose size follows the capacity: visited bitsets of both lanes, the builders' workspace
     lane_store(idx);
     for (kdb_lane &l : idx->lanes) {
@@ -608,6 +622,62 @@ extern "C" int kdb_index_drop_f16_shadow(kdb_index *idx, int refuse_for_good) {
     }
     idx->rows16_refused = false;
     if (refuse_for_good) idx->desc.reserved |= KDB_INDEX_NO_F16_SHADOW;
+    return KDB_OK;
+}
+
+// The walk planes of a float32 cosine index (made by its first large-batch walk, +100 % row memory) can be given back the same
+// way: the next such walk makes them again (or never, with refuse_for_good != 0 -- KDB_INDEX_NO_WALK_PLANES from then on).
+static void free_walk_planes(kdb_index *idx) {
+    if (idx->d_walk_hi) (void)hipFree(idx->d_walk_hi);
+    if (idx->d_walk_lo) (void)hipFree(idx->d_walk_lo);
+    if (idx->d_walk_err) (void)hipFree(idx->d_walk_err);
+    idx->d_walk_hi = idx->d_walk_lo = nullptr;
+    idx->d_walk_err = nullptr;
+}
+extern "C" int kdb_index_drop_walk_planes(kdb_index *idx, int refuse_for_good) {
+    KDB_CHECK_IDX(idx);
+    KdbWriteLock wl(idx); // excludes host-pointer calls in flight
+    KDB_HIP(hipSetDevice(idx->device));
+    if (idx->d_walk_hi) {
+        KDB_HIP(hipDeviceSynchronize()); // walks of callers' streams may still read them
+        free_walk_planes(idx);
+    }
+    idx->walk_refused = false;
+    if (refuse_for_good) idx->desc.reserved |= KDB_INDEX_NO_WALK_PLANES;
+    return KDB_OK;
+}
+
+// Called under idx->mu by the launch that has picked a planes kernel (search_kernel.cuh), so latency-mode walks, L2 and quantised
+// indexes never get here.  Every row of the allocation is converted (rows uploaded ahead of set_count included; what was never
+// uploaded converts to whatever it holds and is never read), and the planes are published only once they are COMPLETE: walks of
+// other streams and later uploads on idx->stream order against nothing but this wait -- a one-time cost of the first such walk.
+// No room: `walk_refused`, the walk carries on on the float32 rows and does not ask again.
+int kdb_ensure_walk_planes(kdb_index *idx, hipStream_t s) {
+    if (idx->d_walk_hi || idx->walk_refused || !kdb_walk_planes_shape(idx)) return KDB_OK;
+    const size_t n1 = (size_t)idx->cap + 1;
+    uint16_t *hi = nullptr, *lo = nullptr;
+    float *err = nullptr;
+    if (hipMalloc(&hi, n1 * idx->ld * 2) != hipSuccess || hipMalloc(&lo, n1 * idx->ld * 2) != hipSuccess || hipMalloc(&err, n1 * 4) != hipSuccess) {
+        (void)hipGetLastError();
+        if (hi) (void)hipFree(hi);
+        if (lo) (void)hipFree(lo);
+        idx->walk_refused = true;
+        return KDB_OK;
+    }
+    int rc = kdb_launch_walk_planes(reinterpret_cast<const float *>(idx->d_rows), hi, lo, err, idx->ld, 0, (uint32_t)n1, s);
+    if (rc == KDB_OK && hipStreamSynchronize(s) != hipSuccess) {
+        kdb_set_error("walk planes: conversion failed");
+        rc = KDB_ERR_HIP;
+    }
+    if (rc) {
+        (void)hipFree(hi);
+        (void)hipFree(lo);
+        (void)hipFree(err);
+        return rc;
+    }
+    idx->d_walk_hi = hi;
+    idx->d_walk_lo = lo;
+    idx->d_walk_err = err;
     return KDB_OK;
 }
 

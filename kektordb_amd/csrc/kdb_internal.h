@@ -49,6 +49,11 @@ struct KdbView {
     uint32_t vis_words;      // words per visited bitset = (cap>>5)+1
     float q_absmax;          // int8 quantizer
     uint32_t has_deleted;    // 0: no soft-deleted node, the per-neighbour Deleted lookup is skipped
+    // walk planes (float32 cosine, ld == 64 * NCH; kdb_ensure_walk_planes): the rows once more as two 16-bit planes + one bound
+    // per row; null unless the launch runs a planes kernel (kdb_launch_search sets them on its own copy of the view)
+    const uint16_t *walk_hi = nullptr; // (cap+1) x ld high halves, permuted inside the row (kdb_walk_plane_pos)
+    const uint16_t *walk_lo = nullptr; // ... low halves: (hi << 16) | lo is the stored float, bit for bit
+    const float *walk_err = nullptr;   // (cap+1): >= ||x - hi||_2 + 2 gamma ||x||_2, +Inf for a row the bound cannot cover
 };
 
 // Heterogeneous batches: query b uses allow list of_query[b] (0xffffffff = none) of G dense bitsets laid out back to
@@ -163,6 +168,11 @@ struct kdb_index {
     bool rows16_refused = false;  // its allocation failed once (no room): not retried
     uint32_t ld16 = 0;            // halfs per row of that copy: ld rounded up to whole 128-byte slabs (zero-filled), so that every
                                   // float32 index -- GloVe's 100 / 200 / 300 columns too -- is ranked by the 256 x 256 tile kernel
+    // float32 cosine indexes of 768 columns: the rows once more as two 16-bit planes + a bound per row (+100 % row
+    // memory), made by the first large-batch walk (kdb_ensure_walk_planes), kept current by every writer of rows
+    uint16_t *d_walk_hi = nullptr, *d_walk_lo = nullptr;
+    float *d_walk_err = nullptr;
+    bool walk_refused = false;    // their allocation failed once (no room): not retried
     float max_norm2 = 0.f; // largest ||x||^2 among the float32 rows uploaded so far (error band of the f16-ranked scan)
     // host copies of the per-node level and first upper slot (incremental refresh validates and places lists with them)
     std::vector<uint8_t> h_levels;
@@ -355,6 +365,10 @@ int kdb_ensure_up_slots(kdb_index *idx, hipStream_t s);
 int kdb_launch_flat_anyk(kdb_index *idx, const KdbView &v, const void *d_q, const float *d_qnorm, uint32_t B, uint32_t k, const uint32_t *d_scan_ids,
                          const uint32_t *d_nscan, unsigned long long *d_keys, uint32_t chunk_q, uint32_t *d_out_ids, float *d_out_dist, uint32_t *d_out_count,
                          int dist64, unsigned long long *d_ctr, hipStream_t s);
+// search.hip: the walk planes of rows first .. first + n - 1 (all three arrays)
+int kdb_launch_walk_planes(const float *d_rows, uint16_t *d_hi, uint16_t *d_lo, float *d_err, uint32_t ld, uint32_t first, uint32_t n, hipStream_t s);
+bool kdb_walk_planes_shape(const kdb_index *idx); // the index is one the planes serve (float32, cosine, 768 columns, not opted out)
+int kdb_ensure_walk_planes(kdb_index *idx, hipStream_t s); // kdb_api.hip, under idx->mu: make them if they can be made; KDB_OK without them too
 int kdb_launch_rows_to_f16(const float *d_rows, uint16_t *d_rows16, uint32_t ld, uint32_t ld16, uint32_t first, uint32_t n, hipStream_t s);
 int kdb_launch_flat_scan_groups(kdb_index *idx, const KdbView &v, const void *d_q, const float *d_qnorm, uint32_t B,
                                 uint32_t k, uint32_t G, const uint32_t *group_offsets, const uint32_t *d_lists,

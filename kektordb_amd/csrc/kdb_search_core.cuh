@@ -61,6 +61,7 @@ struct WaveLds {
     float *ins_d;      // [ins_cap] scatter scratch of the one-pass insertion (may alias nb_d when nobody else writes nb_id)
     uint32_t *ins_id;  // [ins_cap]
     uint32_t ins_cap = 0; // entries the scratch holds: 64 aliased on nb_d / nb_id, 64 x slots when the kernel gives a multi-slot beam its own
+    float qn_up = INFINITY; // planes kernels: >= ||q||_2 of the prepared query (kdb_query_norm_up); +Inf = nothing is decided from the high plane
 };
 // Latency mode (several waves per query): the control words through which the waves of a workgroup talk.  No barriers:
 // a word that announces something (MB_SEQ, ROWS_SEQ, DONE) is written AFTER what it announces and polled by its reader;
@@ -131,10 +132,162 @@ __device__ __forceinline__ float lds_f32_or(const float *p, uint32_t i, uint32_t
     return i < n ? x : other;
 }
 
-template <int PREC, int METRIC, int NCH = 0, int RMAX = 0>
-__device__ __forceinline__ void compute_dists(const KdbView &v, const WaveLds &s, uint32_t n, float qnorm) {
+// ---- walk planes (KdbView::walk_hi / walk_lo / walk_err; layout and bound: walk_planes_kernel in search.hip) ------------
+// >= ||q||_2 of the query in LDS (ld floats, pad columns zero), wave-uniform: the squares are summed in double (no underflow, no
+// overflow, relative error ~1e-14), the root is padded by 2^-20 and rounded up.  A norm beyond 2^20 gives +Inf (no candidate is
+// ever rejected): with ||q|| <= 2^20 and every |x_i| <= 2^100 (else err = +Inf) no partial sum of either evaluation reaches 2^127.
+__device__ __forceinline__ float kdb_query_norm_up(const float *q, uint32_t ld) {
+    double sq = 0.0;
+    for (uint32_t i = (uint32_t)kdb_lane(); i < ld; i += 64u) {
+        const double y = (double)q[i];
+        sq += y * y;
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) sq += __shfl_xor(sq, o, 64);
+    const double nrm = sqrt(sq) * (1.0 + 0x1p-20);
+    float f = (float)nrm;
+    if ((double)f < nrm) f = __uint_as_float(__float_as_uint(f) + 1u);
+    return unif(nrm <= 0x1p20 ? f : INFINITY);
+}
+// the four float32 values of one piece from its halves: words (wh, wl) hold components 0 | 1, (wh2, wl2) components 2 | 3.
+// One v_perm_b32 per value, straight from the packed words (selector bytes 0..3 pick from the second operand, 4..7 from the first,
+// 0x0c is a zero byte).  Deliberately NOT shifts and masks: written that way the compiler shares `wh << 16` / `wh & 0xffff0000`
+// between the high-plane pass and the exact pass and keeps 144 more registers alive across the second round trip (it spilled 390).
+__device__ __forceinline__ float kdb_perm_f(uint32_t a, uint32_t b, uint32_t sel) { return __uint_as_float(__builtin_amdgcn_perm(a, b, sel)); }
+__device__ __forceinline__ float4 kdb_plane_piece(uint32_t wh, uint32_t wh2, uint32_t wl, uint32_t wl2) {
+    return make_float4(kdb_perm_f(wh, wl, 0x05040100u), kdb_perm_f(wh, wl, 0x07060302u), kdb_perm_f(wh2, wl2, 0x05040100u), kdb_perm_f(wh2, wl2, 0x07060302u));
+}
+// ... and from the high halves alone (the low halves read as zero)
+__device__ __forceinline__ float4 kdb_plane_piece_hi(uint32_t wh, uint32_t wh2) {
+    return make_float4(kdb_perm_f(wh, wh, 0x05040c0cu), kdb_perm_f(wh, wh, 0x07060c0cu), kdb_perm_f(wh2, wh2, 0x05040c0cu), kdb_perm_f(wh2, wh2, 0x07060c0cu));
+}
+// RR rows against the query pieces yq (the lane's NCH pieces of the query, read from LDS once for both passes), cosine: element-to-lane,
+// element-to-accumulator and FMA order of kdb_row_partialR_f32 (piece i = 2j + u of the lane is words 2u, 2u + 1 of its j-th load).
+// HI: from the high plane alone.  The scheduling barrier after every piece keeps the unpacking next to its FMAs: left alone, the
+// scheduler unpacks every word of every row first and holds 4 registers per piece where the packed words need 2 (it spilled 170).
+template <int NCH, int RR, bool HI>
+__device__ __forceinline__ void kdb_planes_partial(const uint4 (&h)[RR][NCH / 2], const uint4 (&l)[RR][NCH / 2], const float4 (&yq)[NCH], float (&p)[RR]) {
+    float a[RR][4];
+#pragma unroll
+    for (int r = 0; r < RR; r++) a[r][0] = a[r][1] = a[r][2] = a[r][3] = 0.f;
+#pragma unroll
+    for (int i = 0; i < NCH; i++) {
+        const float4 y = yq[i];
+#pragma unroll
+        for (int r = 0; r < RR; r++) {
+            const uint4 wh = h[r][i >> 1], wl = l[r][i >> 1];
+            const float4 x = HI ? ((i & 1) ? kdb_plane_piece_hi(wh.z, wh.w) : kdb_plane_piece_hi(wh.x, wh.y))
+                                : ((i & 1) ? kdb_plane_piece(wh.z, wh.w, wl.z, wl.w) : kdb_plane_piece(wh.x, wh.y, wl.x, wl.y));
+            a[r][0] = __builtin_fmaf(y.x, x.x, a[r][0]);
+            a[r][1] = __builtin_fmaf(y.y, x.y, a[r][1]);
+            a[r][2] = __builtin_fmaf(y.z, x.z, a[r][2]);
+            a[r][3] = __builtin_fmaf(y.w, x.w, a[r][3]);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    }
+#pragma unroll
+    for (int r = 0; r < RR; r++) p[r] = (a[r][0] + a[r][1]) + (a[r][2] + a[r][3]);
+}
+// One trip of the planes walk: rows base + 4r + g (r < RR) of nb_id -> nb_d.
+// Beam not full (wave-uniform): both planes in one round trip, the exact key of every row -- bytes and latency of the float32 rows.
+// Beam full: the high plane and err[id] first.  With hi = x with its low halves cleared and fl() the kernel's own evaluation order,
+//     |fl(q.x) - q.x| <= g18 ||q|| ||x||,  |fl(q.hi) - q.hi| <= g18 ||q|| ||hi|| <= g18 ||q|| ||x||   (18 roundings per term, no
+//     overflow: kdb_query_norm_up; underflow adds at most 768 * 2^-149 to either),   |q.x - q.hi| <= ||q|| ||x - hi||,   hence
+//     fl(q.x) <= fl(q.hi) + ||q|| (||x - hi|| + 2 g18 ||x||) + 2^-138.
+// err[id] >= ||x - hi|| + 2 g32 ||x|| and qn_up >= ||q||, so  bound = fl(fl(qn_up * err + fl(q.hi)) + 2^-100)  is an upper bound of
+// fl(q.x): the FMA's and the add's roundings (2^-23 |bound| <= 2^-22 ||q|| ||x||, |bound| <= 1.02 ||q|| ||x||) are inside the slack
+// 2 (g32 - g18) ||q|| ||x|| >= 2^-20.3 ||q|| ||x||, and 2^-100 covers the underflow terms.  The candidate's key is -fl(q.x)
+// (kdb_key_from_raw), it passes iff key < worst, so  bound <= -worst  proves that it does not: it is REJECTED, nb_d = +Inf, and its low
+// plane is never read.  A NaN on either side (err = +Inf against qn_up = 0, a beam whose worst is not a number) compares false, and
+// a bound of -Inf decides nothing.  Survivors: the low plane in a second trip (the high words are still in registers), the exact key.
+// No compaction: a survivor stays in its 16-lane group; a rejected row's loads go to row 0 of the low plane (all zero, one cached
+// row) instead, so no load and no FMA is predicated per group -- nothing for the ISA gate to find.
+template <int NCH, int RR>
+__device__ __forceinline__ void kdb_planes_trip(const KdbView &v, const WaveLds &s, uint32_t base, uint32_t n, int g, int t, bool full, float neg_worst) {
+    constexpr int NJ = NCH / 2;
+    uint32_t rr[RR];
+    size_t off[RR];
+    uint4 h[RR][NJ], l[RR][NJ];
+    float er[RR];
+#pragma unroll
+    for (int r = 0; r < RR; r++) {
+        rr[r] = base + 4u * (uint32_t)r + (uint32_t)g;
+        const uint32_t id = lds_u32_or(s.nb_id, rr[r], n, 0u); // row 0 is all zero
+        off[r] = (size_t)id * v.ld;
+        const uint4 *hp = reinterpret_cast<const uint4 *>(v.walk_hi + off[r]);
+#pragma unroll
+        for (int j = 0; j < NJ; j++) h[r][j] = hp[t + 16 * j];
+        er[r] = full ? v.walk_err[id] : 0.f;
+    }
+    float4 yq[NCH];
+#pragma unroll
+    for (int i = 0; i < NCH; i++) yq[i] = reinterpret_cast<const float4 *>(s.q)[t + 16 * i];
+    bool surv[RR];
+    if (full) {
+        float ph[RR];
+        kdb_planes_partial<NCH, RR, true>(h, h, yq, ph);
+        bool any = false;
+#pragma unroll
+        for (int r = 0; r < RR; r++) {
+            const float bound = __builtin_fmaf(s.qn_up, er[r], kdb_reduce16(ph[r])) + 0x1p-100f;
+            surv[r] = rr[r] < n && !(bound <= neg_worst && bound >= -3.0e38f); // (uniform in the 16-lane group)
+            any = any || surv[r];
+        }
+        if (__ballot(any) == 0ull) { // wave-uniform: nobody needs a low plane
+#pragma unroll
+            for (int r = 0; r < RR; r++)
+                if (rr[r] < n && t == 0) s.nb_d[rr[r]] = INFINITY;
+            return;
+        }
+    } else {
+#pragma unroll
+        for (int r = 0; r < RR; r++) surv[r] = true;
+    }
+#pragma unroll
+    for (int r = 0; r < RR; r++) {
+        const uint4 *lp = reinterpret_cast<const uint4 *>(v.walk_lo + (surv[r] ? off[r] : (size_t)0));
+#pragma unroll
+        for (int j = 0; j < NJ; j++) l[r][j] = lp[t + 16 * j];
+    }
+    float p[RR];
+    kdb_planes_partial<NCH, RR, false>(h, l, yq, p);
+#pragma unroll
+    for (int r = 0; r < RR; r++) {
+        const float key = kdb_key_from_raw<KDB_PREC_F32, KDB_METRIC_COSINE>(kdb_reduce16(p[r]));
+        if (rr[r] < n && t == 0) s.nb_d[rr[r]] = surv[r] ? kdb_sane_key(key) : INFINITY;
+    }
+}
+
+// PL = 1 (planes kernels: float32, cosine, v.ld == 64 * NCH, NCH even): the rows are read from the walk planes -- `full` (wave-uniform:
+// the beam holds ef results) and `worst` say which candidates may be rejected from the high plane alone (kdb_planes_trip)
+template <int PREC, int METRIC, int NCH = 0, int RMAX = 0, int PL = 0>
+__device__ __forceinline__ void compute_dists(const KdbView &v, const WaveLds &s, uint32_t n, float qnorm, bool full = false, float worst = INFINITY) {
     const int lane = kdb_lane();
     const int g = lane >> 4, t = lane & 15;
+    if constexpr (PL != 0) { // the trips of the float32 branch below: 4 * R rows, 5 .. 8, 1 .. 4
+        static_assert(PREC == KDB_PREC_F32 && METRIC == KDB_METRIC_COSINE && NCH > 0 && NCH <= 12 && NCH % 2 == 0 && RMAX == 0, "walk planes: float32 cosine, ld == 64 * NCH");
+        // (768 columns: two rows per group and trip, not the float32 branch's three -- two planes of three rows, the query pieces and the
+        // walk's own state do not fit 256 registers; most hops bring fewer than nine new neighbours and take the two-row trip anyway)
+        constexpr int R = 2;
+        // (both are wave-uniform; told so, the branch on `full` is a scalar one and no load or FMA below runs under an exec mask)
+        const float neg_worst = unif(-worst);
+        full = uni(full ? 1u : 0u) != 0u;
+        for (uint32_t base = 0; base < n;) {
+            const uint32_t left = n - base;
+            if (left > 4u * (R - 1) || R == 1) {
+                kdb_planes_trip<NCH, R>(v, s, base, n, g, t, full, neg_worst);
+                base += 4u * R;
+            } else if (left > 4u) {
+                kdb_planes_trip<NCH, 2>(v, s, base, n, g, t, full, neg_worst);
+                base += 8u;
+            } else {
+                kdb_planes_trip<NCH, 1>(v, s, base, n, g, t, full, neg_worst);
+                base += 4u;
+            }
+        }
+        wave_lds_fence();
+        return;
+    }
     if constexpr (PREC == KDB_PREC_F32 && NCH > 0 && NCH <= 16 && KDB_F32_DUAL) { // 4*R rows per round trip
         constexpr int R0 = NCH <= 2 ? KDB_F32_ROWS2 : NCH <= 6 ? KDB_F32_ROWS6 : NCH <= 12 ? KDB_F32_ROWS : 2;
         constexpr int R = (RMAX > 0 && R0 > RMAX) ? RMAX : R0;
@@ -1517,7 +1670,8 @@ __device__ __forceinline__ void kdb_tiny_dot_rule(BeamT &b, unsigned long long p
 }
 
 // searchLayerUnlocked (hnsw_index.go:2351-2611) on one layer, ONE wave; leaves the result in the beam.
-template <int PREC, int METRIC, int NCH, class BeamT, class VisT>
+// PL = 1: the rows come from the walk planes (compute_dists); the walk, its answers and its counters are the same.
+template <int PREC, int METRIC, int NCH, class BeamT, class VisT, int PL = 0>
 __device__ void search_layer(const KdbView &v, const WaveLds &s, BeamT &b, VisT &vis,
                              const uint32_t *allow, uint32_t ep, int level, uint32_t ef, float qnorm, QCtr &ctr,
                              EpKnown epk = EpKnown()) {
@@ -1533,7 +1687,7 @@ __device__ void search_layer(const KdbView &v, const WaveLds &s, BeamT &b, VisT 
     if (!epk.known) {
         if (lane == 0) s.nb_id[0] = ep;
         wave_lds_fence();
-        compute_dists<PREC, METRIC, NCH>(v, s, 1, qnorm);
+        compute_dists<PREC, METRIC, NCH, 0, PL>(v, s, 1, qnorm);
         ep_key = unif(s.nb_d[0]);
         ep_lo = WK ? uni(s.nb_lo[0]) : 0u;
     }
@@ -1586,7 +1740,9 @@ __device__ void search_layer(const KdbView &v, const WaveLds &s, BeamT &b, VisT 
         const uint32_t my_id = lds_u32_or(s.nb_id, (uint32_t)lane, n, 0u);
         const uint32_t delw = ((uint32_t)lane < n && v.has_deleted) ? v.deleted[my_id >> 5] : 0u;
         KDB_T(const unsigned long long tq1 = __builtin_readcyclecounter();)
-        compute_dists<PREC, METRIC, NCH>(v, s, n, qnorm);
+        // (PL: a candidate the high plane proves "not < worst" while the beam is full comes back as +Inf -- not in `pass` below, and
+        // nothing after `pass` looks at a candidate outside it; n_dist counts it like any other)
+        compute_dists<PREC, METRIC, NCH, 0, PL>(v, s, n, qnorm, !(b.n_res < ef), b.worst);
         ctr.n_dist += n;
         const bool my_nr = ((delw >> (my_id & 31)) & 1u) != 0;
         const float my_d = lds_f32_or(s.nb_d, (uint32_t)lane, n, INFINITY);

@@ -375,6 +375,70 @@ int kdb_launch_row_norms(const KdbView &v, float *d_norms, uint32_t first, uint3
     return KDB_OK;
 }
 
+// Walk planes (KdbView::walk_hi / walk_lo / walk_err): the float32 rows once more as a plane of high and a plane of low
+// 16-bit halves, permuted inside the row so that the j-th 16-byte load of lane t (t = lane & 15) of either plane holds the eight
+// halves of the lane's float32 pieces t + 16 * 2j and t + 16 * (2j + 1) -- the pieces kdb_row_partialR_f32 gives that lane, in its
+// order.  Piece c = t + 16 i of a row therefore lands at halves (t + 16 (i >> 1)) * 8 + (i & 1) * 4 .. + 3 of the plane row.
+// err[id] >= ||x - hi||_2 + 2 gamma ||x||_2 (hi = x with the low halves cleared), computed in double and rounded UP to float;
+// gamma = 32 * 2^-24 covers the 18 roundings a term of either evaluation passes through (12 FMAs, 2 adds, 4 reduction adds) with
+// room for the roundings of the comparison itself (compute_dists).  +Inf ("never decided from the high plane") for a row with a
+// component that is not finite or beyond 2^100: the bound's derivation assumes that neither evaluation overflows.
+// 16 lanes per row, 16 rows per block; ld is a multiple of 128 (kdb_walk_planes_shape: 768 so far -- 384 and 128 columns compiled
+// to kernels that spilled a hundred registers at their four waves per SIMD and stay on the float32 rows).
+__global__ void __launch_bounds__(256) walk_planes_kernel(const float *__restrict__ rows, uint16_t *__restrict__ hi, uint16_t *__restrict__ lo,
+                                                           float *__restrict__ err, uint32_t ld, uint32_t first, uint32_t n) {
+    const uint32_t t = threadIdx.x & 15u;
+    const uint32_t r = blockIdx.x * 16u + (threadIdx.x >> 4);
+    const bool act = r < n;
+    const size_t id = (size_t)first + (act ? r : 0u);
+    const float4 *r4 = reinterpret_cast<const float4 *>(rows + id * ld);
+    uint2 *h2 = reinterpret_cast<uint2 *>(hi + id * ld);
+    uint2 *l2 = reinterpret_cast<uint2 *>(lo + id * ld);
+    double sd = 0.0, sx = 0.0;
+    bool bad = false;
+    for (uint32_t i = 0; i < (ld >> 6); i++) {
+        const float4 x = r4[t + 16u * i];
+        const uint32_t b[4] = {__float_as_uint(x.x), __float_as_uint(x.y), __float_as_uint(x.z), __float_as_uint(x.w)};
+        const float f[4] = {x.x, x.y, x.z, x.w};
+#pragma unroll
+        for (int c = 0; c < 4; c++) {
+            bad = bad || !(__builtin_fabsf(f[c]) <= 0x1p100f);
+            const double d = (double)f[c] - (double)__uint_as_float(b[c] & 0xffff0000u);
+            sd += d * d;
+            sx += (double)f[c] * (double)f[c];
+        }
+        if (act) {
+            const uint32_t at = (t + 16u * (i >> 1)) * 2u + (i & 1u); // in 8-byte units
+            h2[at] = make_uint2((b[0] >> 16) | (b[1] & 0xffff0000u), (b[2] >> 16) | (b[3] & 0xffff0000u));
+            l2[at] = make_uint2((b[0] & 0xffffu) | (b[1] << 16), (b[2] & 0xffffu) | (b[3] << 16));
+        }
+    }
+#pragma unroll
+    for (int o = 8; o >= 1; o >>= 1) {
+        sd += __shfl_xor(sd, o, 64);
+        sx += __shfl_xor(sx, o, 64);
+        bad = bad || __shfl_xor((int)bad, o, 64) != 0;
+    }
+    if (act && t == 0u) {
+        const double e = (sqrt(sd) + 0x1p-18 * sqrt(sx)) * (1.0 + 0x1p-30); // (the double roundings of the sums and roots)
+        float fe = (float)e;
+        if ((double)fe < e) fe = __uint_as_float(__float_as_uint(fe) + 1u); // round up (e >= 0; past the largest float: +Inf)
+        err[id] = bad ? INFINITY : fe;
+    }
+}
+
+int kdb_launch_walk_planes(const float *d_rows, uint16_t *d_hi, uint16_t *d_lo, float *d_err, uint32_t ld, uint32_t first, uint32_t n, hipStream_t s) {
+    if (n == 0) return KDB_OK;
+    hipLaunchKernelGGL(walk_planes_kernel, dim3((n + 15u) / 16u), dim3(256), 0, s, d_rows, d_hi, d_lo, d_err, ld, first, n);
+    KDB_HIP(hipGetLastError());
+    return KDB_OK;
+}
+
+bool kdb_walk_planes_shape(const kdb_index *idx) {
+    return idx->desc.precision == KDB_PREC_F32 && idx->desc.metric == KDB_METRIC_COSINE && idx->ld == 768u &&
+           !(idx->desc.reserved & KDB_INDEX_NO_WALK_PLANES);
+}
+
 // One heap-order pass BESIDE its search kernel at a time per process (launch_any below): the last such launch's closing event.
 namespace {
 std::mutex g_ov_mu;

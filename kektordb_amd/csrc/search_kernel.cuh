@@ -69,7 +69,10 @@ constexpr int kdb_search_minw() {
     if (PREC == KDB_PREC_F16) return NCH > 16 ? 2 : KDB_F16_MINW; // (1536 columns: three waves per SIMD spilled ~40 registers -- and the gate found a reload ahead of an exec restore there)
     return NCH > 12 ? 2 : NCH > 6 ? KDB_F32_MINW : NCH > 4 ? KDB_F32_MINW6 : NCH == 0 ? KDB_GENERIC_MINW : KDB_SEARCH_MINW; // wide rows keep 16+ float4 per lane in flight
 }
-template <int PREC, int METRIC, int NCH, int BS, int VIS, int WIDE = 1>
+// PL = 1: a planes kernel (one wave per query only): rows are read from the walk planes (v.walk_hi / walk_lo / walk_err, compute_dists).
+template <int PREC, int METRIC, int NCH>
+constexpr bool kdb_planes_kernel() { return PREC == KDB_PREC_F32 && METRIC == KDB_METRIC_COSINE && NCH == 12; } // (768 columns: kdb_walk_planes_shape)
+template <int PREC, int METRIC, int NCH, int BS, int VIS, int WIDE = 1, int PL = 0>
 __global__ void __launch_bounds__(64 * WIDE, (kdb_search_minw<PREC, NCH, WIDE>()))
 hnsw_search_kernel(KdbView v, const void *__restrict__ queries, const float *__restrict__ qnorms, uint32_t raw, uint32_t B,
                    uint32_t k, uint32_t ef, const uint32_t *__restrict__ allow, KdbMultiAllow ma, uint32_t entry,
@@ -161,6 +164,7 @@ hnsw_search_kernel(KdbView v, const void *__restrict__ queries, const float *__r
         // query -> LDS (prepared in the reference's order: kdb_load_query)
         bool dead = false; // a query that is not finite: no results, no walk
         const float qnorm = kdb_load_query<PREC>(v, s, queries, qnorms, raw, qi, &dead);
+        if constexpr (PL != 0) s.qn_up = kdb_query_norm_up(s.q, v.ld);
 
         QCtr ctr{};
         b.tied = 0u;
@@ -187,7 +191,7 @@ hnsw_search_kernel(KdbView v, const void *__restrict__ queries, const float *__r
         }
         auto layer = [&](uint32_t from, int l, uint32_t ef_l) {
             if constexpr (WIDE > 1) search_layer_wide<PREC, METRIC, NCH, decltype(b), WIDE>(v, s, b, wc, from, l, ef_l, q_allow, ctr, epk);
-            else search_layer<PREC, METRIC, NCH, decltype(b), decltype(vis)>(v, s, b, vis, q_allow, from, l, ef_l, qnorm, ctr, epk);
+            else search_layer<PREC, METRIC, NCH, decltype(b), decltype(vis), PL>(v, s, b, vis, q_allow, from, l, ef_l, qnorm, ctr, epk);
         };
         // greedy descent, ef = 1 (:450-459)
         for (int l = v.max_level; l > 0 && !failed; l--) {
@@ -344,6 +348,7 @@ static int launch_search_bs(kdb_index *idx, const KdbView &v, const void *d_q, c
     // compare-and-swap probe loop that ends when the slowest of 32 lanes has found its slot -- at a load below 7 % that is
     // two rounds, not three
     const uint32_t hsize_w = hsize ? (hsize * 4u > 16384u ? 16384u : hsize * 4u) : 0u;
+    KdbView vk = v; // the search kernel's view: with the walk planes once a planes kernel has been picked (use_planes)
     auto launch_any = [&](auto kern, uint32_t vis_size, uint32_t waves, size_t lds) -> int {
         if (lds > 64 * 1024) KDB_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         uint32_t grid = ncu * (uint32_t)occupancy_blocks(kern, (int)(64u * waves), lds);
@@ -437,7 +442,7 @@ static int launch_search_bs(kdb_index *idx, const KdbView &v, const void *d_q, c
             KDB_HIP(hipEventRecord(ln.side_ev0, s));
             KDB_HIP(hipStreamWaitEvent(ln.side, ln.side_ev0, 0));
         }
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(64u * waves), lds, s, v, d_q, d_qnorm, raw_l, B, k, eff, d_allow, ma, entry, beam_cap, nr_cap, vis_size,
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(64u * waves), lds, s, vk, d_q, d_qnorm, raw_l, B, k, eff, d_allow, ma, entry, beam_cap, nr_cap, vis_size,
                            idx->d_visited, reinterpret_cast<uint32_t *>(d_acc + 2), d_ctr, d_out_ids, d_out_dist, d_out_count, d_tr_ndist, d_tr_nhops,
                            d_tie_list, d_stash);
         KDB_HIP(hipGetLastError());
@@ -469,6 +474,23 @@ static int launch_search_bs(kdb_index *idx, const KdbView &v, const void *d_q, c
     };
     auto launch_lds = [&](auto kern, uint32_t vis_size, size_t lds) -> int { return launch_any(kern, vis_size, 1u, lds); };
     (void)launch_lds;
+    // Walk planes: asked for only HERE, by a launch that has picked the one-wave register-beam kernel of an index the planes serve
+    // (latency-mode launches, the LDS beam of ef > 256, L2 and quantised indexes never allocate them); made by the first such launch, under idx->mu.  *use = false (no room,
+    // opted out, another shape): the walk reads the float32 rows as ever.
+    auto use_planes = [&](bool *use) -> int {
+        *use = false;
+        if constexpr (kdb_planes_kernel<PREC, METRIC, NCH>()) {
+            if (v.ld != 64u * NCH || v.rows != idx->d_rows || !kdb_walk_planes_shape(idx)) return KDB_OK;
+            const int rc = kdb_ensure_walk_planes(idx, s);
+            if (rc) return rc;
+            if (!idx->d_walk_hi) return KDB_OK;
+            vk.walk_hi = idx->d_walk_hi;
+            vk.walk_lo = idx->d_walk_lo;
+            vk.walk_err = idx->d_walk_err;
+            *use = true;
+        }
+        return KDB_OK;
+    };
     if constexpr (BS == 1 || BS == 2 || BS == 4) {
         // latency mode: a batch that leaves most of the chip idle gives every query four waves: wave 0 walks, the other
         // three evaluate a hop's rows (one HBM round trip per hop instead of three), wave 1 prepares the next node while
@@ -497,7 +519,15 @@ static int launch_search_bs(kdb_index *idx, const KdbView &v, const void *d_q, c
     // bookkeeping for one query per wave becomes vector work per half (a half-ballot is five instructions, not one), and a four-slot
     // beam per half triples the insertion: more instructions per QUERY, not fewer.  Not shipped.)
     if constexpr (BS == 1 || BS == 2 || BS == 4) {
-        if (hsize) return launch(hnsw_search_kernel<PREC, METRIC, NCH, BS, 1>, hsize);
+        if (hsize) {
+            if constexpr (kdb_planes_kernel<PREC, METRIC, NCH>()) {
+                bool planes = false;
+                const int rc = use_planes(&planes);
+                if (rc) return rc;
+                if (planes) return launch(hnsw_search_kernel<PREC, METRIC, NCH, BS, 1, 1, 1>, hsize);
+            }
+            return launch(hnsw_search_kernel<PREC, METRIC, NCH, BS, 1>, hsize);
+        }
     }
     if constexpr (BS == 0) {
         // ef 261 .. 1040: the visited set of a walk (~9 ef ids) still fits LDS when the batch leaves LDS free -- 32 KB (64 KB above

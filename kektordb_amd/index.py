@@ -60,9 +60,12 @@ def _ready(stream):
 
 class HipIndex:
     def __init__(self, dim: int, metric: int = COSINE, precision: int = F32, m: int = 16,
-                 ef_construction: int = 200, capacity: int = 1 << 20, device_id: int = 0, f16_shadow: bool = True):
+                 ef_construction: int = 200, capacity: int = 1 << 20, device_id: int = 0, f16_shadow: bool = True,
+                 walk_planes: bool = True):
         """f16_shadow: float32 indexes make a half-precision RANKING copy of the rows at their first exact scan (+50 % row
-        memory from then on, answers unchanged); False sets KDB_INDEX_NO_F16_SHADOW (never)."""
+        memory from then on, answers unchanged); False sets KDB_INDEX_NO_F16_SHADOW (never).
+        walk_planes: float32 cosine indexes of 768 columns make the walk planes (the rows as two 16-bit planes + a bound per
+        row, +100 % row memory, answers unchanged) at their first large-batch walk; False sets KDB_INDEX_NO_WALK_PLANES (never)."""
         self.L = _lib.load()
         self.dim, self.metric, self.precision = int(dim), int(metric), int(precision)
         self.m = m if m > 0 else 16
@@ -71,7 +74,7 @@ class HipIndex:
         self.device_id = device_id
         self.needs_refine = False
         desc = _lib.IndexDesc(self.dim, self.metric, self.precision, self.m, self.ef_construction, self.capacity,
-                              device_id, 0 if f16_shadow else 1)
+                              device_id, (0 if f16_shadow else 1) | (0 if walk_planes else 2))
         h = C.c_void_p()
         check(self.L.kdb_index_create(C.byref(desc), C.byref(h)), "kdb_index_create")
         self.h = h
@@ -157,6 +160,9 @@ class HipIndex:
 
     def drop_f16_shadow(self, refuse_for_good: bool = False):
         check(self.L.kdb_index_drop_f16_shadow(self.h, 1 if refuse_for_good else 0), "kdb_index_drop_f16_shadow")
+
+    def drop_walk_planes(self, refuse_for_good: bool = False):
+        check(self.L.kdb_index_drop_walk_planes(self.h, 1 if refuse_for_good else 0), "kdb_index_drop_walk_planes")
 
     def set_count(self, count: int):
         check(self.L.kdb_index_set_count(self.h, int(count)), "set_count")
