@@ -83,9 +83,9 @@ struct FsParams {
     float *g_pub;             // [n_stripes][qstride] shared thresholds: stripe s publishes the r-th smallest key of its list, r = ceil(kl / n_stripes)
     float *part_thr;          // [n_stripes][qstride] the threshold a stripe ended with: its list is complete for keys <= that
     uint32_t fb_alt;          // 1: odd tiles walk their slabs backwards
-    uint32_t fb_grow;         // 1: compaction rounds thin out once the thresholds have settled (KDB_FB_NOGROW: A/B switch)
-    uint32_t fb_seeded;       // 1: a seed launch published first thresholds into g_pub (KDB_FB_NOSEED: A/B switch)
-    uint32_t fb_pref;         // 1: threads 0..255 pull the row lines of the slab three steps ahead into L2 (KDB_FB_PREFETCH)
+    uint32_t fb_grow;         // 1: compaction rounds thin out once the thresholds have settled (the host always sets it)
+    uint32_t fb_seeded;       // 1: a seed launch published first thresholds into g_pub
+    uint32_t fb_pref;         // 1: threads 0..255 pull the row lines of the slab three steps ahead into L2 (the host never sets it)
     uint32_t fb_seed_nstr;    // the number of stripes the HOST derived when it decided so: both kernels check it against fs_resolve's
     uint32_t fb_slack, fb_period; // compaction rounds every fb_period tiles for lists longer than kl + fb_slack
     uint32_t fb_dbg;          // measurement switches (KDB_FB_DBG): 1 no selection, 2 no DMA after the first slab, 4 no MFMAs
@@ -627,7 +627,7 @@ __host__ __device__ inline size_t fss_q_bytes(uint32_t ld) {
 // workgroups per CU).  6 is preferred (2 x 12 row loads per lane in flight; 1 % ahead of 8 on the gathered scan of config 5, equal
 // on streamed rows), then 8, 7, 5, 4; rows of exactly two chunks of 3 / 2 / 1 steps (192 / 128 / 64 halfs) get those (16 queries
 // x 1M x 128 columns: 0.195 ms generic, 0.084 ms with CS = 2).  0: the generic instantiation (any row length; 289 registers,
-// one workgroup per CU).  KDB_FSS_CS forces a feasible value (measurements).
+// one workgroup per CU).
 template <int PREC>
 __host__ inline uint32_t fss_exact_cs(uint32_t ld) {
     constexpr bool RAW = PREC == KDB_PREC_I8 || PREC == FS_PREC_F32R || PREC == KDB_PREC_F16;
@@ -638,11 +638,6 @@ __host__ inline uint32_t fss_exact_cs(uint32_t ld) {
     auto fits = [&](uint32_t c) { // whole chunks, an even number of them; a chunk of fewer than 4 steps only for rows of two chunks
         return c >= 1u && c <= 8u && nsteps % (2u * c) == 0u && (c >= 4u || nsteps == 2u * c);
     };
-    if (const char *e = KDB_AB_ENV("KDB_FSS_CS")) {
-        const uint32_t c = (uint32_t)atoi(e);
-        if (c == 0u) return 0u;
-        if (fits(c)) return c;
-    }
     for (uint32_t c : {6u, 8u, 7u, 5u, 4u, 3u, 2u, 1u}) // (7 / 5 / 3 / 2 / 1: rows of 14 / 10 / 6 / 4 / 2 steps -- 300, 100 / 128, 64 columns as halfs)
         if (fits(c)) return c;
     return 0u;
@@ -1004,9 +999,6 @@ __device__ __forceinline__ float fs_unpack_key(unsigned long long x) {
 }
 
 #include "flat_scan_big.cuh"
-#ifdef KDB_AB // A/B build only (make ab): the out-of-phase variant, measured slower in round 5
-#include "flat_scan_skew.cuh"
-#endif
 
 // Merge the per-stripe lists of one query (block = 256 threads): SELECT the best nf entries of the n gathered
 // ones (nf = k for cosine, the re-score set kl for L2) with a block-wide bitwise search for the nf-th smallest
@@ -1737,29 +1729,23 @@ merge_topk_kernel(int negate, uint32_t G, uint32_t B, uint32_t k, const uint32_t
 
 } // namespace
 
-// Batches of at least this many queries rank with the big-tile kernel (KDB_FLAT_BIG_MIN overrides for measurements;
-// 0x7fffffff switches it off).
-static int kdb_flat_big_min() {
-    static int v = -1;
-    if (v < 0) {
-        const char *e = KDB_AB_ENV("KDB_FLAT_BIG_MIN");
-        v = e ? atoi(e) : 33;
-        if (v < 1) v = 1;
-    }
-    return v;
-}
-
-// Batches up to this many queries use flat_scan_small_kernel (KDB_FLAT_SMALL_MAX overrides for measurements).
-static int kdb_flat_small_max() {
-    static int v = -1;
-    if (v < 0) {
-        const char *e = KDB_AB_ENV("KDB_FLAT_SMALL_MAX");
-        v = e ? atoi(e) : 64;
-        if (v < 0) v = 0;
-        if (v > 128) v = 128; // the merge layout of the small kernel holds one 128-query tile
-    }
-    return v;
-}
+// Batches of at least this many queries rank with the big-tile kernel.
+constexpr uint32_t FS_BIG_MIN = 33;
+// Batches up to this many queries use flat_scan_small_kernel (the merge layout of the small kernel holds one 128-query tile, so
+// never more than 128).
+constexpr uint32_t FS_SMALL_MAX = 64;
+// One launch = one round of 512 workgroups = (stripes) x (query tiles): with more than 64 query tiles the stripes
+// get so long, and so many workgroups stream the same stripe out of step, that the rows fall out of L2 (32768
+// queries in one launch: 3x slower per query, 150x the HBM traffic).  Larger batches run as 8192-query launches.
+constexpr uint32_t FS_MAX_B = 8192;
+// exact pass, first tier: up to FS_FEW unsettled queries go through the streaming kernel (16 queries per workgroup, the
+// rows read at HBM speed by every CU) -- the tile kernel gives ONE query tile a handful of stripes: a single unsettled
+// query of an 8192-query batch cost 78 ms behind a 12 ms ranking scan (seen once in five calls on the clustered corpus)
+constexpr uint32_t FS_FEW = 64;
+constexpr size_t FS_LDS_MAX = 150u * 1024u; // what a workgroup of the streaming / rescue kernels may ask for
+// the 128 x 128 tile kernel's LDS: both operand tiles, thresholds, the per-query mini queues, the LDS lists
+constexpr size_t FS_TILE_LDS = (size_t)(FS_TR + FS_TQ) * FS_LDS_STRIDE * 4 + FS_TQ * 12 + (size_t)FS_TQ * FS_QPER * 8 +
+                               (size_t)FS_TQ * FS_LDS_KL * 8 + (size_t)FS_TQ * 8 + 32;
 
 int kdb_launch_merge_topk(int negate, uint32_t G, uint32_t B, uint32_t k, const uint32_t *d_in_ids,
                           const float *d_in_dist, const uint32_t *d_in_count, size_t stride_e, size_t stride_c,
@@ -1797,70 +1783,247 @@ int kdb_launch_rows_to_f16(const float *d_rows, uint16_t *d_rows16, uint32_t ld,
     return KDB_OK;
 }
 
-int kdb_launch_flat_scan(kdb_index *idx, const KdbView &v, const void *d_q, const float *d_qnorm, uint32_t B,
-                         uint32_t k, const uint32_t *d_allow, const uint32_t *d_first_allowed, uint32_t *d_out_ids,
-                         float *d_out_dist, uint32_t *d_out_count, int queries_normalised, hipStream_t s) {
-    if (k == 0 || k > KDB_FLAT_MAX_K) {
-        kdb_set_error("flat scan: k must be in 1..%u (got %u)", KDB_FLAT_MAX_K, k);
-        return KDB_ERR_INVALID;
+// Host side of the scan: what both launchers (one allow list for the batch / one per group of queries) share.
+
+// The (metric, precision) pairs the scan kernels are built for, as compile-time tags: f(metric tag, precision tag).  F32_AS names
+// the precision tag a float32 index gets: FS_PREC_F32R where the kernel RANKS float32 rows as halfs.
+template <int V>
+using FsTag = std::integral_constant<int, V>;
+template <int F32_AS = KDB_PREC_F32, class F>
+static int fs_dispatch(uint32_t precision, uint32_t metric, F &&f) {
+    if (precision == KDB_PREC_I8) return f(FsTag<KDB_METRIC_COSINE>{}, FsTag<KDB_PREC_I8>{}); // int8 is cosine only
+    if (precision == KDB_PREC_F16) return f(FsTag<KDB_METRIC_L2>{}, FsTag<KDB_PREC_F16>{});   // f16 is L2 only
+    if (metric == KDB_METRIC_COSINE) return f(FsTag<KDB_METRIC_COSINE>{}, FsTag<F32_AS>{});
+    return f(FsTag<KDB_METRIC_L2>{}, FsTag<F32_AS>{});
+}
+// float32 indexes only (the band merge and the exact pass of an f16-ranked scan): the metric alone
+template <class F>
+static int fs_dispatch_f32(uint32_t metric, F &&f) {
+    if (metric == KDB_METRIC_COSINE) return f(FsTag<KDB_METRIC_COSINE>{});
+    return f(FsTag<KDB_METRIC_L2>{});
+}
+
+// What every launch of one scan call shares.
+struct FsCall {
+    kdb_index *idx;
+    const KdbView &v;
+    const void *d_q;
+    const float *d_qnorm;
+    uint32_t B, k, kl;
+    uint32_t *d_out_ids; float *d_out_dist; uint32_t *d_out_count;
+    hipStream_t s;
+};
+
+// Scratch carving: take() returns the next region and advances past it, in whole 256-byte units.
+struct FsBump {
+    unsigned char *at;
+    template <class T>
+    T *take(size_t bytes) {
+        T *r = reinterpret_cast<T *>(at);
+        at += (bytes + 255) & ~(size_t)255;
+        return r;
     }
-    if (B == 0) return KDB_OK;
-    if (k > 128) { // beyond the tile kernels' lists: every distance in the final order + a radix select per query (flat_anyk.hip)
-        const size_t ids_b = ((size_t)v.count * 4 + 255) / 256 * 256;
-        const bool ids_needed = d_allow != nullptr || idx->n_deleted > 0;
-        const size_t stride = ((size_t)v.count + 63) & ~(size_t)63;
-        uint32_t chunk_q = (uint32_t)(((size_t)2 << 30) / (stride * 8)); // <= 2 GB of keys at a time
-        if (chunk_q < 1) chunk_q = 1;
-        if (chunk_q > B) chunk_q = B;
-        if (chunk_q > 65535u) chunk_q = 65535u;
-        int rc = kdb_ensure_scratch(idx, ids_b + 256 + (size_t)chunk_q * stride * 8 + 256);
+};
+
+// measurement switches of the `make dbg` build (KDB_FB_DBG: big-tile kernel, KDB_FSS_DBG: small kernel); no other build reads them
+static uint32_t fs_dbg_switches(const char *name) {
+#ifdef KDB_FB_DEBUG
+    const char *e = getenv(name);
+    return e ? (uint32_t)atoi(e) : 0u;
+#else
+    (void)name;
+    return 0u;
+#endif
+}
+
+// per-stripe list length: a stripe keeps its k+16 best by the ranking key; the merge kernel checks that no full
+// list reaches into the error band of the k-th key (else the query goes to the exact / rescue pass)
+static uint32_t fs_kl(uint32_t k) { return k + 16 > 144 ? 144 : k + 16; }
+static uint32_t fs_cap_s(uint32_t kl) { return kl + FS_TR + FSS_SLACK; } // a query's buffer in the small kernel
+
+// LDS of the small kernel: 16 queries in the encoding PREC, their buffers, thresholds and counts
+template <int PREC>
+static size_t fs_small_lds_as(uint32_t ld, uint32_t kl) {
+    return fss_q_bytes<PREC>(ld) + (size_t)FSS_TQ * fs_cap_s(kl) * 8 + FSS_TAIL;
+}
+static size_t fs_small_lds(const KdbView &v, uint32_t kl) {
+    return v.precision == KDB_PREC_I8    ? fs_small_lds_as<KDB_PREC_I8>(v.ld, kl)
+           : v.precision == KDB_PREC_F16 ? fs_small_lds_as<KDB_PREC_F16>(v.ld, kl)
+                                         : fs_small_lds_as<KDB_PREC_F32>(v.ld, kl);
+}
+// LDS of the merge kernel: <= FS_MAX_MERGE gathered entries, the finalists, the query, the stripes' counts and thresholds
+static size_t fs_merge_lds(const KdbView &v, uint32_t want, uint32_t kl) {
+    return (size_t)want * kl * 8 + FS_FIN * 8 + 48 + 1024 + (size_t)v.ld * 4 + (size_t)want * 12 + 16;
+}
+
+// float32 cosine / L2: rank on the f16 MFMA inside a rigorous error band, settle the rest exactly (only when the library
+// normalised the queries itself and the rows are far from the f16 range limit).  KDB_FLAT_EXACT_ONLY is read per call: a
+// test toggles it inside one process.
+static bool fs_rank16_ok(const kdb_index *idx, const KdbView &v, bool queries_normalised) {
+    return v.precision == KDB_PREC_F32 && (v.metric == KDB_METRIC_L2 || queries_normalised) && idx->max_norm2 > 0.f &&
+           idx->max_norm2 <= 1.0e4f && !getenv("KDB_FLAT_EXACT_ONLY");
+}
+// eps bounds |q.x (wave order) - sum f16(q)f16(x) (MFMA order)| for rows and queries of norm <= 1: f16 rounding
+// of both factors (2^-10 and its square), f32 summation in either order (dim * 2^-23); band = 2 * eps
+// rows of norm R widen it by R (queries are normalised by the preparation step)
+static float fs_band(const kdb_index *idx, const KdbView &v) {
+    const float rmax = v.metric == KDB_METRIC_COSINE ? (idx->max_norm2 > 1.0f ? sqrtf(idx->max_norm2) : 1.0f) : sqrtf(idx->max_norm2);
+    return 2.0f * (9.9e-4f + (float)v.dim * 2.4e-7f) * rmax * 1.001f; // cosine: the band; L2: per unit of ||q|| (x2 in the kernel)
+}
+
+// float32 indexes: the ranking copy has its own row stride (idx->ld16: whole 128-byte slabs, zero pad).  The kernels that
+// read it take a view with that stride (this one) and queries re-laid with it (fs_pad_queries); everything exact keeps v and d_q.
+static KdbView fs_rank_view(const kdb_index *idx, const KdbView &v) {
+    KdbView vr = v;
+    if (v.precision == KDB_PREC_F32 && idx->d_rows16 != nullptr && idx->ld16 != v.ld) vr.ld = idx->ld16;
+    return vr;
+}
+static int fs_pad_queries(const KdbView &v, const KdbView &vr, const void *d_q, size_t n_rows, float *d_qp, hipStream_t s) {
+    const size_t quads = n_rows * (vr.ld >> 2);
+    hipLaunchKernelGGL(pad_queries_kernel, dim3((unsigned)((quads + 255) / 256)), dim3(256), 0, s, reinterpret_cast<const float *>(d_q), v.ld, d_qp,
+                       vr.ld, quads);
+    KDB_HIP(hipGetLastError());
+    return KDB_OK;
+}
+
+// the small kernel over n_q16 16-query tiles x pp.want stripes (upper bound: workgroups of stripes past the resolved count
+// return at once)
+template <class K>
+static int fs_launch_small(const FsCall &c, K kern, const KdbView &vv, const void *qv, const FsParams &pp, uint32_t n_q16, size_t lds) {
+    KDB_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(kern, dim3((pp.want + 7) / 8 * 8 * n_q16), dim3(256), lds, c.s, vv, reinterpret_cast<const float *>(qv), pp, n_q16,
+                       fs_cap_s(c.kl));
+    KDB_HIP(hipGetLastError());
+    return KDB_OK;
+}
+// the 128 x 128 tile kernel
+template <class K>
+static int fs_launch_tile(const FsCall &c, K kern, const KdbView &vv, const void *qv, const FsParams &pp) {
+    KDB_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)FS_TILE_LDS));
+    hipLaunchKernelGGL(kern, dim3((pp.want + 7) / 8 * 8 * pp.n_qtiles), dim3(256), FS_TILE_LDS, c.s, vv, reinterpret_cast<const float *>(qv), pp);
+    KDB_HIP(hipGetLastError());
+    return KDB_OK;
+}
+template <class K>
+static int fs_launch_merge(const FsCall &c, K kern, const FsParams &pp, const void *qv) {
+    const uint32_t nmax = pp.want * c.kl; // <= FS_MAX_MERGE entries gathered per query
+    const size_t mlds = fs_merge_lds(c.v, pp.want, c.kl);
+    KDB_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mlds));
+    hipLaunchKernelGGL(kern, dim3(c.B), dim3(256), mlds, c.s, c.v, reinterpret_cast<const float *>(qv), c.d_qnorm, pp, c.k, nmax, c.d_out_ids,
+                       c.d_out_dist, c.d_out_count);
+    KDB_HIP(hipGetLastError());
+    return KDB_OK;
+}
+// exact scans isolate their finalists inside the rounding band (FM_ROUND); what that cannot settle -- a cluster of
+// near-duplicates larger than a stripe list or than the 1024 re-score slots -- is re-scanned in the final summation
+// order (rtq queries per work item) and merged again.  All three launches return at once when the list is empty (the usual case).
+template <int M, int P>
+static int fs_round_merge_and_rescue(const FsCall &c, const FsParams &pp, const void *qv, uint32_t rtq) {
+    int rc = fs_launch_merge(c, flat_merge_kernel<M, P, FM_ROUND>, pp, qv);
+    if (rc) return rc;
+    const size_t rlds = fsr_lds_bytes(c.v.ld, rtq);
+    auto scan_k = flat_rescue_kernel<M, P>;
+    KDB_HIP(hipFuncSetAttribute((const void *)scan_k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)rlds));
+    hipLaunchKernelGGL(scan_k, dim3(512), dim3(256), rlds, c.s, c.v, reinterpret_cast<const float *>(qv), pp, rtq);
+    KDB_HIP(hipGetLastError());
+    return fs_launch_merge(c, flat_merge_kernel<M, P, FM_EXACT>, pp, qv);
+}
+
+// Everything after the ranking launch.  p: the ranking scan's parameters (ranked16: with band and fb_count set, *fb_count
+// zero).  ranked16: the band merge settles what it can; exact_pass(metric tag, p2, qx) then fills p2 (the exact scan's
+// parameters) and qx (the queries it read), having scanned the queries the band merge marked or listed -- usually none: every
+// launch of the exact pass returns at once; their number never leaves the device.
+template <class ExactPass>
+static int fs_settle(const FsCall &c, const FsParams &p, bool ranked16, uint32_t rtq, unsigned long long *stat_slot, ExactPass &&exact_pass) {
+    int rc;
+    if (ranked16) {
+        rc = fs_dispatch_f32(c.v.metric, [&](auto M) -> int {
+            constexpr int m = decltype(M)::value;
+            int r = fs_launch_merge(c, flat_merge_kernel<m, KDB_PREC_F32, FM_BAND16>, p, c.d_q);
+            if (r) return r;
+            FsParams p2;
+            const void *qx = nullptr;
+            r = exact_pass(M, p2, qx);
+            if (r) return r;
+            return fs_round_merge_and_rescue<m, KDB_PREC_F32>(c, p2, qx, rtq);
+        });
         if (rc) return rc;
-        unsigned char *base = reinterpret_cast<unsigned char *>(idx->d_scratch);
-        uint32_t *d_ids = reinterpret_cast<uint32_t *>(base);
-        uint32_t *d_nscan = reinterpret_cast<uint32_t *>(base + ids_b);
-        unsigned long long *d_keys = reinterpret_cast<unsigned long long *>(base + ids_b + 256);
-        if (ids_needed) {
-            KDB_HIP(hipMemsetAsync(d_nscan, 0, 8, s));
-            hipLaunchKernelGGL(compact_ids_kernel, dim3(((v.count >> 5) + 256) / 256), dim3(256), 0, s, v.deleted, d_allow, d_first_allowed, v.count, d_ids,
-                               d_nscan);
-            KDB_HIP(hipGetLastError());
-        }
-        unsigned long long *slot = kdb_stats_begin(idx, 2, B, 0);
-        KDB_HIP(hipMemsetAsync(slot, 0, 32, s));
-        KDB_HIP(hipEventRecord(idx->ev0, s));
-        rc = kdb_launch_flat_anyk(idx, v, d_q, d_qnorm, B, k, ids_needed ? d_ids : nullptr, ids_needed ? d_nscan : nullptr, d_keys, chunk_q, d_out_ids, d_out_dist,
-                                  d_out_count, (queries_normalised & 2) ? 1 : 0, slot, s);
+        // statistics: how many queries the exact pass settled (kdb_counters.n_hops of a flat-scan launch)
+        KDB_HIP(hipMemcpyAsync(stat_slot + 1, p.fb_count, 4, hipMemcpyDeviceToDevice, c.s));
+    } else {
+        rc = fs_dispatch(c.v.precision, c.v.metric, [&](auto M, auto P) -> int {
+            constexpr int m = decltype(M)::value, pr = decltype(P)::value;
+            if constexpr (pr == KDB_PREC_I8) return fs_launch_merge(c, flat_merge_kernel<m, pr, FM_KL>, p, c.d_q);
+            else return fs_round_merge_and_rescue<m, pr>(c, p, c.d_q, rtq);
+        });
         if (rc) return rc;
-        KDB_HIP(hipEventRecord(idx->ev1, s));
-        return KDB_OK;
     }
-    const bool dist64 = (queries_normalised & 2) != 0; // int8: d_out_dist is a double array (KDB_SEARCH_DIST_F64)
-    const int qn_arg = queries_normalised;
-    queries_normalised &= 1;
-    // One launch = one round of 512 workgroups = (stripes) x (query tiles): with more than 64 query tiles the stripes
-    // get so long, and so many workgroups stream the same stripe out of step, that the rows fall out of L2 (32768
-    // queries in one launch: 3x slower per query, 150x the HBM traffic).  Larger batches run as 8192-query launches.
-    constexpr uint32_t FS_MAX_B = 8192;
-    if (B > FS_MAX_B) {
-        const size_t qbytes = v.precision == KDB_PREC_I8 ? (size_t)v.ld : (size_t)v.ld * 4; // one prepared query
-        for (uint32_t b0 = 0; b0 < B; b0 += FS_MAX_B) {
-            const uint32_t nb = B - b0 < FS_MAX_B ? B - b0 : FS_MAX_B;
-            int rc = kdb_launch_flat_scan(idx, v, reinterpret_cast<const unsigned char *>(d_q) + (size_t)b0 * qbytes,
-                                          d_qnorm ? d_qnorm + b0 : nullptr, nb, k, d_allow, d_first_allowed, d_out_ids + (size_t)b0 * k,
-                                          d_out_dist + (size_t)b0 * k * (dist64 ? 2u : 1u), d_out_count + b0, qn_arg, s);
-            if (rc) return rc;
-        }
-        return KDB_OK;
+    // statistics: queries answered by the rescue pass (high word of kdb_counters.n_hops of a flat-scan launch)
+    if (c.v.precision != KDB_PREC_I8)
+        KDB_HIP(hipMemcpyAsync(reinterpret_cast<uint32_t *>(stat_slot + 1) + 1, p.rs_count, 4, hipMemcpyDeviceToDevice, c.s));
+    return KDB_OK;
+}
+
+// ---- one allow list (or none) for the whole batch
+
+// k > 128, beyond the tile kernels' lists: every distance in the final order + a radix select per query (flat_anyk.hip)
+static int flat_scan_anyk(kdb_index *idx, const KdbView &v, const void *d_q, const float *d_qnorm, uint32_t B, uint32_t k,
+                          const uint32_t *d_allow, const uint32_t *d_first_allowed, uint32_t *d_out_ids, float *d_out_dist,
+                          uint32_t *d_out_count, int queries_normalised, hipStream_t s) {
+    const size_t ids_b = (size_t)v.count * 4;
+    const bool ids_needed = d_allow != nullptr || idx->n_deleted > 0;
+    const size_t stride = ((size_t)v.count + 63) & ~(size_t)63;
+    uint32_t chunk_q = (uint32_t)(((size_t)2 << 30) / (stride * 8)); // <= 2 GB of keys at a time
+    if (chunk_q < 1) chunk_q = 1;
+    if (chunk_q > B) chunk_q = B;
+    if (chunk_q > 65535u) chunk_q = 65535u;
+    int rc = kdb_ensure_scratch(idx, (ids_b + 255) / 256 * 256 + 256 + (size_t)chunk_q * stride * 8 + 256);
+    if (rc) return rc;
+    FsBump scratch{reinterpret_cast<unsigned char *>(idx->d_scratch)};
+    uint32_t *d_ids = scratch.take<uint32_t>(ids_b);
+    uint32_t *d_nscan = scratch.take<uint32_t>(256);
+    unsigned long long *d_keys = scratch.take<unsigned long long>((size_t)chunk_q * stride * 8);
+    if (ids_needed) {
+        KDB_HIP(hipMemsetAsync(d_nscan, 0, 8, s));
+        hipLaunchKernelGGL(compact_ids_kernel, dim3(((v.count >> 5) + 256) / 256), dim3(256), 0, s, v.deleted, d_allow, d_first_allowed, v.count, d_ids,
+                           d_nscan);
+        KDB_HIP(hipGetLastError());
     }
-    const uint32_t n_qtiles = (B + FS_TQ - 1) / FS_TQ;
-    // per-stripe list length: a stripe keeps its k+16 best by the ranking key; the merge kernel checks that no full
-    // list reaches into the error band of the k-th key (else the query goes to the exact / rescue pass)
-    const uint32_t kl = k + 16 > 144 ? 144 : k + 16;
+    unsigned long long *slot = kdb_stats_begin(idx, 2, B, 0);
+    KDB_HIP(hipMemsetAsync(slot, 0, 32, s));
+    KDB_HIP(hipEventRecord(idx->ev0, s));
+    rc = kdb_launch_flat_anyk(idx, v, d_q, d_qnorm, B, k, ids_needed ? d_ids : nullptr, ids_needed ? d_nscan : nullptr, d_keys, chunk_q, d_out_ids, d_out_dist,
+                              d_out_count, (queries_normalised & 2) ? 1 : 0, slot, s);
+    if (rc) return rc;
+    KDB_HIP(hipEventRecord(idx->ev1, s));
+    return KDB_OK;
+}
+
+// Geometry of one scan of <= FS_MAX_B queries with k <= 128: which kernels, how many stripes, how much scratch.
+struct FsPlan {
+    uint32_t kl, n_qtiles, n_q16;
+    size_t lds_s;         // the small kernel's LDS with the queries in the index's own precision
+    KdbView vr;           // the view of the ranking copy (fs_rank_view)
+    bool copy_padded;     // ... which has another row stride than v
+    bool need_ids;        // scan list: the compacted ids of the rows that are live and allowed (else identity)
+    bool rank16, small, big, few_tier;
+    uint32_t want, min_tiles, cap;                   // small / 128 x 128 tile kernel
+    uint32_t want_big, cap_big;                      // big-tile kernel ...
+    uint32_t fb_nqt, fb_nqg, fb_nqx, fb_spx;         // ... its blockIdx -> (query tile, stripe) map (FsParams)
+    uint32_t fb_slack, fb_period;
+    uint32_t fb_seeded, fb_seed_nstr;                // a seed launch goes first; the stripe count that decision assumed
+    uint32_t want_few;                               // first tier of the exact pass
+    size_t n_part, n_part_big, n_part_few, n_qpad;   // (stripe, query) lists; query rows the ranking kernels may touch
+    size_t ids_bytes, fbq_bytes, fbl_bytes, rsl_bytes, part_bytes, qp_bytes;
+};
+
+static FsPlan fs_plan(const kdb_index *idx, const KdbView &v, uint32_t B, uint32_t k, bool need_ids, bool queries_normalised) {
+    FsPlan g{};
+    g.n_qtiles = (B + FS_TQ - 1) / FS_TQ;
+    g.kl = fs_kl(k);
     // small batches take the HBM-bound streaming kernel (16 queries per workgroup, whole queries in LDS)
-    const uint32_t n_q16 = (B + FSS_TQ - 1) / FSS_TQ;
-    const uint32_t cap_s = kl + FS_TR + FSS_SLACK;
-    const size_t lds_s = (v.precision == KDB_PREC_I8 ? fss_q_bytes<KDB_PREC_I8>(v.ld) : v.precision == KDB_PREC_F16 ? fss_q_bytes<KDB_PREC_F16>(v.ld) : fss_q_bytes<KDB_PREC_F32>(v.ld)) +
-                         (size_t)FSS_TQ * cap_s * 8 + FSS_TAIL;
+    g.n_q16 = (B + FSS_TQ - 1) / FSS_TQ;
+    g.lds_s = fs_small_lds(v, g.kl);
     // which kernel (measured at 1M x 768, scripts/flat_probe.py): the streaming kernel re-reads the rows once per 16 queries
     // and wins up to 32 queries (0.47 ms at 32); the big-tile kernel (flat_scan_big.cuh: 256 queries x 256 rows per
     // workgroup; rows must be whole 128-byte slabs -- any number: 64-d halfs are ONE slab, 8192 queries 11.4 -> 2.9 ms against the
@@ -1868,118 +2031,144 @@ int kdb_launch_flat_scan(kdb_index *idx, const KdbView &v, const void *d_q, cons
     // half-precision ranking copy of float32 rows) wins from 65 queries on (128 queries 0.92 vs 1.20 ms for the 128 x 128
     // tile kernel, 256 queries 1.10 vs 1.81 ms; k=100: 1.30 vs 3.66 ms) and between 33 and 64 queries when the lists are
     // short (k=10, 48 queries: 0.69 vs 1.04 ms; k=100, 64 queries: 1.12 vs 0.94 ms)
-    // float32 indexes: the ranking copy has its own row stride (idx->ld16: whole 128-byte slabs, zero pad).  The kernels that
-    // read it take a view with that stride (vr) and queries re-laid with it (q_rank); everything exact keeps v and d_q.
-    const bool copy_padded = v.precision == KDB_PREC_F32 && idx->d_rows16 != nullptr && idx->ld16 != v.ld;
-    KdbView vr = v;
-    if (copy_padded) vr.ld = idx->ld16;
-    const uint32_t rowb = v.precision == KDB_PREC_I8 ? v.ld : vr.ld * 2u;
-    const bool rank16_ok = v.precision == KDB_PREC_F32 && (v.metric == KDB_METRIC_L2 || queries_normalised) && idx->max_norm2 > 0.f &&
-                           idx->max_norm2 <= 1.0e4f && !getenv("KDB_FLAT_EXACT_ONLY");
-    const bool big_ok = B >= (uint32_t)kdb_flat_big_min() && rowb % (uint32_t)FB_SLAB == 0u &&
+    g.vr = fs_rank_view(idx, v);
+    g.copy_padded = g.vr.ld != v.ld;
+    const uint32_t rowb = v.precision == KDB_PREC_I8 ? v.ld : g.vr.ld * 2u;
+    const bool rank16_ok = fs_rank16_ok(idx, v, queries_normalised);
+    const bool big_ok = B >= FS_BIG_MIN && rowb % (uint32_t)FB_SLAB == 0u &&
                         (v.precision == KDB_PREC_I8 || v.precision == KDB_PREC_F16 || (rank16_ok && idx->d_rows16 != nullptr));
-    const bool small = B <= (uint32_t)kdb_flat_small_max() && lds_s <= 150u * 1024u && !(big_ok && B > 32u && kl <= 48u);
-    // float32 cosine, large batches: rank on the f16 MFMA inside a rigorous error band, settle the rest exactly
-    // (only when the library normalised the queries itself and the rows are far from the f16 range limit)
+    g.small = B <= FS_SMALL_MAX && g.lds_s <= FS_LDS_MAX && !(big_ok && B > 32u && g.kl <= 48u);
+    // float32, large batches: rank on the f16 MFMA inside a rigorous error band, settle the rest exactly
     // (small batches rank on the half-precision copy of the rows, when the index keeps one: half the HBM bytes)
-    const bool rank16 = (!small || idx->d_rows16) && rank16_ok;
+    g.rank16 = (!g.small || idx->d_rows16) && rank16_ok;
+    g.big = !g.small && big_ok;
 
-    // ---- scan list: identity, or the compacted ids of the rows that are live and allowed.  Nothing on this path
-    //      waits for the device: the number of rows to scan stays in HBM and every kernel derives the stripe
-    //      geometry from it (fs_resolve).
-    // scratch layout: [scan_ids: count u32][n_scan word (256 B)][partials]
-    const size_t ids_bytes = ((size_t)v.count * 4 + 255) / 256 * 256;
-    const bool need_ids = d_allow != nullptr || idx->n_deleted > 0;
-    uint32_t stripes_max = FS_MAX_MERGE / kl;
+    g.ids_bytes = ((size_t)v.count * 4 + 255) / 256 * 256;
+    g.need_ids = need_ids;
+    uint32_t stripes_max = FS_MAX_MERGE / g.kl;
     if (stripes_max < 1) stripes_max = 1;
     // stripes: ONE round of resident workgroups (two fit a CU: 512 in all).  Every stripe pays a start-up phase
     // (threshold still open, everything is a survivor), so more, shorter stripes only cost: measured at 1M x 768,
     // 512 workgroups beat 1024 and 2048 for every batch from 1 to 8192 queries.
-    uint32_t want = 512 / (small ? n_q16 : n_qtiles);
-    if (want < 1) want = 1;
-    if (want > stripes_max) want = stripes_max;
-    const uint32_t min_tiles = small ? 4u : 8u;
+    g.want = 512 / (g.small ? g.n_q16 : g.n_qtiles);
+    if (g.want < 1) g.want = 1;
+    if (g.want > stripes_max) g.want = stripes_max;
+    g.min_tiles = g.small ? 4u : 8u;
     {   // never more stripes than the index could fill
         const uint32_t max_tiles = (v.count + FS_TR - 1) / FS_TR;
-        const uint32_t lim = (max_tiles + min_tiles - 1) / min_tiles;
-        if (want > lim) want = lim;
-        if (want < 1) want = 1;
+        const uint32_t lim = (max_tiles + g.min_tiles - 1) / g.min_tiles;
+        if (g.want > lim) g.want = lim;
+        if (g.want < 1) g.want = 1;
     }
-    const size_t n_part = (size_t)want * n_qtiles * FS_TQ;
+    g.n_part = (size_t)g.want * g.n_qtiles * FS_TQ;
     // buffered mode: kl entries + room for max(kl, 64) appends between two compactions (<= 320 in all)
-    const uint32_t cap = (small || kl <= (uint32_t)FS_LDS_KL) ? kl : kl + (kl > 64u ? kl : 64u);
-    const bool big = !small && big_ok;
-    uint32_t fb_nqt = 0, fb_nqg = 1, fb_nqx = 1, fb_spx = 1, want_big = 1;
-    if (big) {
-        fb_nqt = (B + FB_T - 1) / FB_T;                 // <= 32 (batches above 8192 queries are split)
-        uint32_t per_xcd = 8u;
-        if (const char *e = KDB_AB_ENV("KDB_FB_NQX")) per_xcd = (uint32_t)atoi(e) >= 1 ? (uint32_t)atoi(e) : 8u;
-        while (fb_nqg * per_xcd < fb_nqt && fb_nqg < 8u) fb_nqg *= 2u; // groups of <= 8 query tiles; 1, 2 or 4 groups
-        fb_nqx = (fb_nqt + fb_nqg - 1u) / fb_nqg;       // query tiles an XCD serves
-        fb_spx = 32u / fb_nqx;                          // stripes an XCD walks (32 CUs, one workgroup each)
-        want_big = (8u / fb_nqg) * fb_spx;
-        if (want_big > stripes_max) want_big = stripes_max;
+    g.cap = (g.small || g.kl <= (uint32_t)FS_LDS_KL) ? g.kl : g.kl + (g.kl > 64u ? g.kl : 64u);
+    g.fb_nqg = g.fb_nqx = g.fb_spx = g.want_big = 1;
+    if (g.big) {
+        g.fb_nqt = (B + FB_T - 1) / FB_T;                 // <= 32 (batches above 8192 queries are split)
+        const uint32_t per_xcd = 8u;
+        while (g.fb_nqg * per_xcd < g.fb_nqt && g.fb_nqg < 8u) g.fb_nqg *= 2u; // groups of <= 8 query tiles; 1, 2 or 4 groups
+        g.fb_nqx = (g.fb_nqt + g.fb_nqg - 1u) / g.fb_nqg; // query tiles an XCD serves
+        g.fb_spx = 32u / g.fb_nqx;                        // stripes an XCD walks (32 CUs, one workgroup each)
+        g.want_big = (8u / g.fb_nqg) * g.fb_spx;
+        if (g.want_big > stripes_max) g.want_big = stripes_max;
         const uint32_t max_tiles = (v.count + FB_T - 1) / FB_T;
         const uint32_t lim = (max_tiles + 3u) / 4u;
-        if (want_big > lim) want_big = lim;
-        if (want_big < 1) want_big = 1;
+        if (g.want_big > lim) g.want_big = lim;
+        if (g.want_big < 1) g.want_big = 1;
     }
-    uint32_t fb_slack = 64u, fb_period = 4u; // measured at 8192 queries over 1M x 768: period 1 / 2 / 4 = 14.8 / 14.0 / 13.9 ms
-    if (const char *e = KDB_AB_ENV("KDB_FB_SLACK")) fb_slack = (uint32_t)atoi(e);
-    if (const char *e = KDB_AB_ENV("KDB_FB_PERIOD")) fb_period = (uint32_t)atoi(e) >= 1 ? (uint32_t)atoi(e) : 1u;
-    while (fb_period > 1u && fb_cap(kl, fb_slack, fb_period) > 64u * (uint32_t)FB_CSLOTS) fb_period--;
-    if (fb_cap(kl, fb_slack, fb_period) > 64u * (uint32_t)FB_CSLOTS) fb_slack = 64u * (uint32_t)FB_CSLOTS - kl - fb_period * (uint32_t)FB_T;
-    const uint32_t cap_big = fb_cap(kl, fb_slack, fb_period);
-    const size_t n_part_big = big ? (size_t)want_big * fb_nqt * FB_T : 0;
-    size_t part_bytes = n_part * cap * 8 + n_part * 4 + 1024;
+    g.fb_slack = 64u;
+    g.fb_period = 4u; // measured at 8192 queries over 1M x 768: period 1 / 2 / 4 = 14.8 / 14.0 / 13.9 ms
+    while (g.fb_period > 1u && fb_cap(g.kl, g.fb_slack, g.fb_period) > 64u * (uint32_t)FB_CSLOTS) g.fb_period--;
+    if (fb_cap(g.kl, g.fb_slack, g.fb_period) > 64u * (uint32_t)FB_CSLOTS) g.fb_slack = 64u * (uint32_t)FB_CSLOTS - g.kl - g.fb_period * (uint32_t)FB_T;
+    g.cap_big = fb_cap(g.kl, g.fb_slack, g.fb_period);
+    g.n_part_big = g.big ? (size_t)g.want_big * g.fb_nqt * FB_T : 0;
+    // Seed launch: only when the stripe geometry is known here (no filter, no deleted rows: the row count never leaves the
+    // device otherwise), every stripe holds a whole first tile, and a stripe's share of the kl best is at most the 16 rows
+    // a tile's block maxima vouch for.  Same integer arithmetic as fs_resolve_n.
+    if (g.big && !need_ids) {
+        const uint32_t n_tiles = (v.count + FB_T - 1) / FB_T;
+        uint32_t ns = g.want_big;
+        const uint32_t lim4 = (n_tiles + 3u) / 4u;
+        if (ns > lim4) ns = lim4;
+        if (ns < 1u) ns = 1u;
+        const uint32_t tiles_per = (n_tiles + ns - 1u) / ns;
+        const uint32_t n_str = (n_tiles + tiles_per - 1u) / tiles_per;
+        const uint64_t last_rows = (uint64_t)v.count - (uint64_t)(n_str - 1u) * tiles_per * FB_T;
+        const uint32_t share = (g.kl + n_str - 1u) / n_str;
+        // (a stripe of fewer than 32 tiles pays more for the extra tile than the open thresholds cost it: 128 queries over
+        //  1M x 768 = 256 stripes of 15 tiles 0.92 vs 0.89 ms; 8192 queries = 8 stripes of 488 tiles 11.80 vs 11.94 ms)
+        uint32_t seed_min_tiles = 32u;
+        if (const char *e = getenv("KDB_FB_SEED_MIN_TILES")) seed_min_tiles = (uint32_t)atoi(e); // (tests: the seed path on small cases)
+        if (n_str >= 2u && last_rows >= (uint64_t)FB_T && share <= 16u && tiles_per >= seed_min_tiles) g.fb_seeded = 1u;
+        g.fb_seed_nstr = n_str;
+    }
+
+    g.part_bytes = g.n_part * g.cap * 8 + g.n_part * 4 + 1024;
     // big-tile kernel: lists + counts + the thresholds the stripes publish / end with (two floats per (stripe, query))
-    if (big && n_part_big * cap_big * 8 + n_part_big * 12 + 1024 > part_bytes) part_bytes = n_part_big * cap_big * 8 + n_part_big * 12 + 1024;
-    size_t fbq_bytes = rank16 ? (((size_t)n_qtiles * FS_TQ * v.ld * 4 + 255) & ~(size_t)255) : 0; // vectors of the unsettled queries
-    if (big && v.precision == KDB_PREC_F16) fbq_bytes = ((size_t)fb_nqt * FB_T * v.ld * 2 + 255) & ~(size_t)255; // the queries as halfs
-    if (rank16 && copy_padded) { // ... the ranking scan's query halfs live there first, with the copy's stride
-        const size_t h = (((size_t)(big ? fb_nqt * FB_T : n_qtiles * FS_TQ) * vr.ld * 2 + 255) & ~(size_t)255);
-        if (h > fbq_bytes) fbq_bytes = h;
+    if (g.big && g.n_part_big * g.cap_big * 8 + g.n_part_big * 12 + 1024 > g.part_bytes) g.part_bytes = g.n_part_big * g.cap_big * 8 + g.n_part_big * 12 + 1024;
+    g.fbq_bytes = g.rank16 ? (((size_t)g.n_qtiles * FS_TQ * v.ld * 4 + 255) & ~(size_t)255) : 0; // vectors of the unsettled queries
+    if (g.big && v.precision == KDB_PREC_F16) g.fbq_bytes = ((size_t)g.fb_nqt * FB_T * v.ld * 2 + 255) & ~(size_t)255; // the queries as halfs
+    g.n_qpad = (size_t)(g.big ? g.fb_nqt * FB_T : g.n_qtiles * FS_TQ); // query rows the ranking kernels may touch (d_q holds >= as many)
+    if (g.rank16 && g.copy_padded) { // ... the ranking scan's query halfs live there first, with the copy's stride
+        const size_t h = ((g.n_qpad * g.vr.ld * 2 + 255) & ~(size_t)255);
+        if (h > g.fbq_bytes) g.fbq_bytes = h;
     }
-    const size_t n_qpad = (size_t)(big ? fb_nqt * FB_T : n_qtiles * FS_TQ); // query rows the ranking kernels may touch (d_q holds >= as many)
-    const size_t qp_bytes = (rank16 && copy_padded) ? ((n_qpad * vr.ld * 4 + 255) & ~(size_t)255) : 0;
-    // exact pass, first tier: up to FS_FEW unsettled queries go through the streaming kernel (16 queries per workgroup, the
-    // rows read at HBM speed by every CU) -- the tile kernel gives ONE query tile a handful of stripes: a single unsettled
-    // query of an 8192-query batch cost 78 ms behind a 12 ms ranking scan (seen once in five calls on the clustered corpus)
-    constexpr uint32_t FS_FEW = 64;
-    const bool few_tier = rank16 && !small && lds_s <= 150u * 1024u;
-    uint32_t want_few = 512u / (FS_FEW / (uint32_t)FSS_TQ);
-    if (want_few > stripes_max) want_few = stripes_max;
+    g.qp_bytes = (g.rank16 && g.copy_padded) ? ((g.n_qpad * g.vr.ld * 4 + 255) & ~(size_t)255) : 0;
+    g.few_tier = g.rank16 && !g.small && g.lds_s <= FS_LDS_MAX;
+    g.want_few = 512u / (FS_FEW / (uint32_t)FSS_TQ);
+    if (g.want_few > stripes_max) g.want_few = stripes_max;
     {
         const uint32_t max_tiles = (v.count + FS_TR - 1) / FS_TR;
         const uint32_t lim = (max_tiles + 3u) / 4u;
-        if (want_few > lim) want_few = lim;
-        if (want_few < 1u) want_few = 1u;
+        if (g.want_few > lim) g.want_few = lim;
+        if (g.want_few < 1u) g.want_few = 1u;
     }
-    const size_t n_part_few = (size_t)want_few * FS_TQ; // one 128-query block of lists per stripe
-    if (few_tier && n_part_few * kl * 8 + n_part_few * 4 + 1024 > part_bytes) part_bytes = n_part_few * kl * 8 + n_part_few * 4 + 1024;
-    const size_t fbl_bytes = rank16 ? (((size_t)n_qtiles * FS_TQ * 4 + 255) & ~(size_t)255) : 0;        // their indices
-    const size_t rsl_bytes = ((size_t)n_qtiles * FS_TQ * 4 + 255) & ~(size_t)255; // queries handed to the rescue pass
-    int rc = kdb_ensure_scratch(idx, ids_bytes + 256 + fbq_bytes + fbl_bytes + rsl_bytes + part_bytes + qp_bytes + 4096);
+    g.n_part_few = (size_t)g.want_few * FS_TQ; // one 128-query block of lists per stripe
+    if (g.few_tier && g.n_part_few * g.kl * 8 + g.n_part_few * 4 + 1024 > g.part_bytes) g.part_bytes = g.n_part_few * g.kl * 8 + g.n_part_few * 4 + 1024;
+    g.fbl_bytes = g.rank16 ? (((size_t)g.n_qtiles * FS_TQ * 4 + 255) & ~(size_t)255) : 0; // their indices
+    g.rsl_bytes = ((size_t)g.n_qtiles * FS_TQ * 4 + 255) & ~(size_t)255;                  // queries handed to the rescue pass
+    return g;
+}
+
+// per-stripe lists in `part`: keys, ids, counts of n_part (stripe, query) pairs with cap entries each
+static void fs_set_lists(FsParams &p, unsigned char *part, size_t n_part, uint32_t cap) {
+    p.cap = cap;
+    p.part_key = reinterpret_cast<float *>(part);
+    p.part_id = reinterpret_cast<uint32_t *>(part + n_part * cap * 4);
+    p.part_cnt = reinterpret_cast<uint32_t *>(part + n_part * cap * 8);
+}
+
+static int flat_scan_one(kdb_index *idx, const KdbView &v, const void *d_q, const float *d_qnorm, uint32_t B, uint32_t k,
+                         const uint32_t *d_allow, const uint32_t *d_first_allowed, uint32_t *d_out_ids, float *d_out_dist,
+                         uint32_t *d_out_count, int queries_normalised, hipStream_t s) {
+    const bool dist64 = (queries_normalised & 2) != 0; // int8: d_out_dist is a double array (KDB_SEARCH_DIST_F64)
+    const FsPlan g = fs_plan(idx, v, B, k, d_allow != nullptr || idx->n_deleted > 0, (queries_normalised & 1) != 0);
+    const FsCall c{idx, v, d_q, d_qnorm, B, k, g.kl, d_out_ids, d_out_dist, d_out_count, s};
+
+    // ---- scan list: identity, or the compacted ids of the rows that are live and allowed.  Nothing on this path
+    //      waits for the device: the number of rows to scan stays in HBM and every kernel derives the stripe
+    //      geometry from it (fs_resolve).
+    // scratch layout: [scan_ids: count u32][n_scan word (256 B)][unsettled queries][their list][rescue list][partials][padded queries]
+    int rc = kdb_ensure_scratch(idx, g.ids_bytes + 256 + g.fbq_bytes + g.fbl_bytes + g.rsl_bytes + g.part_bytes + g.qp_bytes + 4096);
     if (rc) return rc;
-    unsigned char *base = reinterpret_cast<unsigned char *>(idx->d_scratch);
-    uint32_t *d_ids = reinterpret_cast<uint32_t *>(base);
-    uint32_t *d_nscan = reinterpret_cast<uint32_t *>(base + ids_bytes);
-    float *d_fbq = reinterpret_cast<float *>(base + ids_bytes + 256);
-    uint32_t *d_fblist = reinterpret_cast<uint32_t *>(base + ids_bytes + 256 + fbq_bytes);
+    FsBump scratch{reinterpret_cast<unsigned char *>(idx->d_scratch)};
+    uint32_t *d_ids = scratch.take<uint32_t>(g.ids_bytes);
+    uint32_t *d_nscan = scratch.take<uint32_t>(256);
     uint32_t *d_fbcount = d_nscan + 4; // inside the 256-byte header
     uint32_t *d_rscount = d_nscan + 8;
-    uint32_t *d_rslist = reinterpret_cast<uint32_t *>(base + ids_bytes + 256 + fbq_bytes + fbl_bytes);
-    unsigned char *part = base + ids_bytes + 256 + fbq_bytes + fbl_bytes + rsl_bytes;
+    float *d_fbq = scratch.take<float>(g.fbq_bytes);
+    uint32_t *d_fblist = scratch.take<uint32_t>(g.fbl_bytes);
+    uint32_t *d_rslist = scratch.take<uint32_t>(g.rsl_bytes);
+    unsigned char *part = scratch.take<unsigned char>(g.part_bytes);
     const void *q_rank = d_q; // what the ranking kernels read as queries
-    if (qp_bytes) {
-        float *d_qp = reinterpret_cast<float *>(part + part_bytes);
-        const size_t quads = n_qpad * (vr.ld >> 2);
-        hipLaunchKernelGGL(pad_queries_kernel, dim3((unsigned)((quads + 255) / 256)), dim3(256), 0, s, reinterpret_cast<const float *>(d_q), v.ld, d_qp,
-                           vr.ld, quads);
-        KDB_HIP(hipGetLastError());
+    if (g.qp_bytes) {
+        float *d_qp = scratch.take<float>(g.qp_bytes);
+        rc = fs_pad_queries(v, g.vr, d_q, g.n_qpad, d_qp, s);
+        if (rc) return rc;
         q_rank = d_qp;
     }
-    if (need_ids) {
+    if (g.need_ids) {
         KDB_HIP(hipMemsetAsync(d_nscan, 0, 8, s));
         hipLaunchKernelGGL(compact_ids_kernel, dim3(((v.count >> 5) + 256) / 256), dim3(256), 0, s, v.deleted, d_allow, d_first_allowed,
                            v.count, d_ids, d_nscan);
@@ -1987,33 +2176,24 @@ int kdb_launch_flat_scan(kdb_index *idx, const KdbView &v, const void *d_q, cons
     }
 
     FsParams p{};
-    p.scan_ids = need_ids ? d_ids : nullptr;
+    p.scan_ids = g.need_ids ? d_ids : nullptr;
     p.n_scan = v.count;
-    p.n_scan_dev = need_ids ? d_nscan : nullptr;
-    p.want = want;
-    p.min_tiles = min_tiles;
-    p.n_qtiles = n_qtiles;
+    p.n_scan_dev = g.need_ids ? d_nscan : nullptr;
+    p.want = g.want;
+    p.min_tiles = g.min_tiles;
+    p.n_qtiles = g.n_qtiles;
     p.B = B;
-    p.kl = kl;
-    p.cap = cap;
-    p.part_key = reinterpret_cast<float *>(part);
-    p.part_id = reinterpret_cast<uint32_t *>(part + n_part * cap * 4);
-    p.part_cnt = reinterpret_cast<uint32_t *>(part + n_part * cap * 8);
-    p.lists_query_major = small ? 1u : 0u;
+    p.kl = g.kl;
+    fs_set_lists(p, part, g.n_part, g.cap);
+    p.lists_query_major = g.small ? 1u : 0u;
     p.rs_count = d_rscount;
     p.rs_list = d_rslist;
     p.rmax = idx->max_norm2 > 0.f ? sqrtf(idx->max_norm2) : 1.0f;
     if (v.precision != KDB_PREC_I8) KDB_HIP(hipMemsetAsync(d_rscount, 0, 4, s));
-    const uint32_t n_stripes = want; // upper bound: workgroups of stripes past the resolved count return at once
-
-    const size_t lds = (size_t)(FS_TR + FS_TQ) * FS_LDS_STRIDE * 4 + FS_TQ * 12 + (size_t)FS_TQ * FS_QPER * 8 +
-                       (size_t)FS_TQ * FS_LDS_KL * 8 + (size_t)FS_TQ * 8 + 32;
-    const uint32_t stripes8 = (n_stripes + 7) / 8 * 8;
-    const uint32_t grid = stripes8 * n_qtiles;
-    if (rank16 && small) p.rows16 = idx->d_rows16;
-    if ((rank16 && !small) || (big && v.precision == KDB_PREC_F16)) { // the query halfs live in the buffer the exact pass fills later (it is idle during the ranking scan)
-        const bool rk = rank16 && copy_padded; // (float16 indexes: their own rows, their own stride)
-        const size_t nq_elems = (big ? (size_t)fb_nqt * FB_T : (size_t)n_qtiles * FS_TQ) * (rk ? vr.ld : v.ld);
+    if (g.rank16 && g.small) p.rows16 = idx->d_rows16;
+    if ((g.rank16 && !g.small) || (g.big && v.precision == KDB_PREC_F16)) { // the query halfs live in the buffer the exact pass fills later (it is idle during the ranking scan)
+        const bool rk = g.rank16 && g.copy_padded; // (float16 indexes: their own rows, their own stride)
+        const size_t nq_elems = g.n_qpad * (rk ? g.vr.ld : v.ld);
         hipLaunchKernelGGL(queries_to_f16_kernel, dim3((unsigned)((nq_elems / 4 + 255) / 256)), dim3(256), 0, s,
                            reinterpret_cast<const float *>(rk ? q_rank : d_q), nq_elems, reinterpret_cast<uint16_t *>(d_fbq));
         KDB_HIP(hipGetLastError());
@@ -2025,276 +2205,135 @@ int kdb_launch_flat_scan(kdb_index *idx, const KdbView &v, const void *d_q, cons
     unsigned long long *stat_slot = p.ctr;
     KDB_HIP(hipMemsetAsync(stat_slot, 0, 32, s));
     KDB_HIP(hipEventRecord(idx->ev0, s));
-    auto launch_scan_on = [&](auto kern, const KdbView &vv, const void *qv) -> int {
-        KDB_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, s, vv, reinterpret_cast<const float *>(qv), p);
-        return KDB_OK;
-    };
-    auto launch_scan = [&](auto kern) -> int { return launch_scan_on(kern, v, d_q); };
-    auto launch_small_view = [&](auto kern, const KdbView &vv, const FsParams &pp, const void *qv, size_t lds_k) -> int {
-        KDB_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_k));
-        hipLaunchKernelGGL(kern, dim3(stripes8 * n_q16), dim3(256), lds_k, s, vv, reinterpret_cast<const float *>(qv), pp, n_q16, cap_s);
-        return KDB_OK;
-    };
-    auto launch_small_on = [&](auto kern, const FsParams &pp, const void *qv, size_t lds_k) -> int { return launch_small_view(kern, v, pp, qv, lds_k); };
-    auto launch_small = [&](auto kern) -> int { return launch_small_on(kern, p, d_q, lds_s); };
-    FsParams p_old = p; // geometry of the 128 x 128 tile kernel (the exact pass of a big-tile ranked scan keeps it)
-    if (big) {
-        p.want = want_big;
+    const FsParams p_old = p; // geometry of the 128 x 128 tile kernel (the exact pass of a big-tile ranked scan keeps it)
+    if (g.big) {
+        p.want = g.want_big;
         p.min_tiles = 4u;
-        p.n_qtiles = fb_nqt * (uint32_t)(FB_T / FS_TQ);
-        p.cap = cap_big;
-        p.part_key = reinterpret_cast<float *>(part);
-        p.part_id = reinterpret_cast<uint32_t *>(part + n_part_big * cap_big * 4);
-        p.part_cnt = reinterpret_cast<uint32_t *>(part + n_part_big * cap_big * 8);
-        if (!KDB_AB_ENV("KDB_FB_NOSHARE")) {
-            p.g_pub = reinterpret_cast<float *>(part + n_part_big * cap_big * 8 + n_part_big * 4);
-            p.part_thr = p.g_pub + n_part_big;
-            KDB_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(p.g_pub), 0x7f800000, n_part_big, s)); // +inf: nothing published yet
-        }
+        p.n_qtiles = g.fb_nqt * (uint32_t)(FB_T / FS_TQ);
+        fs_set_lists(p, part, g.n_part_big, g.cap_big);
+        p.g_pub = reinterpret_cast<float *>(part + g.n_part_big * g.cap_big * 8 + g.n_part_big * 4);
+        p.part_thr = p.g_pub + g.n_part_big;
+        KDB_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(p.g_pub), 0x7f800000, g.n_part_big, s)); // +inf: nothing published yet
         p.lists_query_major = 1u;
         p.tile_rows = FB_T;
-        p.fb_nqt = fb_nqt;
-        p.fb_nqg = fb_nqg;
-        p.fb_nqx = fb_nqx;
-        p.fb_spx = fb_spx;
-        p.fb_slack = fb_slack;
-        p.fb_alt = KDB_AB_ENV("KDB_FB_NOALT") ? 0u : 1u;
-        { const char *e = KDB_AB_ENV("KDB_FB_PREFETCH"); p.fb_pref = e ? (uint32_t)atoi(e) : 0u; }
-        p.fb_grow = KDB_AB_ENV("KDB_FB_NOGROW") ? 0u : 1u;
-        // Seed launch: only when the stripe geometry is known here (no filter, no deleted rows: the row count never leaves the
-        // device otherwise), every stripe holds a whole first tile, and a stripe's share of the kl best is at most the 16 rows
-        // a tile's block maxima vouch for.  Same integer arithmetic as fs_resolve_n.
-        if (p.g_pub && !need_ids && !KDB_AB_ENV("KDB_FB_NOSEED")) {
-            const uint32_t n_tiles = (v.count + FB_T - 1) / FB_T;
-            uint32_t ns = want_big;
-            const uint32_t lim4 = (n_tiles + 3u) / 4u;
-            if (ns > lim4) ns = lim4;
-            if (ns < 1u) ns = 1u;
-            const uint32_t tiles_per = (n_tiles + ns - 1u) / ns;
-            const uint32_t n_str = (n_tiles + tiles_per - 1u) / tiles_per;
-            const uint64_t last_rows = (uint64_t)v.count - (uint64_t)(n_str - 1u) * tiles_per * FB_T;
-            const uint32_t share = (kl + n_str - 1u) / n_str;
-            // (a stripe of fewer than 32 tiles pays more for the extra tile than the open thresholds cost it: 128 queries over
-            //  1M x 768 = 256 stripes of 15 tiles 0.92 vs 0.89 ms; 8192 queries = 8 stripes of 488 tiles 11.80 vs 11.94 ms)
-            uint32_t seed_min_tiles = 32u;
-            if (const char *e = getenv("KDB_FB_SEED_MIN_TILES")) seed_min_tiles = (uint32_t)atoi(e); // (tests: the seed path on small cases)
-            if (n_str >= 2u && last_rows >= (uint64_t)FB_T && share <= 16u && tiles_per >= seed_min_tiles) p.fb_seeded = 1u;
-            p.fb_seed_nstr = n_str;
-        }
-        p.fb_period = fb_period;
-        { const char *e = KDB_AB_ENV("KDB_FB_DBG"); p.fb_dbg = e ? (uint32_t)atoi(e) : 0u; }
+        p.fb_nqt = g.fb_nqt, p.fb_nqg = g.fb_nqg, p.fb_nqx = g.fb_nqx, p.fb_spx = g.fb_spx;
+        p.fb_slack = g.fb_slack, p.fb_period = g.fb_period;
+        // the switches of closed experiments, here and nowhere else: no shipped build can set them otherwise
+        p.fb_alt = 1u, p.fb_grow = 1u, p.fb_pref = 0u;
+        p.fb_dbg = fs_dbg_switches("KDB_FB_DBG");
+        p.fb_seeded = g.fb_seeded, p.fb_seed_nstr = g.fb_seed_nstr;
     }
-    auto launch_big_one = [&](auto kern, const void *rows_b, const void *q_b) -> int {
-        KDB_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)FB_LDS));
-        hipLaunchKernelGGL(kern, dim3(256), dim3(512), FB_LDS, s, rows_b == (const void *)idx->d_rows16 ? vr : v,
-                           reinterpret_cast<const unsigned char *>(rows_b), reinterpret_cast<const unsigned char *>(q_b), p);
-        KDB_HIP(hipGetLastError());
-        return KDB_OK;
-    };
-    // the seed launch (first tile of every stripe -> first thresholds, flat_scan_big.cuh) and the scan proper.  (A/B build, -DKDB_AB +
-    // KDB_FB_SKEW=1: the kernel whose two row halves run half a tile apart, flat_scan_skew.cuh -- measured slower, not shipped.)
-    auto launch_big = [&](auto seed_kern, auto kern, auto skew_kern, const void *rows_b, const void *q_b) -> int {
-        if (p.fb_seeded) {
-            int r1 = launch_big_one(seed_kern, rows_b, q_b);
-            if (r1) return r1;
-        }
-#ifdef KDB_AB
-        const char *skew_env = KDB_AB_ENV("KDB_FB_SKEW");
-        const KdbView &vv = rows_b == (const void *)idx->d_rows16 ? vr : v;
-        const uint32_t rowb = v.precision == KDB_PREC_I8 ? vv.ld : vv.ld * 2u;
-        if (skew_env && atoi(skew_env) != 0 && rowb / FB_SLAB >= 4u) {
-            KDB_HIP(hipFuncSetAttribute((const void *)skew_kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)FK_LDS));
-            hipLaunchKernelGGL(skew_kern, dim3(256), dim3(512), FK_LDS, s, vv, reinterpret_cast<const unsigned char *>(rows_b),
-                               reinterpret_cast<const unsigned char *>(q_b), p);
-            KDB_HIP(hipGetLastError());
-            return KDB_OK;
-        }
-#else
-        (void)skew_kern;
-#endif
-        return launch_big_one(kern, rows_b, q_b);
-    };
-#ifdef KDB_AB
-#define KDB_SKEW_K(M, P) flat_scan_skew_kernel<M, P>
-#else
-#define KDB_SKEW_K(M, P) nullptr
-#endif
-    if (big) {
-        if (v.precision == KDB_PREC_I8)
-            rc = launch_big(flat_scan_big_kernel<KDB_METRIC_COSINE, KDB_PREC_I8, true>, flat_scan_big_kernel<KDB_METRIC_COSINE, KDB_PREC_I8>,
-                            KDB_SKEW_K(KDB_METRIC_COSINE, KDB_PREC_I8), v.rows, d_q);
-        else if (v.precision == KDB_PREC_F16)
-            rc = launch_big(flat_scan_big_kernel<KDB_METRIC_L2, KDB_PREC_F16, true>, flat_scan_big_kernel<KDB_METRIC_L2, KDB_PREC_F16>,
-                            KDB_SKEW_K(KDB_METRIC_L2, KDB_PREC_F16), v.rows, d_fbq);
-        else if (v.metric == KDB_METRIC_COSINE)
-            rc = launch_big(flat_scan_big_kernel<KDB_METRIC_COSINE, FS_PREC_F32R, true>, flat_scan_big_kernel<KDB_METRIC_COSINE, FS_PREC_F32R>,
-                            KDB_SKEW_K(KDB_METRIC_COSINE, FS_PREC_F32R), idx->d_rows16, d_fbq);
-        else rc = launch_big(flat_scan_big_kernel<KDB_METRIC_L2, FS_PREC_F32R, true>, flat_scan_big_kernel<KDB_METRIC_L2, FS_PREC_F32R>,
-                             KDB_SKEW_K(KDB_METRIC_L2, FS_PREC_F32R), idx->d_rows16, d_fbq);
-#undef KDB_SKEW_K
-    } else if (small && rank16) { // queries as halfs: half the LDS, more workgroups per CU
-        const size_t lds_r = fss_q_bytes<FS_PREC_F32R>(vr.ld) + (size_t)FSS_TQ * cap_s * 8 + FSS_TAIL;
-        if (v.metric == KDB_METRIC_COSINE) rc = launch_small_view(fss_kernel_for<KDB_METRIC_COSINE, FS_PREC_F32R>(vr.ld), vr, p, q_rank, lds_r);
-        else rc = launch_small_view(fss_kernel_for<KDB_METRIC_L2, FS_PREC_F32R>(vr.ld), vr, p, q_rank, lds_r);
-    } else if (small) {
-        if (v.precision == KDB_PREC_I8) rc = launch_small(fss_kernel_for<KDB_METRIC_COSINE, KDB_PREC_I8>(v.ld));
-        else if (v.precision == KDB_PREC_F16) rc = launch_small(fss_kernel_for<KDB_METRIC_L2, KDB_PREC_F16>(v.ld));
-        else if (v.metric == KDB_METRIC_COSINE) rc = launch_small(fss_kernel_for<KDB_METRIC_COSINE, KDB_PREC_F32>(v.ld));
-        else rc = launch_small(fss_kernel_for<KDB_METRIC_L2, KDB_PREC_F32>(v.ld));
-    } else if (v.precision == KDB_PREC_I8) rc = launch_scan(flat_scan_kernel<KDB_METRIC_COSINE, KDB_PREC_I8>); // int8 is cosine only
-    else if (v.precision == KDB_PREC_F16) rc = launch_scan(flat_scan_kernel<KDB_METRIC_L2, KDB_PREC_F16>); // f16 is L2 only
-    else if (rank16 && v.metric == KDB_METRIC_COSINE) rc = launch_scan_on(flat_scan_kernel<KDB_METRIC_COSINE, FS_PREC_F32R>, p.rows16 ? vr : v, p.rows16 ? q_rank : d_q);
-    else if (rank16) rc = launch_scan_on(flat_scan_kernel<KDB_METRIC_L2, FS_PREC_F32R>, p.rows16 ? vr : v, p.rows16 ? q_rank : d_q);
-    else if (v.metric == KDB_METRIC_COSINE) rc = launch_scan(flat_scan_kernel<KDB_METRIC_COSINE, KDB_PREC_F32>);
-    else rc = launch_scan(flat_scan_kernel<KDB_METRIC_L2, KDB_PREC_F32>);
+
+    // ---- rank
+    if (g.big) {
+        // float32 rows: their half-precision copy; float16 and float32: the queries as halfs.  The seed launch (first tile of
+        // every stripe -> first thresholds, flat_scan_big.cuh), then the scan proper.
+        rc = fs_dispatch<FS_PREC_F32R>(v.precision, v.metric, [&](auto M, auto P) -> int {
+            constexpr int m = decltype(M)::value, pr = decltype(P)::value;
+            const void *rows_b = pr == FS_PREC_F32R ? (const void *)idx->d_rows16 : v.rows;
+            const void *q_b = pr == KDB_PREC_I8 ? d_q : (const void *)d_fbq;
+            auto launch_big_one = [&](auto kern) -> int {
+                KDB_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)FB_LDS));
+                hipLaunchKernelGGL(kern, dim3(256), dim3(512), FB_LDS, s, pr == FS_PREC_F32R ? g.vr : v, reinterpret_cast<const unsigned char *>(rows_b),
+                                   reinterpret_cast<const unsigned char *>(q_b), p);
+                KDB_HIP(hipGetLastError());
+                return KDB_OK;
+            };
+            if (p.fb_seeded) {
+                int r1 = launch_big_one(flat_scan_big_kernel<m, pr, true>);
+                if (r1) return r1;
+            }
+            return launch_big_one(flat_scan_big_kernel<m, pr>);
+        });
+    } else {
+        // f16-ranked: the ranking copy's view and the queries laid out for it (queries as halfs: half the LDS, more workgroups per CU)
+        const KdbView &v_rank = g.rank16 ? g.vr : v;
+        auto rank = [&](auto M, auto P) -> int {
+            constexpr int m = decltype(M)::value, pr = decltype(P)::value;
+            if (g.small) return fs_launch_small(c, fss_kernel_for<m, pr>(v_rank.ld), v_rank, q_rank, p, g.n_q16, fs_small_lds_as<pr>(v_rank.ld, g.kl));
+            return fs_launch_tile(c, flat_scan_kernel<m, pr>, v_rank, q_rank, p);
+        };
+        rc = g.rank16 ? fs_dispatch<FS_PREC_F32R>(v.precision, v.metric, rank) : fs_dispatch(v.precision, v.metric, rank);
+    }
     if (rc) return rc;
-    KDB_HIP(hipGetLastError());
     KDB_HIP(hipEventRecord(idx->ev1, s));
-    auto launch_merge = [&](auto kern, const FsParams &pp, const void *qv) -> int {
-        const uint32_t nmax = pp.want * kl; // <= FS_MAX_MERGE entries gathered per query
-        const size_t mlds = (size_t)nmax * 8 + FS_FIN * 8 + 48 + 1024 + (size_t)v.ld * 4 + (size_t)pp.want * 12 + 16;
-        KDB_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mlds));
-        hipLaunchKernelGGL(kern, dim3(B), dim3(256), mlds, s, v, reinterpret_cast<const float *>(qv), d_qnorm, pp, k, nmax, d_out_ids,
-                           d_out_dist, d_out_count);
-        return KDB_OK;
-    };
-    // exact scans isolate their finalists inside the rounding band (FM_ROUND); what that cannot settle -- a cluster of
-    // near-duplicates larger than a stripe list or than the 1024 re-score slots -- is re-scanned in the final summation
-    // order.  Both launches return at once when the list is empty (the usual case).
+
+    // ---- settle
     uint32_t rtq = FSR_TQ; // queries per rescue work item: as many as fit LDS
-    while (rtq > 1 && fsr_lds_bytes(v.ld, rtq) > 150u * 1024u) rtq--;
-    const size_t rlds = fsr_lds_bytes(v.ld, rtq);
-    auto rescue = [&](auto scan_k, auto merge_k, const FsParams &pp, const void *qv) -> int {
-        KDB_HIP(hipFuncSetAttribute((const void *)scan_k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)rlds));
-        hipLaunchKernelGGL(scan_k, dim3(512), dim3(256), rlds, s, v, reinterpret_cast<const float *>(qv), pp, rtq);
-        KDB_HIP(hipGetLastError());
-        return launch_merge(merge_k, pp, qv);
-    };
-    if (rank16) {
-        // eps bounds |q.x (wave order) - sum f16(q)f16(x) (MFMA order)| for rows and queries of norm <= 1: f16 rounding
-        // of both factors (2^-10 and its square), f32 summation in either order (dim * 2^-23); band = 2 * eps
-        // rows of norm R widen it by R (queries are normalised by the preparation step)
-        const float rmax = v.metric == KDB_METRIC_COSINE ? (idx->max_norm2 > 1.0f ? sqrtf(idx->max_norm2) : 1.0f) : sqrtf(idx->max_norm2);
-        p.band = 2.0f * (9.9e-4f + (float)v.dim * 2.4e-7f) * rmax * 1.001f; // cosine: the band; L2: per unit of ||q|| (x2 in the kernel)
+    while (rtq > 1 && fsr_lds_bytes(v.ld, rtq) > FS_LDS_MAX) rtq--;
+    if (g.rank16) {
+        p.band = fs_band(idx, v);
         p.fb_count = d_fbcount;
         p.fb_list = d_fblist;
         KDB_HIP(hipMemsetAsync(d_fbcount, 0, 4, s));
-        if (v.metric == KDB_METRIC_COSINE) rc = launch_merge(flat_merge_kernel<KDB_METRIC_COSINE, KDB_PREC_F32, FM_BAND16>, p, d_q);
-        else rc = launch_merge(flat_merge_kernel<KDB_METRIC_L2, KDB_PREC_F32, FM_BAND16>, p, d_q);
-        if (rc) return rc;
-        KDB_HIP(hipGetLastError());
-        // the exact pass over the queries the band could not settle (usually none: every launch below returns at
-        // once); their number never leaves the device
+    }
+    // the exact pass over the queries the band could not settle: gathered into d_fbq, their indices in d_fblist
+    auto exact_pass = [&](auto M, FsParams &p2, const void *&qx) -> int {
+        constexpr int m = decltype(M)::value;
         hipLaunchKernelGGL(gather_queries_kernel, dim3(B), dim3(64), 0, s, reinterpret_cast<const float *>(d_q), v.ld, d_fblist,
                            d_fbcount, d_fbq);
-        FsParams p2 = big ? p_old : p; // the exact kernels keep their own tiling and list layout
+        qx = d_fbq;
+        p2 = g.big ? p_old : p; // the exact kernels keep their own tiling and list layout
         p2.band = p.band;
         p2.b_dev = d_fbcount;
         p2.q_map = d_fblist;
         p2.ctr = nullptr;
-        p2.fb_count = nullptr;
-        p2.fb_list = nullptr;
-        p2.rows16 = nullptr;
-        p2.q16 = nullptr;
-        if (few_tier) { // first tier: *d_fbcount <= FS_FEW (both launches return at once otherwise, and when nothing is unsettled)
+        p2.fb_count = p2.fb_list = nullptr;
+        p2.rows16 = p2.q16 = nullptr;
+        if (g.few_tier) { // first tier: *d_fbcount <= FS_FEW (both launches return at once otherwise, and when nothing is unsettled)
             FsParams ps = p2;
-            ps.want = want_few;
+            ps.want = g.want_few;
             ps.min_tiles = 4u;
             ps.tile_rows = 0u;
             ps.n_qtiles = 1u;
-            ps.cap = kl;
-            ps.part_key = reinterpret_cast<float *>(part);
-            ps.part_id = reinterpret_cast<uint32_t *>(part + n_part_few * kl * 4);
-            ps.part_cnt = reinterpret_cast<uint32_t *>(part + n_part_few * kl * 8);
+            fs_set_lists(ps, part, g.n_part_few, g.kl);
             ps.lists_query_major = 1u;
             ps.g_pub = nullptr;
             ps.part_thr = nullptr;
             ps.b_le = FS_FEW;
             p2.b_gt = FS_FEW; // the tile kernel and its merge take the rest
-            auto kf = v.metric == KDB_METRIC_COSINE ? fss_kernel_for<KDB_METRIC_COSINE, KDB_PREC_F32>(v.ld) : fss_kernel_for<KDB_METRIC_L2, KDB_PREC_F32>(v.ld);
-            const uint32_t nq16_few = FS_FEW / (uint32_t)FSS_TQ;
-            KDB_HIP(hipFuncSetAttribute((const void *)kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_s));
-            hipLaunchKernelGGL(kf, dim3((want_few + 7u) / 8u * 8u * nq16_few), dim3(256), lds_s, s, v, reinterpret_cast<const float *>(d_fbq), ps, nq16_few, cap_s);
-            KDB_HIP(hipGetLastError());
-            if (v.metric == KDB_METRIC_COSINE) rc = launch_merge(flat_merge_kernel<KDB_METRIC_COSINE, KDB_PREC_F32, FM_ROUND>, ps, d_fbq);
-            else rc = launch_merge(flat_merge_kernel<KDB_METRIC_L2, KDB_PREC_F32, FM_ROUND>, ps, d_fbq);
-            if (rc) return rc;
-            KDB_HIP(hipGetLastError());
+            int r = fs_launch_small(c, fss_kernel_for<m, KDB_PREC_F32>(v.ld), v, d_fbq, ps, FS_FEW / (uint32_t)FSS_TQ, g.lds_s);
+            if (r) return r;
+            r = fs_launch_merge(c, flat_merge_kernel<m, KDB_PREC_F32, FM_ROUND>, ps, d_fbq);
+            if (r) return r;
         }
-        if (small) {
-            if (v.metric == KDB_METRIC_COSINE) rc = launch_small_on(fss_kernel_for<KDB_METRIC_COSINE, KDB_PREC_F32>(v.ld), p2, d_fbq, lds_s);
-            else rc = launch_small_on(fss_kernel_for<KDB_METRIC_L2, KDB_PREC_F32>(v.ld), p2, d_fbq, lds_s);
-            if (rc) return rc;
-            KDB_HIP(hipGetLastError());
-        } else if (v.metric == KDB_METRIC_COSINE) {
-            auto kx = flat_scan_kernel<KDB_METRIC_COSINE, KDB_PREC_F32>;
-            KDB_HIP(hipFuncSetAttribute((const void *)kx, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            hipLaunchKernelGGL(kx, dim3(grid), dim3(256), lds, s, v, reinterpret_cast<const float *>(d_fbq), p2);
-            KDB_HIP(hipGetLastError());
-        } else {
-            auto kx = flat_scan_kernel<KDB_METRIC_L2, KDB_PREC_F32>;
-            KDB_HIP(hipFuncSetAttribute((const void *)kx, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            hipLaunchKernelGGL(kx, dim3(grid), dim3(256), lds, s, v, reinterpret_cast<const float *>(d_fbq), p2);
-            KDB_HIP(hipGetLastError());
-        }
-        if (v.metric == KDB_METRIC_COSINE) rc = launch_merge(flat_merge_kernel<KDB_METRIC_COSINE, KDB_PREC_F32, FM_ROUND>, p2, d_fbq);
-        else rc = launch_merge(flat_merge_kernel<KDB_METRIC_L2, KDB_PREC_F32, FM_ROUND>, p2, d_fbq);
-        if (rc) return rc;
-        KDB_HIP(hipGetLastError());
-        if (v.metric == KDB_METRIC_COSINE)
-            rc = rescue(flat_rescue_kernel<KDB_METRIC_COSINE, KDB_PREC_F32>, flat_merge_kernel<KDB_METRIC_COSINE, KDB_PREC_F32, FM_EXACT>, p2, d_fbq);
-        else rc = rescue(flat_rescue_kernel<KDB_METRIC_L2, KDB_PREC_F32>, flat_merge_kernel<KDB_METRIC_L2, KDB_PREC_F32, FM_EXACT>, p2, d_fbq);
-        // statistics: how many queries the exact pass settled (kdb_counters.n_hops of a flat-scan launch)
-        KDB_HIP(hipMemcpyAsync(stat_slot + 1, d_fbcount, 4, hipMemcpyDeviceToDevice, s));
-    } else if (v.precision == KDB_PREC_I8) {
-        rc = launch_merge(flat_merge_kernel<KDB_METRIC_COSINE, KDB_PREC_I8, FM_KL>, p, d_q);
-    } else if (v.precision == KDB_PREC_F16) {
-        rc = launch_merge(flat_merge_kernel<KDB_METRIC_L2, KDB_PREC_F16, FM_ROUND>, p, d_q);
-        if (rc) return rc;
-        KDB_HIP(hipGetLastError());
-        rc = rescue(flat_rescue_kernel<KDB_METRIC_L2, KDB_PREC_F16>, flat_merge_kernel<KDB_METRIC_L2, KDB_PREC_F16, FM_EXACT>, p, d_q);
-    } else if (v.metric == KDB_METRIC_COSINE) {
-        rc = launch_merge(flat_merge_kernel<KDB_METRIC_COSINE, KDB_PREC_F32, FM_ROUND>, p, d_q);
-        if (rc) return rc;
-        KDB_HIP(hipGetLastError());
-        rc = rescue(flat_rescue_kernel<KDB_METRIC_COSINE, KDB_PREC_F32>, flat_merge_kernel<KDB_METRIC_COSINE, KDB_PREC_F32, FM_EXACT>, p, d_q);
-    } else {
-        rc = launch_merge(flat_merge_kernel<KDB_METRIC_L2, KDB_PREC_F32, FM_ROUND>, p, d_q);
-        if (rc) return rc;
-        KDB_HIP(hipGetLastError());
-        rc = rescue(flat_rescue_kernel<KDB_METRIC_L2, KDB_PREC_F32>, flat_merge_kernel<KDB_METRIC_L2, KDB_PREC_F32, FM_EXACT>, p, d_q);
+        if (g.small) return fs_launch_small(c, fss_kernel_for<m, KDB_PREC_F32>(v.ld), v, d_fbq, p2, g.n_q16, g.lds_s);
+        return fs_launch_tile(c, flat_scan_kernel<m, KDB_PREC_F32>, v, d_fbq, p2);
+    };
+    return fs_settle(c, p, g.rank16, rtq, stat_slot, exact_pass);
+}
+
+int kdb_launch_flat_scan(kdb_index *idx, const KdbView &v, const void *d_q, const float *d_qnorm, uint32_t B,
+                         uint32_t k, const uint32_t *d_allow, const uint32_t *d_first_allowed, uint32_t *d_out_ids,
+                         float *d_out_dist, uint32_t *d_out_count, int queries_normalised, hipStream_t s) {
+    if (k == 0 || k > KDB_FLAT_MAX_K) {
+        kdb_set_error("flat scan: k must be in 1..%u (got %u)", KDB_FLAT_MAX_K, k);
+        return KDB_ERR_INVALID;
     }
-    if (rc) return rc;
-    KDB_HIP(hipGetLastError());
-    // statistics: queries answered by the rescue pass (high word of kdb_counters.n_hops of a flat-scan launch)
-    if (v.precision != KDB_PREC_I8)
-        KDB_HIP(hipMemcpyAsync(reinterpret_cast<uint32_t *>(stat_slot + 1) + 1, d_rscount, 4, hipMemcpyDeviceToDevice, s));
+    if (B == 0) return KDB_OK;
+    if (k > 128) return flat_scan_anyk(idx, v, d_q, d_qnorm, B, k, d_allow, d_first_allowed, d_out_ids, d_out_dist, d_out_count, queries_normalised, s);
+    const bool dist64 = (queries_normalised & 2) != 0; // int8: d_out_dist is a double array (KDB_SEARCH_DIST_F64)
+    const size_t qbytes = v.precision == KDB_PREC_I8 ? (size_t)v.ld : (size_t)v.ld * 4; // one prepared query
+    for (uint32_t b0 = 0; b0 < B; b0 += FS_MAX_B) {
+        const uint32_t nb = B - b0 < FS_MAX_B ? B - b0 : FS_MAX_B;
+        int rc = flat_scan_one(idx, v, reinterpret_cast<const unsigned char *>(d_q) + (size_t)b0 * qbytes, d_qnorm ? d_qnorm + b0 : nullptr, nb, k,
+                               d_allow, d_first_allowed, d_out_ids + (size_t)b0 * k, d_out_dist + (size_t)b0 * k * (dist64 ? 2u : 1u),
+                               d_out_count + b0, queries_normalised, s);
+        if (rc) return rc;
+    }
     return KDB_OK;
 }
 
 // Grouped exact scan: the queries of group g (rows [group_offsets[g], group_offsets[g+1]) of the batch) are scanned
 // against the rows allowed by list g.  One launch sequence for all groups, nothing read back from the device
 // unless the caller gave no bound on the total number of allowed rows.
-int kdb_launch_flat_scan_groups(kdb_index *idx, const KdbView &v, const void *d_q, const float *d_qnorm, uint32_t B,
-                                uint32_t k, uint32_t G, const uint32_t *group_offsets, const uint32_t *d_lists,
-                                uint32_t words32, uint64_t max_total_allowed, uint32_t *d_out_ids, float *d_out_dist,
-                                uint32_t *d_out_count, int queries_normalised, hipStream_t s) {
-    if (k == 0 || k > 128) {
-        kdb_set_error("flat scan: k must be in 1..128 (got %u)", k);
-        return KDB_ERR_INVALID;
-    }
-    if (B == 0 || G == 0) return KDB_OK;
-    const uint32_t kl = k + 16 > 144 ? 144 : k + 16; // finalists are re-scored in the order of the graph search
-    const uint32_t cap_s = kl + FS_TR + FSS_SLACK;
-    const size_t lds_s = (v.precision == KDB_PREC_I8 ? fss_q_bytes<KDB_PREC_I8>(v.ld) : v.precision == KDB_PREC_F16 ? fss_q_bytes<KDB_PREC_F16>(v.ld) : fss_q_bytes<KDB_PREC_F32>(v.ld)) +
-                         (size_t)FSS_TQ * cap_s * 8 + FSS_TAIL;
-    if (lds_s > 150u * 1024u) {
-        kdb_set_error("grouped flat scan: %u-d rows need %zu bytes of LDS per workgroup", v.dim, lds_s);
-        return KDB_ERR_UNSUPPORTED;
-    }
-    // 16-query tiles of every group + the group of every query (host: the caller's grouping is host knowledge)
-    std::vector<uint32_t> tiles, qgrp((size_t)B, 0u), qtile((size_t)B, 0u);
+
+// 16-query tiles of every group ([T][3]: group, first query, queries) + the group and the tile of every query (host: the
+// caller's grouping is host knowledge)
+static int fs_group_tables(uint32_t B, uint32_t G, const uint32_t *group_offsets, std::vector<uint32_t> &tiles, std::vector<uint32_t> &qgrp,
+                           std::vector<uint32_t> &qtile) {
+    qgrp.assign((size_t)B, 0u);
+    qtile.assign((size_t)B, 0u);
     for (uint32_t g = 0; g < G; g++) {
         const uint32_t a = group_offsets[g], b = group_offsets[g + 1];
         if (b < a || b > B) {
@@ -2313,16 +2352,59 @@ int kdb_launch_flat_scan_groups(kdb_index *idx, const KdbView &v, const void *d_
         kdb_set_error("grouped flat scan: group_offsets must start at 0 and end at B");
         return KDB_ERR_INVALID;
     }
+    return KDB_OK;
+}
+
+// Stripes per group.  Workgroup b runs on XCD b % 8 (the dispatcher deals workgroups round-robin) and serves stripe
+// (b/8/T)*8 + b%8, so that the tiles of one stripe share an L2: XCD x owns the stripes s = x (mod 8) and therefore
+// T * ceil-ish(want/8) workgroups for its n_cu/8 CUs.  Round 2 sized `want` as if the chip were one pool of slots: with
+// 105 tiles it picked 9 stripes, which gave XCD 0 twice the work of the others (config 5 ran at 2.85 TB/s).  Now the
+// estimated time -- rounds of the BUSIEST XCD x (rows of a stripe + a start-up allowance for the open threshold of a
+// stripe's first tiles) -- is minimised over the stripe counts the merge can take.
+static uint32_t fs_group_stripes(const kdb_index *idx, uint32_t T, uint32_t G, uint64_t total, uint32_t stripes_max, size_t lds_s) {
+    const uint32_t per_cu = (uint32_t)(160u * 1024u / lds_s) > 0 ? (uint32_t)(160u * 1024u / lds_s) : 1u;
+    const uint32_t slots_x = ((uint32_t)idx->n_cu / 8u > 0 ? (uint32_t)idx->n_cu / 8u : 1u) * (per_cu > 2 ? 2u : per_cu);
+    uint32_t want = 1;
+    const double rows_g = (double)total / (double)G; // rows per group (the caller's bound, or counted)
+    const double startup = 3.0 * FS_TR;
+    double best = 1e300;
+    const uint32_t lim = stripes_max < 64u ? stripes_max : 64u;
+    for (uint32_t w = 1; w <= lim; w++) {
+        if ((double)w * 4.0 * FS_TR > rows_g && w > 1) break; // a stripe is at least min_tiles tiles
+        const uint64_t on_x = (uint64_t)T * ((w + 7u) / 8u);  // workgroups of the busiest XCD
+        const uint64_t rounds = (on_x + slots_x - 1) / slots_x;
+        const double t = (double)rounds * (rows_g / (double)w + startup);
+        if (t < best * 0.98) { best = t; want = w; } // the fewest stripes within 2 % of the best
+    }
+    return want;
+}
+
+int kdb_launch_flat_scan_groups(kdb_index *idx, const KdbView &v, const void *d_q, const float *d_qnorm, uint32_t B,
+                                uint32_t k, uint32_t G, const uint32_t *group_offsets, const uint32_t *d_lists,
+                                uint32_t words32, uint64_t max_total_allowed, uint32_t *d_out_ids, float *d_out_dist,
+                                uint32_t *d_out_count, int queries_normalised, hipStream_t s) {
+    if (k == 0 || k > 128) {
+        kdb_set_error("flat scan: k must be in 1..128 (got %u)", k);
+        return KDB_ERR_INVALID;
+    }
+    if (B == 0 || G == 0) return KDB_OK;
+    const uint32_t kl = fs_kl(k); // finalists are re-scored in the order of the graph search
+    const size_t lds_s = fs_small_lds(v, kl);
+    if (lds_s > FS_LDS_MAX) {
+        kdb_set_error("grouped flat scan: %u-d rows need %zu bytes of LDS per workgroup", v.dim, lds_s);
+        return KDB_ERR_UNSUPPORTED;
+    }
+    const FsCall c{idx, v, d_q, d_qnorm, B, k, kl, d_out_ids, d_out_dist, d_out_count, s};
+    std::vector<uint32_t> tiles, qgrp, qtile;
+    int rc = fs_group_tables(B, G, group_offsets, tiles, qgrp, qtile);
+    if (rc) return rc;
     const uint32_t T = (uint32_t)(tiles.size() / 3);
-    uint32_t stripes_max = FS_MAX_MERGE / kl;
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const uint32_t nwords = (v.count >> 5) + 1u;
     const dim3 ggrid(FG_NB, G);
-    (void)nwords;
 
     // group sizes first if the caller gave no bound (one 4*G-byte read-back)
     const size_t chunk_words = (size_t)G * FG_NB;
-    int rc = kdb_ensure_scratch(idx, al(chunk_words * 4) * 2 + al((size_t)G * 4) * 2 + 4096);
+    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    rc = kdb_ensure_scratch(idx, al(chunk_words * 4) * 2 + al((size_t)G * 4) * 2 + 4096);
     if (rc) return rc;
     uint64_t total = max_total_allowed;
     if (total == 0) {
@@ -2332,69 +2414,39 @@ int kdb_launch_flat_scan_groups(kdb_index *idx, const KdbView &v, const void *d_
         std::vector<uint32_t> gn(chunk_words);
         KDB_HIP(hipMemcpyAsync(gn.data(), d_gn0, chunk_words * 4, hipMemcpyDeviceToHost, s));
         KDB_HIP(hipStreamSynchronize(s));
-        for (uint32_t c : gn) total += c;
+        for (uint32_t n : gn) total += n;
         if (total == 0) total = 1;
     }
     if (total > (uint64_t)G * v.count) total = (uint64_t)G * v.count;
-    // Stripes per group.  Workgroup b runs on XCD b % 8 (the dispatcher deals workgroups round-robin) and serves stripe
-    // (b/8/T)*8 + b%8, so that the tiles of one stripe share an L2: XCD x owns the stripes s = x (mod 8) and therefore
-    // T * ceil-ish(want/8) workgroups for its n_cu/8 CUs.  Round 2 sized `want` as if the chip were one pool of slots: with
-    // 105 tiles it picked 9 stripes, which gave XCD 0 twice the work of the others (config 5 ran at 2.85 TB/s).  Now the
-    // estimated time -- rounds of the BUSIEST XCD x (rows of a stripe + a start-up allowance for the open threshold of a
-    // stripe's first tiles) -- is minimised over the stripe counts the merge can take.
-    const uint32_t per_cu = (uint32_t)(160u * 1024u / lds_s) > 0 ? (uint32_t)(160u * 1024u / lds_s) : 1u;
-    const uint32_t slots_x = ((uint32_t)idx->n_cu / 8u > 0 ? (uint32_t)idx->n_cu / 8u : 1u) * (per_cu > 2 ? 2u : per_cu);
-    uint32_t want = 1;
-    {
-        const double rows_g = (double)total / (double)G; // rows per group (the caller's bound, or counted)
-        const double startup = 3.0 * FS_TR;
-        double best = 1e300;
-        const uint32_t lim = stripes_max < 64u ? stripes_max : 64u;
-        for (uint32_t w = 1; w <= lim; w++) {
-            if ((double)w * 4.0 * FS_TR > rows_g && w > 1) break; // a stripe is at least min_tiles tiles
-            const uint64_t on_x = (uint64_t)T * ((w + 7u) / 8u);  // workgroups of the busiest XCD
-            const uint64_t rounds = (on_x + slots_x - 1) / slots_x;
-            const double t = (double)rounds * (rows_g / (double)w + startup);
-            if (t < best * 0.98) { best = t; want = w; } // the fewest stripes within 2 % of the best
-        }
-        if (const char *e = KDB_AB_ENV("KDB_GROUP_STRIPES")) { // measurement knob
-            const uint32_t w = (uint32_t)atoi(e);
-            if (w >= 1 && w <= stripes_max) want = w;
-        }
-    }
-    const uint32_t min_tiles = 4;
+    const uint32_t want = fs_group_stripes(idx, T, G, total, FS_MAX_MERGE / kl, lds_s);
     const uint32_t n_qtiles = (B + FS_TQ - 1) / FS_TQ;
     const size_t n_part = (size_t)want * n_qtiles * FS_TQ;
 
-    const size_t ids_bytes = al((size_t)total * 4 + 1024);
+    const size_t ids_bytes = (size_t)total * 4 + 1024;
     const size_t part_bytes = n_part * kl * 8 + n_part * 4 + 1024;
-    // (the ranking copy's own row stride: see kdb_launch_flat_scan)
-    const bool copy_padded = v.precision == KDB_PREC_F32 && idx->d_rows16 != nullptr && idx->ld16 != v.ld;
-    KdbView vr = v;
-    if (copy_padded) vr.ld = idx->ld16;
-    const size_t qp_bytes = copy_padded ? al((size_t)B * vr.ld * 4) : 0;
-    const size_t need = ids_bytes + al((size_t)G * 4) * 2 + al(chunk_words * 4) * 2 + al(tiles.size() * 4) * 2 + al((size_t)B * 4) * 4 + 256 + al(part_bytes) + qp_bytes + 4096;
-    rc = kdb_ensure_scratch(idx, need);
+    const KdbView vr = fs_rank_view(idx, v);
+    const size_t qp_bytes = vr.ld != v.ld ? al((size_t)B * vr.ld * 4) : 0;
+    rc = kdb_ensure_scratch(idx, al(ids_bytes) + al((size_t)G * 4) * 2 + al(chunk_words * 4) * 2 + al(tiles.size() * 4) * 2 + al((size_t)B * 4) * 4 + 256 +
+                                     al(part_bytes) + qp_bytes + 4096);
     if (rc) return rc;
-    unsigned char *base = reinterpret_cast<unsigned char *>(idx->d_scratch);
-    uint32_t *d_ids = reinterpret_cast<uint32_t *>(base);
-    uint32_t *d_gn = reinterpret_cast<uint32_t *>(base + ids_bytes);
-    uint32_t *d_gbase = reinterpret_cast<uint32_t *>(base + ids_bytes + al((size_t)G * 4));
-    uint32_t *d_ccnt = reinterpret_cast<uint32_t *>(base + ids_bytes + 2 * al((size_t)G * 4));                  // [G][FG_NB] rows per chunk
-    uint32_t *d_cbase = reinterpret_cast<uint32_t *>(base + ids_bytes + 2 * al((size_t)G * 4) + al(chunk_words * 4)); // where each chunk writes
-    uint32_t *d_tiles = reinterpret_cast<uint32_t *>(base + ids_bytes + 2 * al((size_t)G * 4) + 2 * al(chunk_words * 4));
-    uint32_t *d_qgrp = reinterpret_cast<uint32_t *>(reinterpret_cast<unsigned char *>(d_tiles) + al(tiles.size() * 4));
-    uint32_t *d_qtile = reinterpret_cast<uint32_t *>(reinterpret_cast<unsigned char *>(d_qgrp) + al((size_t)B * 4));
-    uint32_t *d_qflag = reinterpret_cast<uint32_t *>(reinterpret_cast<unsigned char *>(d_qtile) + al((size_t)B * 4));
-    uint32_t *d_tflag = reinterpret_cast<uint32_t *>(reinterpret_cast<unsigned char *>(d_qflag) + al((size_t)B * 4));
-    uint32_t *d_fbc = reinterpret_cast<uint32_t *>(reinterpret_cast<unsigned char *>(d_tflag) + al(tiles.size() * 4));
+    FsBump scratch{reinterpret_cast<unsigned char *>(idx->d_scratch)};
+    uint32_t *d_ids = scratch.take<uint32_t>(ids_bytes);
+    uint32_t *d_gn = scratch.take<uint32_t>((size_t)G * 4);
+    uint32_t *d_gbase = scratch.take<uint32_t>((size_t)G * 4);
+    uint32_t *d_ccnt = scratch.take<uint32_t>(chunk_words * 4);  // [G][FG_NB] rows per chunk
+    uint32_t *d_cbase = scratch.take<uint32_t>(chunk_words * 4); // where each chunk writes
+    uint32_t *d_tiles = scratch.take<uint32_t>(tiles.size() * 4);
+    uint32_t *d_qgrp = scratch.take<uint32_t>((size_t)B * 4);
+    uint32_t *d_qtile = scratch.take<uint32_t>((size_t)B * 4);
+    uint32_t *d_qflag = scratch.take<uint32_t>((size_t)B * 4);
+    uint32_t *d_tflag = scratch.take<uint32_t>(tiles.size() * 4);
+    uint32_t *d_fbc = scratch.take<uint32_t>(256);
     uint32_t *d_rsc = d_fbc + 4; // queries handed to the rescue pass: count (inside the 256-byte block), list
-    uint32_t *d_rsl = reinterpret_cast<uint32_t *>(reinterpret_cast<unsigned char *>(d_fbc) + 256);
-    unsigned char *part = reinterpret_cast<unsigned char *>(d_rsl) + al((size_t)B * 4);
-    // float32 indexes with a half-precision row copy rank on it inside the error band (see kdb_launch_flat_scan); the
+    uint32_t *d_rsl = scratch.take<uint32_t>((size_t)B * 4);
+    unsigned char *part = scratch.take<unsigned char>(part_bytes);
+    // float32 indexes with a half-precision row copy rank on it inside the error band (see fs_plan); the
     // exact pass re-runs only the tiles that hold an unsettled query, with their group's id list
-    const bool rank16 = v.precision == KDB_PREC_F32 && idx->d_rows16 && (v.metric == KDB_METRIC_L2 || queries_normalised) &&
-                        idx->max_norm2 > 0.f && idx->max_norm2 <= 1.0e4f && !getenv("KDB_FLAT_EXACT_ONLY");
+    const bool rank16 = idx->d_rows16 && fs_rank16_ok(idx, v, queries_normalised != 0);
 
     FsParams p{};
     p.ctr = kdb_stats_begin(idx, 2, B, 0);
@@ -2414,121 +2466,60 @@ int kdb_launch_flat_scan_groups(kdb_index *idx, const KdbView &v, const void *d_
     p.n_scan = 0;
     p.n_scan_dev = nullptr;
     p.want = want;
-    p.min_tiles = min_tiles;
+    p.min_tiles = 4;
     p.n_qtiles = n_qtiles;
     p.B = B;
     p.kl = kl;
-    p.cap = kl;
-    p.part_key = reinterpret_cast<float *>(part);
-    p.part_id = reinterpret_cast<uint32_t *>(part + n_part * kl * 4);
-    p.part_cnt = reinterpret_cast<uint32_t *>(part + n_part * kl * 8);
+    fs_set_lists(p, part, n_part, kl);
     p.lists_query_major = 1u;
     p.rs_count = d_rsc;
     p.rs_list = d_rsl;
     p.rmax = idx->max_norm2 > 0.f ? sqrtf(idx->max_norm2) : 1.0f;
-    { const char *e = KDB_AB_ENV("KDB_FSS_DBG"); p.fb_dbg = e ? (uint32_t)atoi(e) : 0u; }
+    p.fb_dbg = fs_dbg_switches("KDB_FSS_DBG");
     p.g_tile = d_tiles;
     p.g_nscan = d_gn;
     p.g_base = d_gbase;
     p.g_of_query = d_qgrp;
     p.ctr = nullptr; // written by group_prefix_kernel
-    const uint32_t stripes8 = (want + 7) / 8 * 8;
     KDB_HIP(hipEventRecord(idx->ev0, s));
-    auto launch_small_view = [&](auto kern, const KdbView &vv, const void *qv, const FsParams &pp, size_t lds_k) -> int {
-        KDB_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_k));
-        hipLaunchKernelGGL(kern, dim3(stripes8 * T), dim3(256), lds_k, s, vv, reinterpret_cast<const float *>(qv), pp, T, cap_s);
-        return KDB_OK;
-    };
-    auto launch_small_on = [&](auto kern, const FsParams &pp, size_t lds_k) -> int { return launch_small_view(kern, v, d_q, pp, lds_k); };
-    auto launch_small = [&](auto kern) -> int { return launch_small_on(kern, p, lds_s); };
+
+    // ---- rank: always the small kernel, over the T tiles of the groups
+    const void *q_rank = d_q;
     if (rank16) {
         p.rows16 = idx->d_rows16;
-        const void *q_rank = d_q;
         if (qp_bytes) {
-            float *d_qp = reinterpret_cast<float *>(part + al(part_bytes));
-            const size_t quads = (size_t)B * (vr.ld >> 2);
-            hipLaunchKernelGGL(pad_queries_kernel, dim3((unsigned)((quads + 255) / 256)), dim3(256), 0, s, reinterpret_cast<const float *>(d_q), v.ld, d_qp,
-                               vr.ld, quads);
-            KDB_HIP(hipGetLastError());
+            float *d_qp = scratch.take<float>(qp_bytes);
+            rc = fs_pad_queries(v, vr, d_q, B, d_qp, s);
+            if (rc) return rc;
             q_rank = d_qp;
         }
-        const size_t lds_r = fss_q_bytes<FS_PREC_F32R>(vr.ld) + (size_t)FSS_TQ * cap_s * 8 + FSS_TAIL;
-        if (v.metric == KDB_METRIC_COSINE) rc = launch_small_view(fss_kernel_for<KDB_METRIC_COSINE, FS_PREC_F32R>(vr.ld), vr, q_rank, p, lds_r);
-        else rc = launch_small_view(fss_kernel_for<KDB_METRIC_L2, FS_PREC_F32R>(vr.ld), vr, q_rank, p, lds_r);
-    } else if (v.precision == KDB_PREC_I8) rc = launch_small(fss_kernel_for<KDB_METRIC_COSINE, KDB_PREC_I8>(v.ld));
-    else if (v.precision == KDB_PREC_F16) rc = launch_small(fss_kernel_for<KDB_METRIC_L2, KDB_PREC_F16>(v.ld));
-    else if (v.metric == KDB_METRIC_COSINE) rc = launch_small(fss_kernel_for<KDB_METRIC_COSINE, KDB_PREC_F32>(v.ld));
-    else rc = launch_small(fss_kernel_for<KDB_METRIC_L2, KDB_PREC_F32>(v.ld));
+    }
+    const KdbView &v_rank = rank16 ? vr : v;
+    auto rank = [&](auto M, auto P) -> int {
+        constexpr int m = decltype(M)::value, pr = decltype(P)::value;
+        return fs_launch_small(c, fss_kernel_for<m, pr>(v_rank.ld), v_rank, q_rank, p, T, fs_small_lds_as<pr>(v_rank.ld, kl));
+    };
+    rc = rank16 ? fs_dispatch<FS_PREC_F32R>(v.precision, v.metric, rank) : fs_dispatch(v.precision, v.metric, rank);
     if (rc) return rc;
-    KDB_HIP(hipGetLastError());
     KDB_HIP(hipEventRecord(idx->ev1, s));
-    const uint32_t nmax = want * kl;
-    const size_t mlds = (size_t)nmax * 8 + FS_FIN * 8 + 48 + 1024 + (size_t)v.ld * 4 + (size_t)want * 12 + 16;
-    auto launch_merge_on = [&](auto kern, const FsParams &pp) -> int {
-        KDB_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mlds));
-        hipLaunchKernelGGL(kern, dim3(B), dim3(256), mlds, s, v, reinterpret_cast<const float *>(d_q), d_qnorm, pp, k, nmax, d_out_ids,
-                           d_out_dist, d_out_count);
-        return KDB_OK;
-    };
-    auto launch_merge = [&](auto kern) -> int { return launch_merge_on(kern, p); };
-    const size_t rlds = fsr_lds_bytes(v.ld, 1); // grouped scan: one query per rescue work item
-    auto rescue = [&](auto scan_k, auto merge_k, const FsParams &pp) -> int { // see kdb_launch_flat_scan
-        KDB_HIP(hipFuncSetAttribute((const void *)scan_k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)rlds));
-        hipLaunchKernelGGL(scan_k, dim3(512), dim3(256), rlds, s, v, reinterpret_cast<const float *>(d_q), pp, 1u);
-        KDB_HIP(hipGetLastError());
-        return launch_merge_on(merge_k, pp);
-    };
+
+    // ---- settle (grouped scan: one query per rescue work item)
     if (rank16) {
-        const float rmax = v.metric == KDB_METRIC_COSINE ? (idx->max_norm2 > 1.0f ? sqrtf(idx->max_norm2) : 1.0f) : sqrtf(idx->max_norm2);
-        p.band = 2.0f * (9.9e-4f + (float)v.dim * 2.4e-7f) * rmax * 1.001f;
+        p.band = fs_band(idx, v);
         p.fb_count = d_fbc;
         p.q_flag = d_qflag;
         p.tile_flag = d_tflag;
         p.q_tile = d_qtile;
-        if (v.metric == KDB_METRIC_COSINE) rc = launch_merge_on(flat_merge_kernel<KDB_METRIC_COSINE, KDB_PREC_F32, FM_BAND16>, p);
-        else rc = launch_merge_on(flat_merge_kernel<KDB_METRIC_L2, KDB_PREC_F32, FM_BAND16>, p);
-        if (rc) return rc;
-        KDB_HIP(hipGetLastError());
-        FsParams p2 = p; // exact pass: the marked tiles, the marked queries
+    }
+    // the exact pass: the marked tiles, the marked queries, in place (their group's id list is needed again)
+    auto exact_pass = [&](auto M, FsParams &p2, const void *&qx) -> int {
+        qx = d_q;
+        p2 = p;
         p2.rows16 = nullptr;
-        p2.fb_count = nullptr;
-        p2.q_flag = nullptr;
-        p2.tile_flag = nullptr;
+        p2.fb_count = p2.q_flag = p2.tile_flag = nullptr;
         p2.q_sel = d_qflag;
         p2.tile_sel = d_tflag;
-        if (v.metric == KDB_METRIC_COSINE) rc = launch_small_on(fss_kernel_for<KDB_METRIC_COSINE, KDB_PREC_F32>(v.ld), p2, lds_s);
-        else rc = launch_small_on(fss_kernel_for<KDB_METRIC_L2, KDB_PREC_F32>(v.ld), p2, lds_s);
-        if (rc) return rc;
-        KDB_HIP(hipGetLastError());
-        if (v.metric == KDB_METRIC_COSINE) rc = launch_merge_on(flat_merge_kernel<KDB_METRIC_COSINE, KDB_PREC_F32, FM_ROUND>, p2);
-        else rc = launch_merge_on(flat_merge_kernel<KDB_METRIC_L2, KDB_PREC_F32, FM_ROUND>, p2);
-        if (rc) return rc;
-        KDB_HIP(hipGetLastError());
-        if (v.metric == KDB_METRIC_COSINE)
-            rc = rescue(flat_rescue_kernel<KDB_METRIC_COSINE, KDB_PREC_F32>, flat_merge_kernel<KDB_METRIC_COSINE, KDB_PREC_F32, FM_EXACT>, p2);
-        else rc = rescue(flat_rescue_kernel<KDB_METRIC_L2, KDB_PREC_F32>, flat_merge_kernel<KDB_METRIC_L2, KDB_PREC_F32, FM_EXACT>, p2);
-        if (stat_slot) KDB_HIP(hipMemcpyAsync(stat_slot + 1, d_fbc, 4, hipMemcpyDeviceToDevice, s));
-    } else if (v.precision == KDB_PREC_I8) {
-        rc = launch_merge(flat_merge_kernel<KDB_METRIC_COSINE, KDB_PREC_I8, FM_KL>);
-    } else if (v.precision == KDB_PREC_F16) {
-        rc = launch_merge(flat_merge_kernel<KDB_METRIC_L2, KDB_PREC_F16, FM_ROUND>);
-        if (rc) return rc;
-        KDB_HIP(hipGetLastError());
-        rc = rescue(flat_rescue_kernel<KDB_METRIC_L2, KDB_PREC_F16>, flat_merge_kernel<KDB_METRIC_L2, KDB_PREC_F16, FM_EXACT>, p);
-    } else if (v.metric == KDB_METRIC_COSINE) {
-        rc = launch_merge(flat_merge_kernel<KDB_METRIC_COSINE, KDB_PREC_F32, FM_ROUND>);
-        if (rc) return rc;
-        KDB_HIP(hipGetLastError());
-        rc = rescue(flat_rescue_kernel<KDB_METRIC_COSINE, KDB_PREC_F32>, flat_merge_kernel<KDB_METRIC_COSINE, KDB_PREC_F32, FM_EXACT>, p);
-    } else {
-        rc = launch_merge(flat_merge_kernel<KDB_METRIC_L2, KDB_PREC_F32, FM_ROUND>);
-        if (rc) return rc;
-        KDB_HIP(hipGetLastError());
-        rc = rescue(flat_rescue_kernel<KDB_METRIC_L2, KDB_PREC_F32>, flat_merge_kernel<KDB_METRIC_L2, KDB_PREC_F32, FM_EXACT>, p);
-    }
-    if (rc) return rc;
-    KDB_HIP(hipGetLastError());
-    if (stat_slot && v.precision != KDB_PREC_I8)
-        KDB_HIP(hipMemcpyAsync(reinterpret_cast<uint32_t *>(stat_slot + 1) + 1, d_rsc, 4, hipMemcpyDeviceToDevice, s));
-    return KDB_OK;
+        return fs_launch_small(c, fss_kernel_for<decltype(M)::value, KDB_PREC_F32>(v.ld), v, d_q, p2, T, lds_s);
+    };
+    return fs_settle(c, p, rank16, 1u, stat_slot, exact_pass);
 }

@@ -1,6 +1,5 @@
 """Config 5 (10M x 1536 cosine, 100 one-percent filters, 1024 queries grouped by filter): the grouped exact scan timed under the
-measurement knobs of flat_scan_small_kernel (KDB_FSS_CS: steps per register chunk, 0 = the generic instantiation; KDB_GROUP_STRIPES).
-The answers of every setting must be identical (a signature is printed).  With the measurement build (make -C kektordb_amd/csrc dbg;
+ceilings of the same table (a signature of the answers is printed).  With the measurement build (make -C kektordb_amd/csrc dbg;
 KEKTOR_HIP_LIB=kektordb_amd/lib/libkektor_hip_dbg.so) the KDB_FSS_DBG switches are walked instead: what each part of the kernel costs.
     python scripts/c5_probe.py [rows]"""
 import hashlib
@@ -31,8 +30,8 @@ def main():
     print(f"ceilings on THIS table (10M x 3072-byte half-precision rows, every row read about once -- nothing for the 256 MB memory-side "
           f"cache to reuse): uniform random whole-row gather {idx.probe_gather(10_000_000, shadow=True):.0f} GB/s, "
           f"one coalesced pass {idx.probe_stream(shadow=True):.0f} GB/s")
-    knobs = ("KDB_FSS_CS", "KDB_FSS_DBG", "KDB_GROUP_STRIPES")
-    cases = [{}, {"KDB_FSS_CS": "6"}, {"KDB_FSS_CS": "0"}, {"KDB_GROUP_STRIPES": "16"}, {"KDB_GROUP_STRIPES": "32"}, {"KDB_GROUP_STRIPES": "48"}, {}]
+    knobs = ("KDB_FSS_DBG",)
+    cases = [{}, {}]
     if "dbg" in os.environ.get("KEKTOR_HIP_LIB", ""):  # the measurement build: parts of the kernel switched off (answers are wrong)
         cases = [{"KDB_FSS_DBG": d} for d in ("0", "1", "2", "4", "6", "10", "14")]  # (8 alone would select with unloaded ids)
     for case in cases:

@@ -1,5 +1,5 @@
-"""round 6: where an UNCONTENDED short-row walk spends its cycles (timers + A/B build, one-wave kernel forced: KDB_WIDE_MAX_B=0
-KDB_WIDE2_MAX_B=0, 256 queries = one walk per CU)."""
+"""round 6: where an UNCONTENDED short-row walk spends its cycles (timers build, 256 queries = one walk per CU; round 6 forced
+the one-wave kernel with a switch that is gone: a batch this small now takes the four-wave latency mode)."""
 import os, sys
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))

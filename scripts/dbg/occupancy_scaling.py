@@ -1,6 +1,7 @@
 """round 6: is the short-row walk latency-bound or throughput-bound?  Kernel time of B one-wave walks for B = a fraction / a multiple of
-one round of resident waves (A/B build: KDB_WIDE_MAX_B=0 KDB_WIDE2_MAX_B=0 keep the one-wave kernel for small batches).
-    KEKTOR_HIP_LIB=.../libkektor_hip_ab.so KDB_WIDE_MAX_B=0 KDB_WIDE2_MAX_B=0 python scripts/dbg/occupancy_scaling.py [dim n metric ef]"""
+one round of resident waves.  (Round 6 ran it with the one-wave kernel forced for small batches; that switch is gone: batches that fit
+one round of four- or two-wave workgroups now take the latency mode.)
+    python scripts/dbg/occupancy_scaling.py [dim n metric ef]"""
 import os, sys
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))

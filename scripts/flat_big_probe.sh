@@ -1,6 +1,7 @@
 #!/bin/bash
 # Ablation + counters of the big-tile ranking kernel (flat_scan_big_kernel), 8192 queries over 1M x 768 f32 cosine.
-# KDB_FB_DBG: 1 no selection, 2 no DMA after the first slab, 4 no MFMAs (timings only: the answers are wrong).
+# KDB_FB_DBG: 1 no selection, 2 no DMA after the first slab, 4 no MFMAs (timings only: the answers are wrong); read only by the
+# `make dbg` build: run with KEKTOR_HIP_LIB=.../kektordb_amd/lib/libkektor_hip_dbg.so
 cd /tmp && export TMPDIR=/tmp
 R=/root/repo; O=$R/gpurun_out; TAG=${1:-fb}
 for d in 0 1 2 3 4 5 6; do echo "dbg=$d"; KDB_FB_DBG=$d python $R/scripts/flat_probe.py --bs ${BS:-8192} --reps 3 2>&1 | grep "B="; done

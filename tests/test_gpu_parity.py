@@ -1135,14 +1135,16 @@ def test_flat_scan_f16_ranked_band_l2(oracle, hip, case, B):
         assert np.array_equal(raw_to_score(idx, dist[b, :c]), od), (case, b)
 
 
-@pytest.mark.parametrize("B", [130, 11])
-@pytest.mark.parametrize("case", ["near_duplicates", "one_dense_stripe", "unnormalised_rows"])
+@pytest.mark.parametrize("case,B", [(c, B) for B in (130, 11) for c in ("near_duplicates", "one_dense_stripe", "unnormalised_rows")] +
+                         [("few_near_the_dense_stripe", 130)])
 def test_flat_scan_f16_ranked_band_is_exact(oracle, hip, case, B):
     """float32 cosine scans of more than 64 queries rank on the f16 MFMA inside an error band and settle what the
     band cannot decide with the exact kernel.  Adversarial corpora: thousands of rows whose scores differ by less
     than the f16 error (band overflow -> exact pass), a block of consecutive ids that all beat the rest (one stripe
     saturates), rows that are not unit length (the band scales with the largest row norm).  Answers must be the
-    oracle's, bit for bit."""
+    oracle's, bit for bit.  few_near_the_dense_stripe: the dense-stripe corpus with only the first 8 of 130 queries near the
+    block, the others plain random directions -- 1 .. 64 unsettled queries of a batch above 64 take the first tier of the exact
+    pass (the streaming kernel, then the tile kernel for none); the other cases leave all or none unsettled."""
     O = oracle
     rng = np.random.default_rng(17)
     n, dim, k = 6000, 64, 10
@@ -1150,12 +1152,14 @@ def test_flat_scan_f16_ranked_band_is_exact(oracle, hip, case, B):
     base /= np.linalg.norm(base)
     if case == "near_duplicates":
         X = base[None, :] + 2e-4 * rng.standard_normal((n, dim)).astype(np.float32)
-    elif case == "one_dense_stripe":
+    elif case in ("one_dense_stripe", "few_near_the_dense_stripe"):
         X = rng.standard_normal((n, dim)).astype(np.float32)
         X[1000:1200] = base[None, :] + 1e-3 * rng.standard_normal((200, dim)).astype(np.float32)
     else:
         X = rng.standard_normal((n, dim)).astype(np.float32) * rng.uniform(0.5, 3.0, size=(n, 1)).astype(np.float32)
     Q = (base[None, :] + 0.05 * rng.standard_normal((B, dim))).astype(np.float32)
+    if case == "few_near_the_dense_stripe":
+        Q[8:] = rng.standard_normal((B - 8, dim)).astype(np.float32)
     orc = O.OracleIndex(dim, 1, O.F32, 8, 20, seed=3)
     if case == "unnormalised_rows":
         # a mirror fed rows that are NOT normalised: bypass the oracle's insert-time normalisation by importing rows
@@ -1182,6 +1186,8 @@ def test_flat_scan_f16_ranked_band_is_exact(oracle, hip, case, B):
         assert settled_exactly == B        # every band overflows
     elif case == "one_dense_stripe":
         assert settled_exactly > 0         # the stripe that holds the block saturates inside the band
+    elif case == "few_near_the_dense_stripe":
+        assert 1 <= settled_exactly <= 64  # the few-unsettled tier of the exact pass
     for b in range(B):
         oi, od = orc.flat_scan(Q[b], k)
         c = int(cnt[b])
