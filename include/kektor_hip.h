@@ -22,6 +22,8 @@
  *   kdb_index_mark_deleted  Node.Deleted soft delete (hnsw_index.go:2303)
  *   kdb_index_build         addBatchInternal (hnsw_index.go:1479-2088), phases 1-4, on the GPU (fast linking)
  *   kdb_index_add_batch     the same phases with the reference's own linking: lists equal the restated batch insert's
+ *   kdb_index_add           Add (hnsw_index.go:472-809), the sequential single insert: one node after another, each against the
+ *                           graph the nodes before it left
  *   kdb_index_refine        GraphOptimizer.Refine / RunTurboRefine (pkg/core/hnsw/optimizer.go:288-560, :679-719): every
  *                           selected node re-linked against the graph as the call found it
  *   kdb_index_vacuum        GraphOptimizer.Vacuum (optimizer.go:133-277): nodes with links to deleted nodes found and re-linked,
@@ -357,6 +359,58 @@ KDB_API int kdb_index_build(kdb_index *idx, uint32_t count, const kdb_build_para
 #define KDB_ADD_REFERENCE_LINKS 1u /* (the only linking this entry point has; accepted for symmetry with kdb_build_params.flags) */
 KDB_API int kdb_index_add_batch(kdb_index *idx, uint32_t first_id, uint32_t n, const uint8_t *levels, uint32_t ef_construction,
                                 uint32_t flags);
+
+/* Add (pkg/core/hnsw/hnsw_index.go:472-809), the sequential single insert behind Engine.VAdd, on the device: afterwards the
+ * index is the one that n consecutive calls of the reference's Add would leave, on a single goroutine, for rows ALREADY uploaded
+ * at ids first_id .. first_id+n-1 in stored form (phase 0 / 1B = kdb_index_upload_rows [+ kdb_index_upload_norms], as for
+ * kdb_index_add_batch).  Per new node x, in id order:
+ *   - levels[i] = len(Connections)-1 as the caller drew it, capped at maxLevel+1 as randomLevel does (:2620-2623) -- the maxLevel
+ *     THAT NODE sees, i.e. after the nodes before it in the same call;
+ *   - empty graph (maxLevel -1; an index that holds rows and no graph at all counts as one: its rows are nodes without links):
+ *     x becomes the entry point, maxLevel its level, no links (:657-670);
+ *   - otherwise a descent with ef = 1 from maxLevel down to level(x)+1 (:685-690), then for l = min(level(x), maxLevel) .. 0:
+ *     searchLayerUnlocked(stored row of x, ep, efC, l, nil, efC) -- deleted nodes are traversed, never returned; int8: the packed
+ *     row with its norm (0 -> 1); selectNeighbors(candidates, mMax0 at level 0 else m) in the walk's ascending order becomes x's
+ *     list (:711-722); each selected neighbour r, in that order (:725-783): a list of r at l shorter than maxM gains x at its
+ *     end, a full one becomes selectNeighbors over its live existing links IN STORED ORDER, each at its node-to-node distance
+ *     from r, followed by x at d(r, x) -- so a full list that is pruned drops its links to deleted nodes (:756-761); ep becomes
+ *     the walk's nearest candidate (:786-788);
+ *   - level(x) above the maxLevel x found: x becomes the entry point, maxLevel its level (:793-801).
+ * Ties: selectNeighbors takes candidates "in the order given"; when a walk holds two different nodes at exactly equal distance
+ * the reference's order depends on its heaps' history ("Equal distances" above).  The walk here orders such nodes by id, as the
+ * builder and Refine do; a new node one of whose walks set the beam's tied bit is counted in tied_nodes, and its lists may differ
+ * from the reference's only where those equal distances meet.  Every other node is the reference's, step for step (float32 /
+ * float16: up to the summation order of the pair distances inside selectNeighbors; int8: bit for bit).
+ * NOT mirrored:
+ *   - a selected neighbour whose level is below l: the reference grows that node (:775-779).  It cannot occur on a graph that Add
+ *     or AddBatch made (a level-l list holds only nodes of level >= l); it is skipped and counted in reverse_skipped;
+ *   - training the quantizer on the first vector (:519-524): the caller sets the quantizer, as everywhere else in this ABI;
+ *   - external ids, the arena, and concurrency between Adds.
+ * first_id must equal count+1 (the slot re-use quirk belongs to kdb_index_add_batch alone), first_id+n-1 must stay within
+ * capacity, levels must not be NULL: otherwise KDB_ERR_INVALID, nothing touched.  n == 0: KDB_OK.  ef_construction outside
+ * 1..512, mMax0 > 64, rows beyond the limit of kdb_index_refine, or rows so long that a kernel's LDS (prune tiles + the walk's
+ * row, beam and side list) would exceed the device's: KDB_ERR_UNSUPPORTED, nothing touched.  A writer exactly
+ * like kdb_index_add_batch (same lock, same device-wide wait; the new nodes are registered as kdb_index_append_nodes registers
+ * them).  The inserts are a chain on the index's stream -- two launches per (node, level), no host synchronisation per node, no
+ * workgroup ever waits for another; everything is allocated before the first launch.  A device failure after the first launch
+ * returns its error with count, entry point and maxLevel unchanged on the host, but lists already rewritten stay as they are:
+ * upload the graph again.  Entry point, maxLevel and count change only after the final synchronisation succeeded.            */
+typedef struct {
+    uint32_t ef_construction; /* 0 = the index's; 1..512 */
+    uint32_t flags;           /* 0 */
+} kdb_add_params;
+typedef struct {
+    uint64_t nodes_added;
+    uint64_t forward_lists;     /* (new node, level) lists written */
+    uint64_t reverse_appended;  /* neighbour lists that had room: new id appended (:748-752) */
+    uint64_t reverse_pruned;    /* neighbour lists that were full: selectNeighbors over old links + new node (:753-771) */
+    uint64_t tied_nodes;        /* new nodes one of whose walks held two different nodes at equal distance (see "Ties") */
+    uint64_t reverse_skipped;   /* selected neighbours whose level is below the link's level (see "NOT mirrored") */
+    uint32_t entry;             /* after the call */
+    int32_t  max_level;         /* after the call */
+} kdb_add_stats;
+KDB_API int kdb_index_add(kdb_index *idx, uint32_t first_id, uint32_t n, const uint8_t *levels,
+                          const kdb_add_params *params, kdb_add_stats *out /* may be NULL */);
 
 /* GraphOptimizer.Refine (pkg/core/hnsw/optimizer.go:288-464; MaintenanceRun("refine"), RunTurboRefine :679-719) on the device:
  * the neighbour lists of the selected nodes are computed again against the graph AS THE CALL FOUND IT and replace the stored

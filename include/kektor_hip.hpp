@@ -105,6 +105,14 @@ class Index {
         kdb_build_params p{batch, 0, seed, 0, 0};
         check(kdb_index_build(h_, count, &p), "build");
     }
+    // Add (hnsw_index.go:472-809) on the device for rows already uploaded at firstID ..: n nodes one after another, each linked against
+    // the graph the nodes before it left; levels[i] as drawn by the caller (capped at maxLevel+1 as randomLevel does)
+    kdb_add_stats Add(uint32_t firstID, const uint8_t *levels, uint32_t n, uint32_t efConstruction = 0) {
+        kdb_add_params p{efConstruction, 0};
+        kdb_add_stats st{};
+        check(kdb_index_add(h_, firstID, n, levels, &p, &st), "add");
+        return st;
+    }
     // GraphOptimizer.Refine (optimizer.go:288-464) on the device: the lists of `ids` (empty: every live node) against the graph as it is
     kdb_refine_stats Refine(const std::vector<uint32_t> &ids = {}, uint32_t efConstruction = 0, uint32_t chunkNodes = 0) {
         kdb_refine_params p{efConstruction, 0, chunkNodes};

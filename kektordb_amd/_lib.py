@@ -26,7 +26,7 @@ ABI_SYMBOLS = [
     "kdb_index_sync", "kdb_index_set_launch_timing", "kdb_test_select_neighbors", "kdb_cluster_create", "kdb_cluster_destroy", "kdb_cluster_info",
     "kdb_sharded_search_batch", "kdb_sharded_flat_scan_batch", "kdb_index_compress", "kdb_index_get_quantizer", "kdb_index_add_batch", "kdb_merge_topk_packed_f64_dev",
     "kdb_cluster_comm_info", "kdb_cluster_debug_fail_next", "kdb_index_reserve", "kdb_index_drop_f16_shadow", "kdb_probe_gather", "kdb_probe_stream", "kdb_probe_poison_lds", "kdb_index_caller_stats", "kdb_merge_topk_f64", "kdb_index_refine",
-    "kdb_index_vacuum", "kdb_index_dead_link_scan", "kdb_index_drop_walk_planes",
+    "kdb_index_vacuum", "kdb_index_dead_link_scan", "kdb_index_drop_walk_planes", "kdb_index_add",
 ]
 
 
@@ -63,6 +63,16 @@ class RefineParams(C.Structure):
 class RefineStats(C.Structure):
     _fields_ = [("nodes_refined", C.c_uint64), ("lists_written", C.c_uint64), ("lists_changed", C.c_uint64),
                 ("dead_links_dropped", C.c_uint64)]
+
+
+class AddParams(C.Structure):
+    _fields_ = [("ef_construction", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class AddStats(C.Structure):
+    _fields_ = [("nodes_added", C.c_uint64), ("forward_lists", C.c_uint64), ("reverse_appended", C.c_uint64),
+                ("reverse_pruned", C.c_uint64), ("tied_nodes", C.c_uint64), ("reverse_skipped", C.c_uint64),
+                ("entry", C.c_uint32), ("max_level", C.c_int32)]
 
 
 class VacuumParams(C.Structure):
@@ -134,6 +144,7 @@ def load():
     L.kdb_distance_batch_dev.argtypes = [vp, vp, u32, vp, u32, u32, vp, vp]
     L.kdb_index_build.argtypes = [vp, u32, C.POINTER(BuildParams)]
     L.kdb_index_add_batch.argtypes = [vp, u32, u32, vp, u32, u32]
+    L.kdb_index_add.argtypes = [vp, u32, u32, vp, C.POINTER(AddParams), C.POINTER(AddStats)]
     L.kdb_index_refine.argtypes = [vp, vp, u32, C.POINTER(RefineParams), C.POINTER(RefineStats)]
     L.kdb_index_vacuum.argtypes = [vp, C.POINTER(VacuumParams), C.POINTER(VacuumStats)]
     L.kdb_index_dead_link_scan.argtypes = [vp, vp, u32, C.POINTER(u32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]

@@ -28,6 +28,7 @@
 // wave resolves the block sequentially from those matrices -- exactly the reference's rule: keep e
 // unless some kept r has d(e,r) < d(e,centre); stop at m; back-fill from the discarded in order.
 #include "kdb_search_core.cuh"
+#include "kdb_add_plan.h"
 #include <algorithm>
 #include <cmath>
 #include <type_traits>
@@ -208,7 +209,8 @@ build_search_kernel(KdbView v, BuildViewT<typename BKey<PREC>::T> bv, uint32_t b
 // ---- selectNeighbors on a workgroup ---------------------------------------------------------------
 template <typename KT>
 struct PruneLdsT {
-    uint32_t *c_id;    // [PR_MAXC] candidates ascending by (key,id)
+    uint32_t *c_id;    // [PR_MAXC] candidates IN THE ORDER selectNeighbors takes them: ascending by (key,id) from a walk or a sort,
+                       // the stored order of a list (+ the new node last) from the reverse prune of Add (add_reverse_kernel)
     KT *c_key;         // [PR_MAXC]
     uint32_t *s_id;    // [PR_MAXSEL]
     KT *s_key;         // [PR_MAXSEL]
@@ -256,7 +258,11 @@ __device__ __forceinline__ double i8_pair_distance(int dot, float n1, float n2) 
     return 1.0 - sim;
 }
 
-// candidates c_id/c_key[0..n) sorted ascending -> s_id/s_key[0..n_sel). Whole workgroup (256 threads).
+// candidates c_id/c_key[0..n) "in the order given" (:2629) -> s_id/s_key[0..n_sel). Whole workgroup (256 threads).
+// ORDER-PRESERVING: every caller but one hands over a list ascending by (key,id), yet nothing below relies on that -- a candidate
+// is tested against the kept ones before it (m1: kept in earlier blocks, m2 + selmask: kept earlier in its own block), the loop
+// stops at maxm kept, the discarded are recorded and back-filled in the order they were met; no early-out compares keys of two
+// candidates.  The reverse prune of Add (add_reverse_kernel) hands over a list's STORED order with the new node last.
 template <int METRIC, int PREC>
 __device__ void select_neighbors_wg(const KdbView &v, const PruneLdsT<typename BKey<PREC>::T> &p, uint32_t n, uint32_t maxm) {
     using KT = typename BKey<PREC>::T;
@@ -1866,6 +1872,198 @@ void vacuum_ids_of(const std::vector<uint32_t> &flags, std::vector<uint32_t> &id
         for (uint32_t f = flags[w]; f; f &= f - 1u) ids.push_back((uint32_t)(w << 5) + (uint32_t)__builtin_ctz(f));
 }
 
+// =====================================================================================================================
+// Add (kdb_index_add): the sequential single insert (pkg/core/hnsw/hnsw_index.go:472-809), one node after another.  Node i+1 must
+// see node i's links, so the inserts are a CHAIN -- kept on the stream, not on the host: two launches per (node, level), their
+// arguments (capped level, the entry point and maxLevel the node finds) known up front from kdb_add_plan.h.
+//   add_link_kernel     one workgroup: wave 0 walks (on the node's first linked level the ef = 1 descent first, :685-690; on the
+//                       levels below, the entry point is the previous level's nearest candidate, left in the state block), the
+//                       workgroup runs selectNeighbors, writes x's list (:711-722) and leaves the selection in the state block;
+//   add_reverse_kernel  maxM workgroups, one per possible selected neighbour r (:725-783): each owns r's list at that level, so
+//                       no two write the same list; appends x, or prunes [live links in stored order, x].
+// No workgroup waits for another; what orders the steps is the stream.  Every loop is bounded by ef, maxM or the list capacity.
+// State block (device words): 0 ep | 1 its distance is known | 2 key | 3 key, low word (int8) | 4 a walk of this node tied |
+// 5 selected count | 8.. selected ids.  Counters (64-bit): 0 appended | 1 pruned | 2 tied nodes | 3 skipped (level below l).
+// =====================================================================================================================
+constexpr uint32_t AD_SEL = 8; // first selected id in the state block
+constexpr uint32_t AD_STATE_WORDS = AD_SEL + PR_MAXSEL;
+
+template <typename KT>
+__host__ __device__ constexpr size_t add_prune_bytes() { return (prune_lds_bytes<KT>() + 15) & ~(size_t)15; }
+
+// from_level: the maxLevel the node found when `level` is its first linked level (the descent starts there), -1 on the levels below
+template <int METRIC, int BS, int PREC>
+__global__ void __launch_bounds__(256)
+add_link_kernel(KdbView v, uint32_t *adj0, uint32_t *adj_up, uint32_t node, int level, int from_level, uint32_t entry, uint32_t efc, uint32_t beam_cap,
+                uint32_t nr_cap, uint32_t *visited, uint32_t *st, unsigned long long *ctr) {
+    using KT = typename BKey<PREC>::T;
+    constexpr bool I8 = PREC == KDB_PREC_I8;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    PruneLdsT<KT> p;
+    prune_carve(smem, p);
+    const uint32_t tid = threadIdx.x;
+    const uint32_t wave = uni(tid >> 6); // (scalar: the walk below is one wave's, behind a scalar branch)
+    if (wave == 0u) {
+        WaveLds s;
+        build_search_carve<BS, I8>(smem + add_prune_bytes<KT>(), v, beam_cap, nr_cap, s);
+        const int lane = kdb_lane();
+        VisBitset vis;
+        vis.bits = visited;
+        vis.words = v.vis_words;
+        vis.marks = s.marks;
+        const bool first = from_level >= level;
+        if (first) vis.begin_query(); // (the levels below find the set clean: a layer above 0 un-marks what it marked)
+        const float qnorm = build_load_own_row<PREC>(v, s, node, lane);
+        __threadfence_block();
+        wave_lds_fence();
+        typename std::conditional<BS == 0, LdsBeamT<I8>, RegBeam<(BS == 0 ? 1 : BS), I8>>::type b;
+        b.bind(s);
+        b.tied = 0u;
+        QCtr qc{};
+        uint32_t ep = entry;
+        EpKnown epk;
+        auto nearest = [&]() { // :786-788
+            if (b.count > 0) {
+                float d0;
+                uint32_t l0, f0;
+                b.get(0, d0, l0, f0);
+                ep = f0 & KDB_ID_MASK;
+                epk.known = true;
+                epk.key = d0;
+                epk.lo = l0;
+            } else {
+                epk.known = false;
+            }
+        };
+        if (first) {
+            for (int l = from_level; l > level; l--) { // zoom in, :685-690
+                search_layer<PREC, METRIC, 0>(v, s, b, vis, nullptr, ep, l, 1u, qnorm, qc, epk);
+                nearest();
+            }
+        } else {
+            ep = uni(st[0]);
+            epk.known = uni(st[1]) != 0u;
+            epk.key = unif(__uint_as_float(st[2]));
+            epk.lo = uni(st[3]);
+            b.tied = uni(st[4]);
+        }
+        uint32_t nc = 0;
+        if (ep - 1u < v.count) { // (never an address from an id that names no node)
+            search_layer<PREC, METRIC, 0>(v, s, b, vis, nullptr, ep, level, efc, qnorm, qc, epk);
+            if constexpr (I8) nc = b.write_results(efc, p.c_id, nullptr, false, p.c_key);
+            else nc = b.write_results(efc, p.c_id, p.c_key, false);
+            nearest();
+        }
+        if (lane == 0) {
+            p.misc[6] = nc;
+            st[0] = ep;
+            st[1] = epk.known ? 1u : 0u;
+            st[2] = __float_as_uint(epk.key);
+            st[3] = epk.lo;
+            st[4] = b.tied;
+            if (level == 0 && b.tied) atomicAdd(ctr + 2, 1ull); // level 0 is a node's last walk
+        }
+    }
+    __syncthreads();
+    const uint32_t n = p.misc[6];
+    const uint32_t maxm = level == 0 ? v.deg0 : v.deg_up;
+    select_neighbors_wg<METRIC, PREC>(v, p, n, maxm);
+    const uint32_t nsel = p.misc[0];
+    uint32_t *adj = level == 0 ? adj0 + (size_t)node * v.deg0 : adj_up + ((size_t)v.up_idx[node] + (size_t)(level - 1)) * v.deg_up;
+    if (tid < maxm) adj[tid] = tid < nsel ? p.s_id[tid] : 0u;
+    if (tid < (uint32_t)PR_MAXSEL) st[AD_SEL + tid] = tid < nsel ? p.s_id[tid] : 0u;
+    if (tid == 0) st[5] = nsel;
+}
+
+// workgroup b: the b-th selected neighbour of `node` at `level`
+template <int METRIC, int PREC>
+__global__ void __launch_bounds__(256)
+add_reverse_kernel(KdbView v, uint32_t *adj0, uint32_t *adj_up, uint32_t node, uint32_t level, const uint32_t *st, unsigned long long *ctr) {
+    using KT = typename BKey<PREC>::T;
+    constexpr bool I8 = PREC == KDB_PREC_I8;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    PruneLdsT<KT> p;
+    prune_carve(smem, p);
+    size_t o = add_prune_bytes<KT>();
+    float *w_d = reinterpret_cast<float *>(smem + o); // [4][64] distances of a wave's chunk
+    o += 4 * 64 * 4;
+    uint32_t *w_lo = reinterpret_cast<uint32_t *>(smem + o);
+    o += 4 * 64 * 4;
+    float *tq = reinterpret_cast<float *>(smem + o); // r's row as the query of the node-to-node distances
+    __shared__ uint32_t sh[2];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const uint32_t maxm = level == 0 ? v.deg0 : v.deg_up;
+    uint32_t nsel = st[5];
+    if (nsel > maxm) nsel = maxm;
+    if (blockIdx.x >= nsel) return;
+    const uint32_t r = st[AD_SEL + blockIdx.x];
+    if (r - 1u >= v.count || r == node) return;                // never an address from an id that names no node
+    if ((v.deleted[r >> 5] >> (r & 31u)) & 1u) return;         // "neighbor == nil || Deleted: continue" (a walk never returns one)
+    if (level > 0u && (uint32_t)v.levels[r] < level) {         // the reference grows r (:775-779): not mirrored, counted
+        if (tid == 0) atomicAdd(ctr + 3, 1ull);
+        return;
+    }
+    uint32_t *adj = level == 0 ? adj0 + (size_t)r * v.deg0 : adj_up + ((size_t)v.up_idx[r] + (size_t)(level - 1u)) * v.deg_up;
+    if (tid < 64u) { // the list as stored; its live links, in that order (:756-761)
+        const uint32_t w = tid < maxm ? adj[tid] : 0u;
+        const unsigned long long holes = ~__ballot(w != 0u);
+        const uint32_t ne = holes ? (uint32_t)__builtin_ctzll(holes) : 64u; // packed from the front: the first zero word ends it
+        const bool live = tid < ne && w - 1u < v.count && w != node && !((v.deleted[w >> 5] >> (w & 31u)) & 1u);
+        const unsigned long long lm = __ballot(live);
+        if (live) p.c_id[kdb_mbcnt(lm)] = w;
+        if (tid == 0) {
+            sh[0] = ne;
+            sh[1] = (uint32_t)__builtin_popcountll(lm);
+        }
+    }
+    __syncthreads();
+    const uint32_t ne = sh[0];
+    if (ne < maxm) { // room: x at the end (:748-752)
+        if (tid == 0) {
+            adj[ne] = node;
+            atomicAdd(ctr + 0, 1ull);
+        }
+        return;
+    }
+    const uint32_t na = sh[1] + 1u; // live links, then x (:762)
+    if (tid == 0) p.c_id[na - 1u] = node;
+    float qnorm = 1.f;
+    if (I8) {
+        const uint4 *src = reinterpret_cast<const uint4 *>(reinterpret_cast<const int8_t *>(v.rows) + (size_t)r * v.ld);
+        for (uint32_t i = tid; i < (v.ld >> 4); i += 256) reinterpret_cast<uint4 *>(tq)[i] = src[i];
+        qnorm = v.norms[r]; // (a zero norm on either side: distance 1, see rl_commit_body)
+        if (qnorm == 0.f) qnorm = 1.f;
+    } else if (PREC == KDB_PREC_F16) {
+        const uint16_t *src = reinterpret_cast<const uint16_t *>(v.rows) + (size_t)r * v.ld;
+        for (uint32_t i = tid; i < v.ld; i += 256) tq[i] = (float)__builtin_bit_cast(_Float16, src[i]);
+    } else {
+        const float4 *src = reinterpret_cast<const float4 *>(reinterpret_cast<const float *>(v.rows) + (size_t)r * v.ld);
+        for (uint32_t i = tid; i < (v.ld >> 2); i += 256) reinterpret_cast<float4 *>(tq)[i] = src[i];
+    }
+    __syncthreads();
+    { // distanceBetweenNodes(r, link) (:297-340): 16 lanes per row, a wave per chunk of 64
+        WaveLds s{};
+        s.q = tq;
+        s.nb_d = w_d + wave * 64u;
+        s.nb_lo = I8 ? w_lo + wave * 64u : nullptr;
+        for (uint32_t c0 = wave * 64u; c0 < na; c0 += 256u) {
+            const uint32_t cn = na - c0 < 64u ? na - c0 : 64u;
+            s.nb_id = p.c_id + c0;
+            compute_dists<PREC, METRIC, 0>(v, s, cn, qnorm);
+            if (lane < cn) {
+                if constexpr (I8) p.c_key[c0 + lane] = kdb_i8_key_double(s.nb_d[lane], s.nb_lo[lane]);
+                else p.c_key[c0 + lane] = s.nb_d[lane];
+            }
+            wave_lds_fence();
+        }
+    }
+    __syncthreads();
+    select_neighbors_wg<METRIC, PREC>(v, p, na, maxm); // NOT sorted first: the stored order is the order given
+    const uint32_t ns2 = p.misc[0];
+    if (tid < maxm) adj[tid] = tid < ns2 ? p.s_id[tid] : 0u;
+    if (tid == 0) atomicAdd(ctr + 1, 1ull);
+}
+
 } // namespace
 
 // d_keys: float keys for float32 / float16 indexes, DOUBLE distances for int8 indexes (the reference's float64)
@@ -1951,6 +2149,170 @@ static int refine_limits(const kdb_index *idx, uint32_t efc, const char *who) {
         return KDB_ERR_UNSUPPORTED;
     }
     return KDB_OK;
+}
+
+// Add for rows already in place.  Everything that can fail for want of memory comes before the first launch; the host side of the
+// handle (level tables, slot count, count, entry point, maxLevel) changes after the final synchronisation succeeded.
+template <int METRIC, int PREC>
+static int add_impl(kdb_index *idx, uint32_t first, uint32_t nb, const uint8_t *lv_in, uint32_t efc, kdb_add_stats *out) {
+    using KT = typename BKey<PREC>::T;
+    hipStream_t s = idx->stream;
+    const uint32_t new_count = first + nb - 1u;
+    const bool bare = idx->h_levels.size() != (size_t)idx->count + 1; // rows without a graph: nodes of level 0 without links
+    // ---- the plan: capped levels, the entry point and maxLevel every node finds (kdb_add_plan.h), upper slots
+    std::vector<KdbAddStep> steps(nb);
+    uint32_t entry = idx->has_graph ? idx->entry : 0u;
+    int32_t max_level = idx->has_graph ? idx->max_level : -1;
+    kdb_add_plan(&entry, &max_level, first, lv_in, nb, steps.data());
+    std::vector<uint8_t> lv(nb);
+    std::vector<uint32_t> up_new(nb);
+    size_t slots = bare ? 0 : idx->up_slots;
+    for (uint32_t i = 0; i < nb; i++) {
+        lv[i] = steps[i].level;
+        up_new[i] = (uint32_t)slots;
+        slots += (size_t)lv[i];
+    }
+    // ---- LDS of the two kernels against the device's limit, before anything is allocated or touched
+    const uint32_t beam_cap = ((efc + 64 + 1) + 63) / 64 * 64;
+    const int bs = kdb_beam_slots(efc) == 0 ? 0 : kdb_beam_slots(efc) < 2 ? 2 : kdb_beam_slots(efc);
+    const uint32_t nr_cap = ((idx->n_deleted < 2047u ? idx->n_deleted : 2047u) + 1u + 3u) & ~3u; // traversal-only candidates (deleted nodes)
+    const size_t lds_search = (PREC == KDB_PREC_I8 ? (size_t)idx->ld + 64 * 12 : (size_t)idx->ld * 4 + 64 * 8) + KDB_UP_MARK_CAP * 4 +
+                              (bs == 0 ? (size_t)beam_cap * (PREC == KDB_PREC_I8 ? 12 : 8) : 0) + (size_t)nr_cap * (PREC == KDB_PREC_I8 ? 12 : 8);
+    const size_t lds_link = add_prune_bytes<KT>() + lds_search;
+    const size_t lds_rev = add_prune_bytes<KT>() + 2048 + (size_t)idx->ld * (PREC == KDB_PREC_I8 ? 1 : 4) + 64; // r's row: packed int8, else f32
+    int lds_max = 0;
+    if (hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, idx->device) != hipSuccess || lds_max <= 0) lds_max = 64 * 1024;
+    if (lds_link > (size_t)lds_max || lds_rev > (size_t)lds_max) {
+        kdb_set_error("add: rows of %u elements with ef_construction %u and %u deleted nodes need %zu bytes of LDS per workgroup, the device has %d",
+                      idx->ld, efc, idx->n_deleted, lds_link > lds_rev ? lds_link : lds_rev, lds_max);
+        return KDB_ERR_UNSUPPORTED;
+    }
+    // ---- workspace, kernels, visited set: every allocation and attribute call of the call, up front
+    const size_t ws_bytes = 256 + (size_t)AD_STATE_WORDS * 4;
+    if (idx->build_bytes < ws_bytes) {
+        if (idx->d_build) KDB_HIP(hipFree(idx->d_build));
+        idx->d_build = nullptr;
+        idx->build_bytes = 0;
+        KDB_HIP(hipMalloc(&idx->d_build, ws_bytes));
+        idx->build_bytes = ws_bytes;
+    }
+    unsigned long long *d_ctr = reinterpret_cast<unsigned long long *>(idx->d_build);
+    uint32_t *d_st = reinterpret_cast<uint32_t *>(reinterpret_cast<unsigned char *>(idx->d_build) + 256);
+    auto klink = bs == 0 ? add_link_kernel<METRIC, 0, PREC> : bs == 2 ? add_link_kernel<METRIC, 2, PREC> : add_link_kernel<METRIC, 4, PREC>;
+    auto krev = add_reverse_kernel<METRIC, PREC>;
+    KDB_HIP(hipFuncSetAttribute((const void *)klink, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_link));
+    KDB_HIP(hipFuncSetAttribute((const void *)krev, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_rev));
+    int rc = kdb_ensure_visited(idx, 1u, s); // one bitset for the call: the walks are a chain
+    if (rc) return rc;
+    if (slots > idx->up_slots_cap || !idx->d_adj_up) { // a larger upper pool, filled with what the old one holds
+        const size_t grown_cap = slots + slots / 2 + 1024;
+        uint32_t *grown = nullptr;
+        KDB_HIP(hipMalloc(&grown, (grown_cap * idx->deg_up + 4) * 4));
+        hipError_t e = hipMemsetAsync(grown, 0, (grown_cap * idx->deg_up + 4) * 4, s);
+        if (e == hipSuccess && idx->d_adj_up && idx->up_slots && !bare)
+            e = hipMemcpyAsync(grown, idx->d_adj_up, idx->up_slots * idx->deg_up * 4, hipMemcpyDeviceToDevice, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) {
+            (void)hipFree(grown);
+            KDB_HIP(e);
+        }
+        if (idx->d_adj_up) (void)hipFree(idx->d_adj_up); // (same lists in a larger pool: no field of the handle means anything else)
+        idx->d_adj_up = grown;
+        idx->up_slots_cap = grown_cap;
+    } else if (slots > (bare ? 0 : idx->up_slots)) {
+        const size_t from = bare ? 0 : idx->up_slots;
+        KDB_HIP(hipMemsetAsync(idx->d_adj_up + from * idx->deg_up, 0, (slots - from) * idx->deg_up * 4, s));
+    }
+    // ---- the new nodes on the device, as kdb_index_append_nodes registers them: empty lists, levels, first upper slots
+    if (bare && idx->count) {
+        KDB_HIP(hipMemsetAsync(idx->d_adj0, 0, ((size_t)idx->count + 1) * idx->deg0 * 4, s));
+        KDB_HIP(hipMemsetAsync(idx->d_levels, 0, (size_t)idx->count + 1, s));
+        KDB_HIP(hipMemsetAsync(idx->d_up_idx, 0, ((size_t)idx->count + 1) * 4, s));
+    }
+    KDB_HIP(hipMemsetAsync(idx->d_adj0 + (size_t)first * idx->deg0, 0, (size_t)nb * idx->deg0 * 4, s));
+    KDB_HIP(hipMemcpyAsync(idx->d_levels + first, lv.data(), nb, hipMemcpyHostToDevice, s));
+    KDB_HIP(hipMemcpyAsync(idx->d_up_idx + first, up_new.data(), (size_t)nb * 4, hipMemcpyHostToDevice, s));
+    KDB_HIP(hipMemsetAsync(idx->d_build, 0, ws_bytes, s));
+    KdbView v = kdb_make_view(idx);
+    v.count = new_count; // the new ids are valid wherever a later node's walk meets them
+    unsigned long long h_ctr[4] = {0, 0, 0, 0};
+    // the derived upper-slot table is a function of levels / up_idx / the upper lists: nodes that only exist at level 0 change
+    // none of its inputs (kdb_index_append_nodes' rule), so the first search after such an insert pays no rebuild
+    if (slots != (bare ? 0 : idx->up_slots) || bare) idx->graph_epoch++;
+    // ---- the chain; an error behind the first launch waits for what is queued before it returns
+    auto chain = [&]() -> int {
+    for (uint32_t i = 0; i < nb; i++) {
+        const KdbAddStep &st = steps[i];
+        if (st.max_level < 0) continue; // the first node of an empty graph: entry point, no links (:657-670)
+        const int top = (int)st.level < st.max_level ? (int)st.level : st.max_level; // links only up to the current top (:694-697)
+        for (int l = top; l >= 0; l--) {
+            hipLaunchKernelGGL(klink, dim3(1), dim3(256), lds_link, s, v, idx->d_adj0, idx->d_adj_up, first + i, l, l == top ? st.max_level : -1, st.entry, efc,
+                               beam_cap, nr_cap, idx->d_visited, d_st, d_ctr);
+            hipLaunchKernelGGL(krev, dim3(l == 0 ? idx->deg0 : idx->deg_up), dim3(256), lds_rev, s, v, idx->d_adj0, idx->d_adj_up, first + i, (uint32_t)l,
+                               (const uint32_t *)d_st, d_ctr);
+        }
+        KDB_HIP(hipGetLastError());
+    }
+    KDB_HIP(hipMemcpyAsync(h_ctr, d_ctr, 32, hipMemcpyDeviceToHost, s));
+    KDB_HIP(hipStreamSynchronize(s));
+    return KDB_OK;
+    };
+    rc = chain();
+    if (rc) {
+        (void)hipStreamSynchronize(s);
+        return rc;
+    }
+    // ---- the host side of the handle
+    if (bare) {
+        idx->h_levels.assign((size_t)idx->count + 1, 0);
+        idx->h_up_idx.assign((size_t)idx->count + 1, 0);
+    }
+    idx->h_levels.insert(idx->h_levels.end(), lv.begin(), lv.end());
+    idx->h_up_idx.insert(idx->h_up_idx.end(), up_new.begin(), up_new.end());
+    idx->up_slots = slots;
+    idx->count = new_count;
+    idx->entry = entry;
+    idx->max_level = max_level;
+    idx->has_graph = true;
+    if (out) {
+        out->nodes_added = nb;
+        out->forward_lists = kdb_add_plan_lists(steps.data(), nb);
+        out->reverse_appended = h_ctr[0];
+        out->reverse_pruned = h_ctr[1];
+        out->tied_nodes = h_ctr[2];
+        out->reverse_skipped = h_ctr[3];
+        out->entry = entry;
+        out->max_level = max_level;
+    }
+    return KDB_OK;
+}
+
+// Add (hnsw_index.go:472-809) for rows ALREADY uploaded at ids first_id .. first_id+n-1: see kektor_hip.h
+int kdb_add_graph(kdb_index *idx, uint32_t first_id, uint32_t n, const uint8_t *levels, uint32_t ef_construction, kdb_add_stats *out) {
+    const uint32_t efc = ef_construction ? ef_construction : idx->desc.ef_construction;
+    if (n == 0) {
+        if (out) {
+            *out = kdb_add_stats{};
+            out->entry = idx->entry;
+            out->max_level = idx->max_level;
+        }
+        return KDB_OK;
+    }
+    if (!levels || first_id != idx->count + 1 || (uint64_t)first_id + n - 1 > idx->cap) {
+        kdb_set_error("add: ids must continue at count+1 = %u and stay within capacity %u, levels must be given", idx->count + 1, idx->cap);
+        return KDB_ERR_INVALID;
+    }
+    int rc = refine_limits(idx, efc, "add");
+    if (rc) return rc;
+    if (idx->has_graph && idx->max_level >= 0 && idx->h_levels.size() != (size_t)idx->count + 1) {
+        kdb_set_error("add: the index holds a graph without its host-side level table");
+        return KDB_ERR_STATE;
+    }
+    KDB_HIP(hipDeviceSynchronize()); // walks of callers' streams may still read the lists this call rewrites
+    if (idx->desc.precision == KDB_PREC_F16) return add_impl<KDB_METRIC_L2, KDB_PREC_F16>(idx, first_id, n, levels, efc, out);
+    if (idx->desc.precision == KDB_PREC_I8) return add_impl<KDB_METRIC_COSINE, KDB_PREC_I8>(idx, first_id, n, levels, efc, out);
+    return idx->desc.metric == KDB_METRIC_COSINE ? add_impl<KDB_METRIC_COSINE, KDB_PREC_F32>(idx, first_id, n, levels, efc, out)
+                                                 : add_impl<KDB_METRIC_L2, KDB_PREC_F32>(idx, first_id, n, levels, efc, out);
 }
 
 // ... and the dispatch on metric and precision (nodes: live, unique, 1..count, not empty)

@@ -2023,6 +2023,21 @@ extern "C" int kdb_index_add_batch(kdb_index *idx, uint32_t first_id, uint32_t n
     return kdb_add_batch_ref(idx, first_id, n, levels, ef_construction);
 }
 
+extern "C" int kdb_index_add(kdb_index *idx, uint32_t first_id, uint32_t n, const uint8_t *levels, const kdb_add_params *params, kdb_add_stats *out) {
+    KDB_CHECK_IDX(idx);
+    if (params && params->flags) {
+        kdb_set_error("add: unknown flag");
+        return KDB_ERR_INVALID;
+    }
+    KdbWriteLock wl(idx); // excludes host-pointer calls in flight
+    // (graph_epoch: bumped by kdb_add_graph, and only when a new node has an upper level -- as kdb_index_append_nodes does it, so that
+    // the first search after a level-0 insert pays no rebuild of the derived upper-slot table; a refused call touches nothing)
+    KDB_HIP(hipSetDevice(idx->device));
+    KdbLaneGuard lane(idx, idx->stream);
+    if (lane.rc) return lane.rc;
+    return kdb_add_graph(idx, first_id, n, levels, params ? params->ef_construction : 0u, out);
+}
+
 extern "C" int kdb_index_refine(kdb_index *idx, const uint32_t *ids, uint32_t n, const kdb_refine_params *params, kdb_refine_stats *out) {
     KDB_CHECK_IDX(idx);
     if (params && params->flags) {

@@ -222,6 +222,17 @@ class HipIndex:
         lv = np.ascontiguousarray(levels, dtype=np.uint8)
         check(self.L.kdb_index_add_batch(self.h, int(first_id), lv.size, _ptr(lv), int(ef_construction), 1), "kdb_index_add_batch")
 
+    def add(self, first_id: int, levels, ef_construction: int = 0) -> dict:
+        """Add (hnsw_index.go:472-809), the sequential single insert, for rows already uploaded at first_id.. (kdb_index_add):
+        one node after another, each linked against the graph the nodes before it left; levels: one per new node, as drawn
+        (capped at maxLevel+1 on the device side of the call); -> the call's statistics"""
+        self._live()
+        lv = np.ascontiguousarray(levels, dtype=np.uint8)
+        p = _lib.AddParams(int(ef_construction), 0)
+        st = _lib.AddStats()
+        check(self.L.kdb_index_add(self.h, int(first_id), lv.size, _ptr(lv), C.byref(p), C.byref(st)), "kdb_index_add")
+        return {f: int(getattr(st, f)) for f, _ in _lib.AddStats._fields_}
+
     def refine(self, ids=None, ef_construction: int = 0, chunk_nodes: int = 0) -> dict:
         """GraphOptimizer.Refine (optimizer.go:288-464) on the device (kdb_index_refine): the lists of `ids` (None: every live
         node) are computed again against the graph as it is and committed together; -> the call's statistics"""
