@@ -569,7 +569,9 @@ KDB_API int kdb_cluster_debug_fail_next(kdb_cluster *c, uint32_t stage);
 
 /* MEASUREMENT HOOKS (probe.hip) -- what this device delivers on the two access patterns of the hot path, on the index's own row
  * array: a uniform random whole-row gather (16 lanes per row, best of four launch shapes) and one coalesced streaming pass.
- * which: 0 = the stored rows, 1 = the half-precision ranking copy.  *ms = duration of the best launch, *bytes = what it read.
+ * which: 0 = the stored rows, 1 = the half-precision ranking copy, 2 (kdb_probe_gather only) = the high walk plane of a float32
+ * cosine index of 768 columns (1536-byte rows; KDB_ERR_UNSUPPORTED until a planes walk has made the planes).
+ * *ms = duration of the best launch, *bytes = what it read.
  * bench.py reports its roofline fractions against these beside the nominal HBM peak.  Blocking.              */
 KDB_API int kdb_probe_gather(kdb_index *idx, int which, uint64_t n_reads, float *ms, uint64_t *bytes);
 KDB_API int kdb_probe_stream(kdb_index *idx, int which, float *ms, uint64_t *bytes);

@@ -37,11 +37,24 @@
 #endif
 // measurement build (make dbgs): where a walk's time goes
 #ifdef KDB_SEARCH_TIMERS
-#define KDB_T(x) x
+#define KDB_T(...) __VA_ARGS__
 #else
-#define KDB_T(x)
+#define KDB_T(...)
 #endif
 namespace kdbcore {
+
+// per-query counters of a walk (n_dist / n_hops: the reference's counts)
+struct QCtr {
+    uint32_t n_dist, n_hops, n_dropped;
+#ifdef KDB_SEARCH_TIMERS // measurement build (make dbgs): where a walk's time goes
+    uint32_t n_ins;
+    unsigned long long t_adj, t_dist, t_ins, t_pop, t_vis, t_upper, t_wait, t_pred;
+    // planes walk, level 0 (kdb_planes_trip): full-beam trips split into the wait for the high plane, its arithmetic and bound, the wait
+    // for the survivors' low plane and the exact arithmetic; trips of a beam that is not full (both planes in one round trip) as a whole
+    unsigned long long t_hi_wait, t_hi_math, t_lo_wait, t_lo_math, t_notfull;
+    uint32_t n_eval_hops, n_two_trips, n_trips, n_trips_lo; // hops with new neighbours, of those with more than 8; trips, of those with a second round trip
+#endif
+};
 
 struct WaveLds {
     float *q;          // query (f32 values, or packed int8)
@@ -161,23 +174,33 @@ __device__ __forceinline__ float4 kdb_plane_piece(uint32_t wh, uint32_t wh2, uin
 __device__ __forceinline__ float4 kdb_plane_piece_hi(uint32_t wh, uint32_t wh2) {
     return make_float4(kdb_perm_f(wh, wh, 0x05040c0cu), kdb_perm_f(wh, wh, 0x07060c0cu), kdb_perm_f(wh2, wh2, 0x05040c0cu), kdb_perm_f(wh2, wh2, 0x07060c0cu));
 }
-// RR rows against the query pieces yq (the lane's NCH pieces of the query, read from LDS once for both passes), cosine: element-to-lane,
-// element-to-accumulator and FMA order of kdb_row_partialR_f32 (piece i = 2j + u of the lane is words 2u, 2u + 1 of its j-th load).
-// HI: from the high plane alone.  The scheduling barrier after every piece keeps the unpacking next to its FMAs: left alone, the
-// scheduler unpacks every word of every row first and holds 4 registers per piece where the packed words need 2 (it spilled 170).
+// RR rows against the query pieces at yq (LDS: the lane's piece i is yq[16 i]), cosine: element-to-lane, element-to-accumulator and FMA
+// order of kdb_row_partialR_f32 (piece i = 2j + u of the lane is words 2u, 2u + 1 of its j-th load).  HI: from the high plane alone.
+// Registers decide how many walks a CU holds (kdb_search_minw), so nothing here may live longer than it must:
+//  * the query pieces are read from LDS piece by piece in both passes (the next piece is requested while this one is summed), not
+//    kept in 48 registers across the two round trips;
+//  * the packed words of piece i pass through an empty asm statement together with the row's accumulators: the unpacking of piece i
+//    cannot start before piece i - 1 is summed.  A scheduling barrier alone orders the machine scheduler, not the passes before it: they
+//    hoisted every v_perm of a pass to its top (4 registers per piece where the packed words need 2; 251 VGPRs spilled of 168).
+// With both, two rows per group and trip fit 168 registers with no scratch access between a trip's first plane load and its last store.
 template <int NCH, int RR, bool HI>
-__device__ __forceinline__ void kdb_planes_partial(const uint4 (&h)[RR][NCH / 2], const uint4 (&l)[RR][NCH / 2], const float4 (&yq)[NCH], float (&p)[RR]) {
+__device__ __forceinline__ void kdb_planes_partial(const uint4 (&h)[RR][NCH / 2], const uint4 (&l)[RR][NCH / 2], const float4 *yq, float (&p)[RR]) {
     float a[RR][4];
 #pragma unroll
     for (int r = 0; r < RR; r++) a[r][0] = a[r][1] = a[r][2] = a[r][3] = 0.f;
+    float4 yn = yq[0];
 #pragma unroll
     for (int i = 0; i < NCH; i++) {
-        const float4 y = yq[i];
+        const float4 y = yn;
+        if (i + 1 < NCH) yn = yq[16 * (i + 1)];
 #pragma unroll
         for (int r = 0; r < RR; r++) {
             const uint4 wh = h[r][i >> 1], wl = l[r][i >> 1];
-            const float4 x = HI ? ((i & 1) ? kdb_plane_piece_hi(wh.z, wh.w) : kdb_plane_piece_hi(wh.x, wh.y))
-                                : ((i & 1) ? kdb_plane_piece(wh.z, wh.w, wl.z, wl.w) : kdb_plane_piece(wh.x, wh.y, wl.x, wl.y));
+            uint32_t h0 = (i & 1) ? wh.z : wh.x, h1 = (i & 1) ? wh.w : wh.y, l0 = (i & 1) ? wl.z : wl.x, l1 = (i & 1) ? wl.w : wl.y;
+            // the piece's packed words pass through the accumulators' last values: no unpacking of piece i starts before piece i - 1 is summed
+            if (HI) asm volatile("" : "+v"(h0), "+v"(h1), "+v"(a[r][0]), "+v"(a[r][1]), "+v"(a[r][2]), "+v"(a[r][3]));
+            else asm volatile("" : "+v"(h0), "+v"(h1), "+v"(l0), "+v"(l1), "+v"(a[r][0]), "+v"(a[r][1]), "+v"(a[r][2]), "+v"(a[r][3]));
+            const float4 x = HI ? kdb_plane_piece_hi(h0, h1) : kdb_plane_piece(h0, h1, l0, l1);
             a[r][0] = __builtin_fmaf(y.x, x.x, a[r][0]);
             a[r][1] = __builtin_fmaf(y.y, x.y, a[r][1]);
             a[r][2] = __builtin_fmaf(y.z, x.z, a[r][2]);
@@ -203,7 +226,7 @@ __device__ __forceinline__ void kdb_planes_partial(const uint4 (&h)[RR][NCH / 2]
 // No compaction: a survivor stays in its 16-lane group; a rejected row's loads go to row 0 of the low plane (all zero, one cached
 // row) instead, so no load and no FMA is predicated per group -- nothing for the ISA gate to find.
 template <int NCH, int RR>
-__device__ __forceinline__ void kdb_planes_trip(const KdbView &v, const WaveLds &s, uint32_t base, uint32_t n, int g, int t, bool full, float neg_worst) {
+__device__ __forceinline__ void kdb_planes_trip(const KdbView &v, const WaveLds &s, uint32_t base, uint32_t n, int g, int t, bool full, float neg_worst KDB_T(, QCtr *tc)) {
     constexpr int NJ = NCH / 2;
     uint32_t rr[RR];
     size_t off[RR];
@@ -219,12 +242,12 @@ __device__ __forceinline__ void kdb_planes_trip(const KdbView &v, const WaveLds 
         for (int j = 0; j < NJ; j++) h[r][j] = hp[t + 16 * j];
         er[r] = full ? v.walk_err[id] : 0.f;
     }
-    float4 yq[NCH];
-#pragma unroll
-    for (int i = 0; i < NCH; i++) yq[i] = reinterpret_cast<const float4 *>(s.q)[t + 16 * i];
+    const float4 *yq = reinterpret_cast<const float4 *>(s.q) + t;
     bool surv[RR];
+    KDB_T(unsigned long long tp0 = __builtin_readcyclecounter(); if (tc) tc->n_trips++;)
     if (full) {
         float ph[RR];
+        KDB_T(asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); if (tc) { const unsigned long long c = __builtin_readcyclecounter(); tc->t_hi_wait += c - tp0; tp0 = c; })
         kdb_planes_partial<NCH, RR, true>(h, h, yq, ph);
         bool any = false;
 #pragma unroll
@@ -233,6 +256,7 @@ __device__ __forceinline__ void kdb_planes_trip(const KdbView &v, const WaveLds 
             surv[r] = rr[r] < n && !(bound <= neg_worst && bound >= -3.0e38f); // (uniform in the 16-lane group)
             any = any || surv[r];
         }
+        KDB_T(if (tc) { const unsigned long long c = __builtin_readcyclecounter(); tc->t_hi_math += c - tp0; tp0 = c; })
         if (__ballot(any) == 0ull) { // wave-uniform: nobody needs a low plane
 #pragma unroll
             for (int r = 0; r < RR; r++)
@@ -250,24 +274,26 @@ __device__ __forceinline__ void kdb_planes_trip(const KdbView &v, const WaveLds 
         for (int j = 0; j < NJ; j++) l[r][j] = lp[t + 16 * j];
     }
     float p[RR];
+    KDB_T(if (full) { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); if (tc) { const unsigned long long c = __builtin_readcyclecounter(); tc->t_lo_wait += c - tp0; tp0 = c; tc->n_trips_lo++; } })
     kdb_planes_partial<NCH, RR, false>(h, l, yq, p);
 #pragma unroll
     for (int r = 0; r < RR; r++) {
         const float key = kdb_key_from_raw<KDB_PREC_F32, KDB_METRIC_COSINE>(kdb_reduce16(p[r]));
         if (rr[r] < n && t == 0) s.nb_d[rr[r]] = surv[r] ? kdb_sane_key(key) : INFINITY;
     }
+    KDB_T(if (tc) { const unsigned long long c = __builtin_readcyclecounter(); if (full) tc->t_lo_math += c - tp0; else tc->t_notfull += c - tp0; })
 }
 
 // PL = 1 (planes kernels: float32, cosine, v.ld == 64 * NCH, NCH even): the rows are read from the walk planes -- `full` (wave-uniform:
 // the beam holds ef results) and `worst` say which candidates may be rejected from the high plane alone (kdb_planes_trip)
 template <int PREC, int METRIC, int NCH = 0, int RMAX = 0, int PL = 0>
-__device__ __forceinline__ void compute_dists(const KdbView &v, const WaveLds &s, uint32_t n, float qnorm, bool full = false, float worst = INFINITY) {
+__device__ __forceinline__ void compute_dists(const KdbView &v, const WaveLds &s, uint32_t n, float qnorm, bool full = false, float worst = INFINITY KDB_T(, QCtr *tc = nullptr)) {
     const int lane = kdb_lane();
     const int g = lane >> 4, t = lane & 15;
     if constexpr (PL != 0) { // the trips of the float32 branch below: 4 * R rows, 5 .. 8, 1 .. 4
         static_assert(PREC == KDB_PREC_F32 && METRIC == KDB_METRIC_COSINE && NCH > 0 && NCH <= 12 && NCH % 2 == 0 && RMAX == 0, "walk planes: float32 cosine, ld == 64 * NCH");
-        // (768 columns: two rows per group and trip, not the float32 branch's three -- two planes of three rows, the query pieces and the
-        // walk's own state do not fit 256 registers; most hops bring fewer than nine new neighbours and take the two-row trip anyway)
+        // (768 columns: two rows per group and trip, not the float32 branch's three -- two planes of two rows are 96 registers of the 168
+        // the one-slot kernel is compiled for; 72 % of the hops bring fewer than nine new neighbours and take one trip anyway)
         constexpr int R = 2;
         // (both are wave-uniform; told so, the branch on `full` is a scalar one and no load or FMA below runs under an exec mask)
         const float neg_worst = unif(-worst);
@@ -275,13 +301,13 @@ __device__ __forceinline__ void compute_dists(const KdbView &v, const WaveLds &s
         for (uint32_t base = 0; base < n;) {
             const uint32_t left = n - base;
             if (left > 4u * (R - 1) || R == 1) {
-                kdb_planes_trip<NCH, R>(v, s, base, n, g, t, full, neg_worst);
+                kdb_planes_trip<NCH, R>(v, s, base, n, g, t, full, neg_worst KDB_T(, tc));
                 base += 4u * R;
             } else if (left > 4u) {
-                kdb_planes_trip<NCH, 2>(v, s, base, n, g, t, full, neg_worst);
+                kdb_planes_trip<NCH, 2>(v, s, base, n, g, t, full, neg_worst KDB_T(, tc));
                 base += 8u;
             } else {
-                kdb_planes_trip<NCH, 1>(v, s, base, n, g, t, full, neg_worst);
+                kdb_planes_trip<NCH, 1>(v, s, base, n, g, t, full, neg_worst KDB_T(, tc));
                 base += 4u;
             }
         }
@@ -1356,13 +1382,6 @@ struct NrListT {
 };
 using NrList = NrListT<false>;
 
-struct QCtr {
-    uint32_t n_dist, n_hops, n_dropped;
-#ifdef KDB_SEARCH_TIMERS // measurement build (make dbgs): where a walk's time goes
-    uint32_t n_ins;
-    unsigned long long t_adj, t_dist, t_ins, t_pop, t_vis, t_upper, t_wait, t_pred;
-#endif
-};
 
 // searchLayerUnlocked (hnsw_index.go:2351-2611) on one layer; leaves the result in the beam.
 // The entry point's distance, when the caller already has it: the entry point of layer l-1 is the nearest result of layer l
@@ -1742,7 +1761,8 @@ __device__ void search_layer(const KdbView &v, const WaveLds &s, BeamT &b, VisT 
         KDB_T(const unsigned long long tq1 = __builtin_readcyclecounter();)
         // (PL: a candidate the high plane proves "not < worst" while the beam is full comes back as +Inf -- not in `pass` below, and
         // nothing after `pass` looks at a candidate outside it; n_dist counts it like any other)
-        compute_dists<PREC, METRIC, NCH, 0, PL>(v, s, n, qnorm, !(b.n_res < ef), b.worst);
+        KDB_T(if (level == 0) { ctr.n_eval_hops++; if (n > 8u) ctr.n_two_trips++; })
+        compute_dists<PREC, METRIC, NCH, 0, PL>(v, s, n, qnorm, !(b.n_res < ef), b.worst KDB_T(, level == 0 ? &ctr : nullptr));
         ctr.n_dist += n;
         const bool my_nr = ((delw >> (my_id & 31)) & 1u) != 0;
         const float my_d = lds_f32_or(s.nb_d, (uint32_t)lane, n, INFINITY);

@@ -108,15 +108,20 @@ int run_gather(const unsigned char *rows, uint32_t row_bytes, uint32_t count, ui
 
 } // namespace
 
-// which: 0 = the stored rows, 1 = the half-precision ranking copy (float32 indexes that have been scanned).  Reads about n_reads
-// random rows in each of several launch shapes (rows in flight per wave x waves per SIMD) and reports the BEST: *ms and the
-// bytes that launch read.  Blocking.
+// which: 0 = the stored rows, 1 = the half-precision ranking copy (float32 indexes that have been scanned), 2 = the high walk plane
+// (1536-byte rows at 768 columns: the granule of the planes walk's first round trip; KDB_ERR_UNSUPPORTED until a planes walk has
+// made the planes).  Reads about n_reads random rows in each of several launch shapes (rows in flight per wave x waves
+// per SIMD) and reports the BEST: *ms and the bytes that launch read.  Blocking.
 extern "C" int kdb_probe_gather(kdb_index *idx, int which, uint64_t n_reads, float *ms, uint64_t *bytes) {
     if (!idx || !ms || !bytes) return KDB_ERR_INVALID;
     std::lock_guard<std::mutex> lk(idx->mu);
     KDB_HIP(hipSetDevice(idx->device));
-    const unsigned char *rows = reinterpret_cast<const unsigned char *>(which ? (const void *)idx->d_rows16 : (const void *)idx->d_rows);
-    const uint32_t row_bytes = which ? idx->ld16 * 2u : idx->ld * (uint32_t)idx->elem;
+    if (which < 0 || which > 2) {
+        kdb_set_error("probe_gather: which is 0 (rows), 1 (half-precision copy) or 2 (high walk plane)");
+        return KDB_ERR_INVALID;
+    }
+    const unsigned char *rows = reinterpret_cast<const unsigned char *>(which == 2 ? (const void *)idx->d_walk_hi : which ? (const void *)idx->d_rows16 : (const void *)idx->d_rows);
+    const uint32_t row_bytes = which == 2 ? idx->ld * 2u : which ? idx->ld16 * 2u : idx->ld * (uint32_t)idx->elem;
     if (!rows || idx->count == 0 || (row_bytes & 255u)) {
         kdb_set_error("probe_gather: no such row array, no rows, or rows that are not whole 256-byte pieces");
         return KDB_ERR_UNSUPPORTED;

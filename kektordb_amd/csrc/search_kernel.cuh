@@ -39,7 +39,14 @@ __device__ __forceinline__ size_t q_lds_bytes(uint32_t ld) {
 #define KDB_F32_MINW6 4 // 384-d rows are latency/issue-bound: occupancy over rows in flight (measured +16 %)
 #endif
 #ifndef KDB_F32_MINW
-#define KDB_F32_MINW 2 // measured: 2 waves/SIMD without spills equal 3 at ef=64 and win 4-5 % at ef 128-200
+#define KDB_F32_MINW 2 // the float32-row kernels (bandwidth-bound: 0.93-0.95 of the HBM peak); measured on them: 2 waves/SIMD without
+                       // spills equal 3 at ef=64 and win 4-5 % at ef 128-200.  Says nothing about the planes kernels (KDB_PLANES_MINW)
+#endif
+#ifndef KDB_PLANES_MINW
+#define KDB_PLANES_MINW 3 // the planes kernel with the one-slot beam (ef <= 64): 12 walks per CU instead of 8.  It is bound by the
+                          // bytes it keeps in flight, not by HBM bandwidth; measured at 1M x 768, ef 60, 32768 queries, alternating runs:
+                          // 7.31 (parent) / 6.96 (this source at 2 waves/SIMD, no spills) / 6.38 ms (3 waves/SIMD, 47 VGPRs spilled
+                          // outside the hop loop's row trips) -- DESIGN 5.1
 #endif
 #ifndef KDB_WIDE4_MINW
 #define KDB_WIDE4_MINW 4 // waves per SIMD the four-wave kernels are compiled for (0 = as the one-wave kernels): measured 1M x 768,
@@ -61,8 +68,12 @@ __device__ __forceinline__ size_t q_lds_bytes(uint32_t ld) {
 // waves per SIMD a kernel is compiled for (= its VGPR budget: 512 / waves).  The multi-wave kernels must not spill: this toolchain
 // places the reload of a VGPR spilled across a divergent region before the exec restore of the join block (scripts/tools/isa_check.py),
 // and long rows (more than 1024 columns: 24 sixteen-byte pieces per lane and row) do not fit 128 registers beside the walk's state.
-template <int PREC, int NCH, int WIDE>
+template <int PREC, int NCH, int WIDE, int PL = 0, int BS = 0>
 constexpr int kdb_search_minw() {
+    // planes kernels: only a kernel whose LDS footprint lets 12 walks fit a CU takes the three-wave budget -- the one-slot beam (11.8 KB
+    // per walk).  The two-slot beam would qualify up to ef 100 only (from ef 101 its hash is 4096 entries: 7 walks per CU) and the
+    // four-slot beam never: LDS holds them at 8 or fewer, they keep two waves (210 / 217 VGPRs, no spills)
+    if (PL != 0 && BS == 1 && WIDE == 1) return KDB_PLANES_MINW;
     if (WIDE == 4 && KDB_WIDE4_MINW) return NCH > 16 ? KDB_WIDE4_MINW_LONG : NCH == 0 ? (KDB_WIDE4_MINW > 3 ? 3 : KDB_WIDE4_MINW) : KDB_WIDE4_MINW; // (any-width rows: two registers short at 128)
     if (WIDE == 2 && NCH > 16) return 2;
     if (PREC == KDB_PREC_I8) return 4;
@@ -73,7 +84,7 @@ constexpr int kdb_search_minw() {
 template <int PREC, int METRIC, int NCH>
 constexpr bool kdb_planes_kernel() { return PREC == KDB_PREC_F32 && METRIC == KDB_METRIC_COSINE && NCH == 12; } // (768 columns: kdb_walk_planes_shape)
 template <int PREC, int METRIC, int NCH, int BS, int VIS, int WIDE = 1, int PL = 0>
-__global__ void __launch_bounds__(64 * WIDE, (kdb_search_minw<PREC, NCH, WIDE>()))
+__global__ void __launch_bounds__(64 * WIDE, (kdb_search_minw<PREC, NCH, WIDE, PL, BS>()))
 hnsw_search_kernel(KdbView v, const void *__restrict__ queries, const float *__restrict__ qnorms, uint32_t raw, uint32_t B,
                    uint32_t k, uint32_t ef, const uint32_t *__restrict__ allow, KdbMultiAllow ma, uint32_t entry,
                    uint32_t beam_cap, uint32_t nr_cap, uint32_t vis_size, uint32_t *visited_pool, uint32_t *work,
@@ -257,7 +268,7 @@ hnsw_search_kernel(KdbView v, const void *__restrict__ queries, const float *__r
         if (ma.done_flags && !requeue) kdb_publish_done(ma.done_flags + qi, ma.done_gen); // (a requeued query is published by the second pass)
         tot_tied += b.tied;
         if (requeue) ctr.n_dist = ctr.n_hops = ctr.n_dropped = 0u;
-        KDB_T(if (lane == 0 && qi < 64u) printf("q %u waves %d: hops %u dist %u inserts %u | cycles: total %llu upper-layers %llu | level 0: pop %llu list %llu visited %llu rows %llu predict+post %llu predict+post+insert %llu wait-for-wave-1 %llu | wave 1: visit %llu cycles, hint hits %u\n", qi, WIDE, ctr.n_hops, ctr.n_dist, ctr.n_ins, __builtin_readcyclecounter() - tq_start, ctr.t_upper, ctr.t_pop, ctr.t_adj, ctr.t_vis, ctr.t_dist, ctr.t_pred, ctr.t_ins, ctr.t_wait, WIDE > 1 ? *reinterpret_cast<unsigned long long *>(s.ctl + 12) : 0ull, WIDE > 1 ? s.ctl[14] : 0u);)
+        KDB_T(if (lane == 0 && qi < 64u) printf("q %u waves %d: hops %u dist %u inserts %u | cycles: total %llu upper-layers %llu | level 0: pop %llu list %llu visited %llu rows %llu predict+post %llu predict+post+insert %llu wait-for-wave-1 %llu | wave 1: visit %llu cycles, hint hits %u | planes %d: level-0 hops with new neighbours %u, with more than 8 %u, trips %u, with a low-plane trip %u, cycles high-wait %llu high-math %llu low-wait %llu low-math %llu not-full %llu\n", qi, WIDE, ctr.n_hops, ctr.n_dist, ctr.n_ins, __builtin_readcyclecounter() - tq_start, ctr.t_upper, ctr.t_pop, ctr.t_adj, ctr.t_vis, ctr.t_dist, ctr.t_pred, ctr.t_ins, ctr.t_wait, WIDE > 1 ? *reinterpret_cast<unsigned long long *>(s.ctl + 12) : 0ull, WIDE > 1 ? s.ctl[14] : 0u, PL, ctr.n_eval_hops, ctr.n_two_trips, ctr.n_trips, ctr.n_trips_lo, ctr.t_hi_wait, ctr.t_hi_math, ctr.t_lo_wait, ctr.t_lo_math, ctr.t_notfull);)
         tot_dist += ctr.n_dist;
         tot_hops += ctr.n_hops;
         tot_dropped += ctr.n_dropped;

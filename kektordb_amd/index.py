@@ -424,10 +424,11 @@ class HipIndex:
     def sync(self):
         check(self.L.kdb_index_sync(self.h), "sync")
 
-    def probe_gather(self, n_reads: int = 4_000_000, shadow: bool = False):
-        """measurement hook: GB/s of a uniform random whole-row gather on this index's rows (or its half-precision copy)"""
+    def probe_gather(self, n_reads: int = 4_000_000, shadow: bool = False, walk_hi: bool = False):
+        """measurement hook: GB/s of a uniform random whole-row gather on this index's rows (or its half-precision copy, or --
+        walk_hi -- the high walk plane: 1536-byte rows at 768 columns, KDB_ERR_UNSUPPORTED until a planes walk has made the planes)"""
         ms, nbytes = C.c_float(), C.c_uint64()
-        check(self.L.kdb_probe_gather(self.h, 1 if shadow else 0, n_reads, C.byref(ms), C.byref(nbytes)), "kdb_probe_gather")
+        check(self.L.kdb_probe_gather(self.h, 2 if walk_hi else 1 if shadow else 0, n_reads, C.byref(ms), C.byref(nbytes)), "kdb_probe_gather")
         return nbytes.value / (ms.value * 1e-3) / 1e9
 
     def poison_lds(self, pattern: int = 0):
