@@ -28,6 +28,13 @@
  *                           selected node re-linked against the graph as the call found it
  *   kdb_index_vacuum        GraphOptimizer.Vacuum (optimizer.go:133-277): nodes with links to deleted nodes found and re-linked,
  *                           the entry point re-elected, the deleted nodes' lists and rows cleared
+ *   kdb_index_decode_rows   GetNodeData(...).Vector (hnsw_index.go:2909-2959) / the vectors of Engine.VGetMany: stored rows as the float32
+ *                           vectors the reference hands to its callers (float16 widened, int8 through Quantizer.Dequantize,
+ *                           pkg/core/hnsw/quantizer.go:181-198)
+ *   kdb_search_by_id        VSearchWithScores(index, VGetMany(ids)[i].Vector, k) for a page of ids -- the loop of
+ *                           Gardener.findRedundantClusters (pkg/cognitive/gardener.go:803-869; again at :915, :1362, :2348) --
+ *                           as ONE call in which the rows never leave the device
+ *   kdb_flat_scan_by_id     the same in front of the exact scan (BruteForceIndex.SearchWithScores)
  *   kdb_merge_topk          the merge step of the id-range shard (no reference
  *                           counterpart -- the reference is single process)
  *   kdb_sharded_search_batch  the same path over every GPU of a node from ONE process: fan-out,
@@ -308,6 +315,51 @@ KDB_API int kdb_flat_scan_groups_dev(kdb_index *idx, const float *d_queries, uin
                              const uint32_t *group_offsets, const uint64_t *d_allow_lists, uint64_t words_per_list,
                              uint64_t max_total_allowed, uint32_t flags, uint32_t *d_out_ids, float *d_out_dist,
                              uint32_t *d_out_count, void *stream);
+
+/* GetNodeData(id).Vector (hnsw_index.go:2909-2959), the vectors Engine.VGetMany returns, for n ids: out[i] = the stored row of
+ * ids[i] as `dim` float32 (out: [n][dim], dense, no padding) --
+ *   float32   the stored row, bit for bit (a cosine row stays normalised, as stored);
+ *   float16   every half widened (exact);
+ *   int8      Quantizer.Dequantize (quantizer.go:181-198): (float32(v) / 127) * AbsMax, in that order, in correctly rounded
+ *             float32; AbsMax == 0 (untrained): zeros.
+ * An id that is 0, above count, or marked deleted is "not found" (:2921-2931): its row is zeros and out_found[i] = 0.  out_found:
+ * NULL or n BYTES (uint8_t), 1 = found.  ids may repeat.  Every id is range-checked before an address is formed from it.  One
+ * gather kernel (by_id.hip).  The host-pointer form stages through the index in pieces of at most 64 MiB of vectors.            */
+KDB_API int kdb_index_decode_rows(kdb_index *idx, const uint32_t *ids, uint32_t n, float *out, uint8_t *out_found);
+KDB_API int kdb_index_decode_rows_dev(kdb_index *idx, const uint32_t *d_ids, uint32_t n, float *d_out, uint8_t *d_out_found, void *stream);
+
+/* Search BY STORED ID -- "more like this".  Gardener.findRedundantClusters (pkg/cognitive/gardener.go:803-869) pages 500 ids with
+ * VGetIDsByCursor, reads them with VGetMany and runs VSearchWithScores(indexName, vData.Vector, 10) for each (the same loop at
+ * :915, :1362 and :2348): every query is a vector that was just read OUT of the index.  Here the page is one call and an id is what
+ * crosses the bus.
+ * DEFINITION: query b is the vector kdb_index_decode_rows gives for ids[b]; the answer -- ids, distance bits, out_count, the
+ * per-query trace (kdb_search_set_trace) and kdb_counters -- is exactly that of kdb_search_batch[_dev] for that float32 vector with
+ * the same (k, ef, allow list, flags).  The call IS that composition: the rows are decoded into scratch of their own and the
+ * existing walk runs on them, query prep included (searchInternal prepares GetNodeData's vector like any other, :404-434: a
+ * float32 cosine row is normalised again, an int8 row quantised again) -- KDB_SEARCH_PREPARED is therefore refused (KDB_ERR_INVALID).
+ * A source id that is not found (0, above count, deleted) gets out_count[b] = 0 and a zeroed id row and is never walked (inside,
+ * it is a query that is not finite: "Conventions"); the other queries are unaffected.  A stored row that holds a NaN or an
+ * infinity is such a query too.  A batch of not-found ids only: KDB_OK, every count 0.
+ * Flags: KDB_SEARCH_NEEDS_REFINE, KDB_SEARCH_FAIL_ON_DROP (kdb_search_by_id only), KDB_SEARCH_DIST_F64 (int8 only),
+ * KDB_SEARCH_TIE_FLAG, KDB_SEARCH_HEAP_ORDER, and
+ *   KDB_BY_ID_DROP_SELF   a stored row's nearest neighbour is itself.  The call runs with k + 1 and the caller's [B][k] arrays
+ *                         receive that answer WITHOUT the entry whose id is ids[b] (there is at most one), or -- when it is not
+ *                         among them, e.g. the allow list excludes it -- without the LAST entry if all k + 1 came back.  Order
+ *                         and distance bits are otherwise those of the k + 1 call, out_count is adjusted (bit 31 kept), the trace
+ *                         and the counters are those of the k + 1 call.  kdb_flat_scan_by_id: k <= 1023, else KDB_ERR_INVALID.
+ * kdb_search_by_id (host pointers) takes turns on the index's staging buffer like kdb_distance_batch, synchronises once and is
+ * never combined with other callers' queries; kdb_flat_scan_by_id[_dev] is the same composition in front of kdb_flat_scan_batch
+ * (k <= 1024).  The grouped scan, the multi-list walk and the sharded entry points have no by-id form.                          */
+#define KDB_BY_ID_DROP_SELF (1u << 8)
+KDB_API int kdb_search_by_id(kdb_index *idx, const uint32_t *ids, uint32_t B, uint32_t k, uint32_t ef, const uint64_t *allow_bits,
+                             uint32_t flags, uint32_t *out_ids, float *out_dist, uint32_t *out_count);
+KDB_API int kdb_search_by_id_dev(kdb_index *idx, const uint32_t *d_ids, uint32_t B, uint32_t k, uint32_t ef,
+                                 const uint64_t *d_allow_bits, uint32_t flags, uint32_t *d_out_ids, float *d_out_dist,
+                                 uint32_t *d_out_count, void *stream);
+KDB_API int kdb_flat_scan_by_id(kdb_index *idx, const uint32_t *ids, uint32_t B, uint32_t k, const uint64_t *allow_bits,
+                                uint32_t flags, uint32_t *out_ids, float *out_dist, uint32_t *out_count);
+KDB_API int kdb_flat_scan_by_id_dev(kdb_index *idx, const uint32_t *d_ids, uint32_t B, uint32_t k, const uint64_t *d_allow_bits,
+                                    uint32_t flags, uint32_t *d_out_ids, float *d_out_dist, uint32_t *d_out_count, void *stream);
 
 /* B queries x C candidate ids each (ids[B][C], id 0 = skip -> +inf): raw accumulates out[B][C].   */
 KDB_API int kdb_distance_batch(kdb_index *idx, const float *queries, uint32_t B, const uint32_t *ids, uint32_t C,

@@ -208,6 +208,32 @@ class Index {
             for (uint32_t i = 0; i < cnt[b]; i++) out[b].push_back({ids[(size_t)b * k + i], score(dist, (size_t)b * k + i)});
         return out;
     }
+    // GetNodeData(id).Vector (hnsw_index.go:2909-2959) for every id, as Engine.VGetMany reads them: ids.size() x Dim() floats, row-major
+    // (float16 widened, int8 dequantised); found (optional): one byte per id, 0 = no such live node (its row is zeros)
+    std::vector<float> GetVectors(const std::vector<uint32_t> &ids, std::vector<uint8_t> *found = nullptr) const {
+        std::vector<float> out(ids.size() * (size_t)dim_);
+        if (found) found->assign(ids.size(), 0);
+        if (!h_ || ids.empty()) return out;
+        check(kdb_index_decode_rows(h_, ids.data(), (uint32_t)ids.size(), out.data(), found ? found->data() : nullptr), "decode_rows");
+        return out;
+    }
+    // One page of the Gardener's loop (pkg/cognitive/gardener.go:803-869: VGetMany, then VSearchWithScores with every vData.Vector) as one
+    // call: results[i] is what SearchWithScores(GetVectors({ids[i]}), k, allowList, efSearch) returns -- the rows never leave the device.
+    // An id that is not found gets an empty list; dropSelf: without the id itself.  Empty lists on any error, like SearchWithScores.
+    std::vector<std::vector<SearchResult>> SearchSimilar(const std::vector<uint32_t> &ids, int k, int efSearch, const AllowList *allowList = nullptr,
+                                                         bool dropSelf = false) const {
+        const uint32_t B = (uint32_t)ids.size();
+        std::vector<std::vector<SearchResult>> out(B);
+        if (!h_ || k <= 0 || B == 0) return out;
+        std::vector<uint32_t> rid((size_t)B * k), cnt(B);
+        DistBuf dist((size_t)B * k, wide());
+        int rc = kdb_search_by_id(h_, ids.data(), B, (uint32_t)k, (uint32_t)(efSearch > 0 ? efSearch : 0), allowList ? allowList->words.data() : nullptr,
+                                  flags() | (dropSelf ? (uint32_t)KDB_BY_ID_DROP_SELF : 0u), rid.data(), dist.ptr(), cnt.data());
+        if (rc) return out; // ":356-359": log and return []
+        for (uint32_t b = 0; b < B; b++)
+            for (uint32_t i = 0; i < cnt[b]; i++) out[b].push_back({rid[(size_t)b * k + i], score(dist, (size_t)b * k + i)});
+        return out;
+    }
     kdb_index *handle() const { return h_; }
     // concurrent kdb_search_batch calls of a few queries share launches inside the library (kektor_hip.h, "Conventions"): a
     // batcher in front of this index passes unfiltered one-query calls through

@@ -27,6 +27,7 @@ ABI_SYMBOLS = [
     "kdb_sharded_search_batch", "kdb_sharded_flat_scan_batch", "kdb_index_compress", "kdb_index_get_quantizer", "kdb_index_add_batch", "kdb_merge_topk_packed_f64_dev",
     "kdb_cluster_comm_info", "kdb_cluster_debug_fail_next", "kdb_index_reserve", "kdb_index_drop_f16_shadow", "kdb_probe_gather", "kdb_probe_stream", "kdb_probe_poison_lds", "kdb_index_caller_stats", "kdb_merge_topk_f64", "kdb_index_refine",
     "kdb_index_vacuum", "kdb_index_dead_link_scan", "kdb_index_drop_walk_planes", "kdb_index_add",
+    "kdb_index_decode_rows", "kdb_index_decode_rows_dev", "kdb_search_by_id", "kdb_search_by_id_dev", "kdb_flat_scan_by_id", "kdb_flat_scan_by_id_dev",
 ]
 
 
@@ -141,6 +142,12 @@ def load():
     L.kdb_flat_scan_batch.argtypes = [vp, vp, u32, u32, vp, u32, vp, vp, vp]
     L.kdb_flat_scan_batch_dev.argtypes = [vp, vp, u32, u32, vp, u32, vp, vp, vp, vp]
     L.kdb_distance_batch.argtypes = [vp, vp, u32, vp, u32, u32, vp]
+    L.kdb_index_decode_rows.argtypes = [vp, vp, u32, vp, vp]
+    L.kdb_index_decode_rows_dev.argtypes = [vp, vp, u32, vp, vp, vp]
+    L.kdb_search_by_id.argtypes = [vp, vp, u32, u32, u32, vp, u32, vp, vp, vp]
+    L.kdb_search_by_id_dev.argtypes = [vp, vp, u32, u32, u32, vp, u32, vp, vp, vp, vp]
+    L.kdb_flat_scan_by_id.argtypes = [vp, vp, u32, u32, vp, u32, vp, vp, vp]
+    L.kdb_flat_scan_by_id_dev.argtypes = [vp, vp, u32, u32, vp, u32, vp, vp, vp, vp]
     L.kdb_distance_batch_dev.argtypes = [vp, vp, u32, vp, u32, u32, vp, vp]
     L.kdb_index_build.argtypes = [vp, u32, C.POINTER(BuildParams)]
     L.kdb_index_add_batch.argtypes = [vp, u32, u32, vp, u32, u32]

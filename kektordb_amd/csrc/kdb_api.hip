@@ -130,6 +130,8 @@ static void lane_store(kdb_index *idx) { // the current lane's buffers may have 
     l.d_work = idx->d_work;
     l.d_tie = idx->d_tie;
     l.tie_bytes = idx->tie_bytes;
+    l.d_byid = idx->d_byid;
+    l.byid_bytes = idx->byid_bytes;
 }
 static void lane_load(kdb_index *idx, int li) {
     const kdb_lane &l = idx->lanes[li];
@@ -145,6 +147,8 @@ static void lane_load(kdb_index *idx, int li) {
     idx->d_work = l.d_work;
     idx->d_tie = l.d_tie;
     idx->tie_bytes = l.tie_bytes;
+    idx->d_byid = l.d_byid;
+    idx->byid_bytes = l.byid_bytes;
 }
 
 int kdb_lane_acquire(kdb_index *idx, hipStream_t s) {
@@ -248,6 +252,20 @@ static int ensure_qbuf(kdb_index *idx, size_t bytes) {
     }
     KDB_HIP(hipMalloc(&idx->d_qbuf, grown(bytes)));
     idx->qbuf_bytes = grown(bytes);
+    return KDB_OK;
+}
+
+static int ensure_byid(kdb_index *idx, size_t bytes) {
+    if (idx->byid_bytes >= bytes) return KDB_OK;
+    if (idx->d_byid) {
+        kdb_close_session(idx); // (an open launch would sit out its 0.5 s device-side safety under this synchronisation: closing it needs idx->mu, which this thread holds)
+        KDB_HIP(hipDeviceSynchronize()); // growth is rare; work of callers' streams may still use the old buffer
+        KDB_HIP(hipFree(idx->d_byid));
+        idx->d_byid = nullptr;
+        idx->byid_bytes = 0;
+    }
+    KDB_HIP(hipMalloc(&idx->d_byid, grown(bytes)));
+    idx->byid_bytes = grown(bytes);
     return KDB_OK;
 }
 
@@ -394,7 +412,7 @@ extern "C" void kdb_index_destroy(kdb_index *idx) {
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     for (kdb_lane &l : idx->lanes) {
-        void *lb[] = {l.d_visited, l.d_scratch, l.d_qbuf, l.d_gentry, l.d_work, l.d_tie};
+        void *lb[] = {l.d_visited, l.d_scratch, l.d_qbuf, l.d_gentry, l.d_work, l.d_tie, l.d_byid};
         for (void *b : lb)
             if (b) (void)hipFree(b);
         if (l.done) (void)hipEventDestroy(l.done);
@@ -1994,6 +2012,228 @@ extern "C" int kdb_distance_batch(kdb_index *idx, const float *queries, uint32_t
     lk.unlock();
     if (rc) return rc;
     KDB_HIP(hipMemcpyAsync(out, d_out, (size_t)B * C * 4, hipMemcpyDeviceToHost, s));
+    KDB_HIP(hipStreamSynchronize(s));
+    return KDB_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Stored rows as queries (by_id.hip): the Gardener's "more like this" loop (pkg/cognitive/gardener.go:803-869 pages ids, reads
+// their vectors with VGetMany and searches with each) without the rows leaving HBM.  A COMPOSITION: the source rows are decoded to
+// float32 -- the vector GetNodeData returns (hnsw_index.go:2909-2959) -- into a buffer of the call's scratch lane that neither the
+// walk nor the scan uses (d_byid), then search_dev_locked / flat_dev_locked run unchanged on that buffer, query prep included.
+// ---------------------------------------------------------------------------------------------
+static int by_id_dev_locked(kdb_index *idx, bool flat, const uint32_t *d_ids, uint32_t B, uint32_t k, uint32_t ef, const uint64_t *d_allow_bits,
+                            uint32_t flags, uint32_t *d_out_ids, float *d_out_dist, uint32_t *d_out_count, hipStream_t s) {
+    const char *who = flat ? "flat_scan_by_id" : "search_by_id";
+    if (B == 0) return KDB_OK;
+    if (k == 0) {
+        kdb_set_error("%s: k must be >= 1", who);
+        return KDB_ERR_INVALID;
+    }
+    if (flags & KDB_SEARCH_PREPARED) {
+        kdb_set_error("%s: KDB_SEARCH_PREPARED is not accepted (a decoded row goes through the normal query prep, as GetNodeData's vector does in the reference)", who);
+        return KDB_ERR_INVALID;
+    }
+    const bool drop = (flags & KDB_BY_ID_DROP_SELF) != 0;
+    const uint32_t inner = flags & ~(uint32_t)KDB_BY_ID_DROP_SELF;
+    if (drop && (k == 0xffffffffu || (flat && k + 1u > KDB_FLAT_MAX_K))) {
+        kdb_set_error("%s: KDB_BY_ID_DROP_SELF runs the call with k + 1 = %llu, above the limit of %u", who, (unsigned long long)k + 1u, flat ? KDB_FLAT_MAX_K : 0xffffffffu);
+        return KDB_ERR_INVALID;
+    }
+    if ((flags & KDB_SEARCH_DIST_F64) && idx->desc.precision != KDB_PREC_I8) {
+        kdb_set_error("%s: KDB_SEARCH_DIST_F64 applies to int8 indexes (the other precisions compute float32 distances)", who);
+        return KDB_ERR_INVALID;
+    }
+    const uint32_t kin = drop ? k + 1u : k;
+    const size_t db = (flags & KDB_SEARCH_DIST_F64) ? 8 : 4;
+    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    const size_t o_found = al((size_t)B * idx->desc.dim * 4), o_ids = o_found + al(B), o_dist = o_ids + al(drop ? (size_t)B * kin * 4 : 0),
+                 o_cnt = o_dist + al(drop ? (size_t)B * kin * db : 0), total = o_cnt + al(drop ? (size_t)B * 4 : 0);
+    int rc = ensure_byid(idx, total);
+    if (rc) return rc;
+    unsigned char *const p = reinterpret_cast<unsigned char *>(idx->d_byid);
+    float *const d_q = reinterpret_cast<float *>(p);
+    uint8_t *const d_found = p + o_found;
+    uint32_t *const i_ids = drop ? reinterpret_cast<uint32_t *>(p + o_ids) : d_out_ids;
+    float *const i_dist = drop ? reinterpret_cast<float *>(p + o_dist) : d_out_dist;
+    uint32_t *const i_cnt = drop ? reinterpret_cast<uint32_t *>(p + o_cnt) : d_out_count;
+    // A source that is not found (id 0, above count, deleted) must get no results.  Graph search: its decoded row is a quiet NaN in
+    // every column, and the documented guarantee for queries that are not finite (kektor_hip.h, "Conventions") does the rest -- no
+    // results, a zeroed id row, no walk, no counter touched, the other queries answered bit for bit as alone.  The exact scan has no
+    // such rule: there the row is zeros (an ordinary query) and the epilogue kernel discards its answer.
+    const KdbView v = kdb_make_view(idx);
+    rc = kdb_launch_decode_rows(v, d_ids, B, d_q, d_found, flat ? 0u : 0x7fc00000u, s);
+    if (rc) return rc;
+    rc = flat ? flat_dev_locked(idx, d_q, B, kin, d_allow_bits, inner, i_ids, i_dist, i_cnt, s)
+              : search_dev_locked(idx, d_q, B, kin, ef, d_allow_bits, inner, i_ids, i_dist, i_cnt, s);
+    if (rc) return rc;
+    if (flat || drop)
+        rc = kdb_launch_by_id_finish(d_ids, d_found, B, k, kin, (uint32_t)(db / 4), i_ids, i_dist, i_cnt, d_out_ids, d_out_dist, d_out_count, s);
+    return rc;
+}
+
+static int by_id_dev_call(kdb_index *idx, bool flat, const uint32_t *d_ids, uint32_t B, uint32_t k, uint32_t ef, const uint64_t *d_allow_bits,
+                          uint32_t flags, uint32_t *d_out_ids, float *d_out_dist, uint32_t *d_out_count, void *stream) {
+    KDB_CHECK_IDX(idx);
+    if (B && (!d_ids || !d_out_ids || !d_out_dist || !d_out_count)) {
+        kdb_set_error("%s: null buffer", flat ? "flat_scan_by_id" : "search_by_id");
+        return KDB_ERR_INVALID;
+    }
+    std::lock_guard<std::mutex> lk(idx->mu);
+    KDB_HIP(hipSetDevice(idx->device));
+    hipStream_t s = stream ? (hipStream_t)stream : idx->stream;
+    KdbLaneGuard lane(idx, s);
+    if (lane.rc) return lane.rc;
+    return by_id_dev_locked(idx, flat, d_ids, B, k, ef, d_allow_bits, flags, d_out_ids, d_out_dist, d_out_count, s);
+}
+
+extern "C" int kdb_search_by_id_dev(kdb_index *idx, const uint32_t *d_ids, uint32_t B, uint32_t k, uint32_t ef, const uint64_t *d_allow_bits,
+                                    uint32_t flags, uint32_t *d_out_ids, float *d_out_dist, uint32_t *d_out_count, void *stream) {
+    return by_id_dev_call(idx, false, d_ids, B, k, ef, d_allow_bits, flags, d_out_ids, d_out_dist, d_out_count, stream);
+}
+extern "C" int kdb_flat_scan_by_id_dev(kdb_index *idx, const uint32_t *d_ids, uint32_t B, uint32_t k, const uint64_t *d_allow_bits, uint32_t flags,
+                                       uint32_t *d_out_ids, float *d_out_dist, uint32_t *d_out_count, void *stream) {
+    return by_id_dev_call(idx, true, d_ids, B, k, 0, d_allow_bits, flags, d_out_ids, d_out_dist, d_out_count, stream);
+}
+
+// Host pointers, modelled on kdb_distance_batch: the index's own staging buffer, one such call at a time (big_mu), idx->mu only
+// around the enqueue, the writers' protocol (writers_waiting / inflight).  What crosses the bus: 4 bytes per query in, the
+// answers out.  Never part of a combined group (the ids are not queries a group's kernel could read).
+static int by_id_host_call(kdb_index *idx, bool flat, const uint32_t *ids, uint32_t B, uint32_t k, uint32_t ef, const uint64_t *allow_bits,
+                           uint32_t flags, uint32_t *out_ids, void *out_dist, uint32_t *out_count) {
+    KDB_CHECK_IDX(idx);
+    if (B == 0) return KDB_OK;
+    if (!ids || !out_ids || !out_dist || !out_count || k == 0) {
+        kdb_set_error("%s: null buffer or k == 0", flat ? "flat_scan_by_id" : "search_by_id");
+        return KDB_ERR_INVALID;
+    }
+    KDB_HIP(hipSetDevice(idx->device));
+    std::lock_guard<std::mutex> big(idx->big_mu);
+    std::unique_lock<std::mutex> lk(idx->mu);
+    close_expired_session(idx);
+    if (idx->writers_waiting) idx->slot_cv.wait(lk, [&] { return idx->writers_waiting == 0; });
+    const size_t db = (flags & KDB_SEARCH_DIST_F64) ? 8 : 4;
+    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    const size_t aw = allow_bits ? ((size_t)(idx->count >> 6) + 1) * 8 : 0;
+    const size_t o_allow = al((size_t)B * 4), o_ids = o_allow + al(aw), o_dist = o_ids + al((size_t)B * k * 4), o_cnt = o_dist + al((size_t)B * k * db);
+    int rc = ensure_iobuf(idx, o_cnt + al((size_t)B * 4));
+    if (rc) return rc;
+    idx->inflight++;
+    struct Done { // every exit: the stream is idle (queued copies touch the CALLER's buffers) and the call no longer counts
+        kdb_index *i;
+        std::unique_lock<std::mutex> &l;
+        ~Done() {
+            if (l.owns_lock()) l.unlock();
+            (void)hipStreamSynchronize(i->stream);
+            l.lock();
+            i->inflight--;
+            if (i->inflight == 0 && i->writers_waiting) i->slot_cv.notify_all();
+        }
+    } done{idx, lk};
+    unsigned char *const d = reinterpret_cast<unsigned char *>(idx->d_iobuf);
+    hipStream_t s = idx->stream;
+    const uint32_t n_deleted = idx->n_deleted;
+    lk.unlock();
+    KDB_HIP(hipMemcpyAsync(d, ids, (size_t)B * 4, hipMemcpyHostToDevice, s));
+    if (allow_bits) KDB_HIP(hipMemcpyAsync(d + o_allow, allow_bits, aw, hipMemcpyHostToDevice, s));
+    lk.lock();
+    uint64_t seq = 0;
+    int kind = 0;
+    {
+        KdbLaneGuard lane(idx, s);
+        if (lane.rc) return lane.rc;
+        rc = by_id_dev_locked(idx, flat, reinterpret_cast<uint32_t *>(d), B, k, ef, allow_bits ? reinterpret_cast<uint64_t *>(d + o_allow) : nullptr,
+                              flags & ~(uint32_t)KDB_SEARCH_FAIL_ON_DROP, reinterpret_cast<uint32_t *>(d + o_ids), reinterpret_cast<float *>(d + o_dist),
+                              reinterpret_cast<uint32_t *>(d + o_cnt), s);
+        seq = idx->launch_seq;
+        kind = idx->last_kind;
+    }
+    lk.unlock();
+    if (rc) return rc;
+    KDB_HIP(hipMemcpyAsync(out_ids, d + o_ids, (size_t)B * k * 4, hipMemcpyDeviceToHost, s));
+    KDB_HIP(hipMemcpyAsync(out_dist, d + o_dist, (size_t)B * k * db, hipMemcpyDeviceToHost, s));
+    KDB_HIP(hipMemcpyAsync(out_count, d + o_cnt, (size_t)B * 4, hipMemcpyDeviceToHost, s));
+    KDB_HIP(hipStreamSynchronize(s));
+    if (!flat && (flags & KDB_SEARCH_FAIL_ON_DROP) && n_deleted > 2047u && seq > 0 && kind == 1) { // as kdb_search_batch (staged_big_call)
+        unsigned long long c[4] = {0, 0, 0, 0};
+        KDB_HIP(hipMemcpy(c, idx->d_ctr + (size_t)((seq - 1) % kdb_index::RING) * 4, 32, hipMemcpyDeviceToHost));
+        if (c[3]) {
+            kdb_set_error("search_by_id: %llu pending traversal-only candidates were discarded (more than 2047 deleted nodes waiting in one "
+                          "walk): answers may differ from the reference's", c[3]);
+            return KDB_ERR_DIVERGED;
+        }
+    }
+    return KDB_OK;
+}
+
+extern "C" int kdb_search_by_id(kdb_index *idx, const uint32_t *ids, uint32_t B, uint32_t k, uint32_t ef, const uint64_t *allow_bits, uint32_t flags,
+                                uint32_t *out_ids, float *out_dist, uint32_t *out_count) {
+    return by_id_host_call(idx, false, ids, B, k, ef, allow_bits, flags, out_ids, out_dist, out_count);
+}
+extern "C" int kdb_flat_scan_by_id(kdb_index *idx, const uint32_t *ids, uint32_t B, uint32_t k, const uint64_t *allow_bits, uint32_t flags,
+                                   uint32_t *out_ids, float *out_dist, uint32_t *out_count) {
+    return by_id_host_call(idx, true, ids, B, k, 0, allow_bits, flags, out_ids, out_dist, out_count);
+}
+
+// GetNodeData(...).Vector / the vectors of VGetMany for n ids (by_id.hip).  Reads only: ordered like a search.
+extern "C" int kdb_index_decode_rows_dev(kdb_index *idx, const uint32_t *d_ids, uint32_t n, float *d_out, uint8_t *d_out_found, void *stream) {
+    KDB_CHECK_IDX(idx);
+    if (n == 0) return KDB_OK;
+    if (!d_ids || !d_out) {
+        kdb_set_error("decode_rows: null buffer");
+        return KDB_ERR_INVALID;
+    }
+    std::lock_guard<std::mutex> lk(idx->mu);
+    KDB_HIP(hipSetDevice(idx->device));
+    return kdb_launch_decode_rows(kdb_make_view(idx), d_ids, n, d_out, d_out_found, 0u, stream ? (hipStream_t)stream : idx->stream);
+}
+
+extern "C" int kdb_index_decode_rows(kdb_index *idx, const uint32_t *ids, uint32_t n, float *out, uint8_t *out_found) {
+    KDB_CHECK_IDX(idx);
+    if (n == 0) return KDB_OK;
+    if (!ids || !out) {
+        kdb_set_error("decode_rows: null buffer");
+        return KDB_ERR_INVALID;
+    }
+    KDB_HIP(hipSetDevice(idx->device));
+    std::lock_guard<std::mutex> big(idx->big_mu);
+    std::unique_lock<std::mutex> lk(idx->mu);
+    close_expired_session(idx);
+    if (idx->writers_waiting) idx->slot_cv.wait(lk, [&] { return idx->writers_waiting == 0; });
+    // in pieces of at most 64 MiB of vectors (VGetMany pages 500 ids; a caller that asks for a million rows must not make the
+    // staging buffer as large as the index)
+    const size_t row_b = (size_t)idx->desc.dim * 4;
+    size_t per = ((size_t)64 << 20) / row_b;
+    if (per < 1) per = 1;
+    if (per > n) per = n;
+    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    const size_t o_rows = al(per * 4), o_found = o_rows + al(per * row_b);
+    int rc = ensure_iobuf(idx, o_found + al(per));
+    if (rc) return rc;
+    idx->inflight++;
+    struct Done {
+        kdb_index *i;
+        std::unique_lock<std::mutex> &l;
+        ~Done() {
+            if (l.owns_lock()) l.unlock();
+            (void)hipStreamSynchronize(i->stream);
+            l.lock();
+            i->inflight--;
+            if (i->inflight == 0 && i->writers_waiting) i->slot_cv.notify_all();
+        }
+    } done{idx, lk};
+    unsigned char *const d = reinterpret_cast<unsigned char *>(idx->d_iobuf);
+    hipStream_t s = idx->stream;
+    const KdbView v = kdb_make_view(idx); // (inflight > 0 keeps writers out: count, rows and deleted bits cannot move)
+    lk.unlock();
+    for (size_t i0 = 0; i0 < n; i0 += per) {
+        const uint32_t m = (uint32_t)(n - i0 < per ? n - i0 : per);
+        KDB_HIP(hipMemcpyAsync(d, ids + i0, (size_t)m * 4, hipMemcpyHostToDevice, s));
+        rc = kdb_launch_decode_rows(v, reinterpret_cast<uint32_t *>(d), m, reinterpret_cast<float *>(d + o_rows), d + o_found, 0u, s);
+        if (rc) return rc;
+        KDB_HIP(hipMemcpyAsync(out + i0 * idx->desc.dim, d + o_rows, (size_t)m * row_b, hipMemcpyDeviceToHost, s));
+        if (out_found) KDB_HIP(hipMemcpyAsync(out_found + i0, d + o_found, m, hipMemcpyDeviceToHost, s));
+    }
     KDB_HIP(hipStreamSynchronize(s));
     return KDB_OK;
 }

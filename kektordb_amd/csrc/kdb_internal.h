@@ -125,6 +125,8 @@ struct kdb_lane {
     uint32_t *d_work = nullptr;
     void *d_tie = nullptr;      // heap-order second pass: [count, cursor, tied query indices ...] | candidate-heap tails
     size_t tie_bytes = 0;
+    void *d_byid = nullptr;     // by-id entry points: decoded source rows | found flags | the inner call's k + 1 answers
+    size_t byid_bytes = 0;
     hipStream_t last_stream = nullptr;
     hipEvent_t done = nullptr;
     hipStream_t side = nullptr;  // heap-order pass beside the search kernel (large batches): created at first use
@@ -185,6 +187,8 @@ struct kdb_index {
     uint32_t gentry_cap = 0;
     void *d_tie = nullptr;           // (current lane's) scratch of the heap-order second pass (search_heap.hip)
     size_t tie_bytes = 0;
+    void *d_byid = nullptr;          // (current lane's) decode buffer of the by-id entry points (by_id.hip): none of the buffers the walk and the scan use
+    size_t byid_bytes = 0;
     void *d_build = nullptr;        // graph-construction workspace
     size_t build_bytes = 0;
     int last_kind = 0;              // 1 search, 2 flat scan, 3 distance tile
@@ -371,6 +375,13 @@ int kdb_launch_merge_topk_f64(uint32_t G, uint32_t B, uint32_t k, const uint32_t
                               const uint32_t *d_in_count, size_t stride_i, size_t stride_d, size_t stride_c,
                               const uint32_t *d_id_base, uint32_t *d_out_ids, void *d_out_dist, int out64, uint32_t *d_out_count,
                               hipStream_t s);
+// by_id.hip: ids -> float32 vectors as GetNodeData returns them (not found: `miss_bits` in every column, found 0), and the epilogue
+// of the by-id entry points (not-found sources answered with nothing; kin == k + 1: the source's own id, else the last entry, leaves)
+int kdb_launch_decode_rows(const KdbView &v, const uint32_t *d_ids, uint32_t n, float *d_out, uint8_t *d_found, uint32_t miss_bits,
+                           hipStream_t s);
+int kdb_launch_by_id_finish(const uint32_t *d_src_ids, const uint8_t *d_found, uint32_t B, uint32_t k, uint32_t kin, uint32_t dist_words,
+                            const uint32_t *d_in_ids, const void *d_in_dist, const uint32_t *d_in_cnt, uint32_t *d_out_ids, void *d_out_dist,
+                            uint32_t *d_out_cnt, hipStream_t s);
 // build.hip
 int kdb_build_graph(kdb_index *idx, uint32_t count, const kdb_build_params *p);
 int kdb_add_batch_ref(kdb_index *idx, uint32_t first_id, uint32_t n, const uint8_t *levels, uint32_t ef_construction);

@@ -25,6 +25,7 @@ SEARCH_PREPARED = 2
 SEARCH_DIST_F64 = 8  # int8 indexes: distances come back as the reference's float64 (KDB_SEARCH_DIST_F64)
 SEARCH_TIE_FLAG = 16    # KDB_SEARCH_TIE_FLAG: bit 31 of out_count marks a walk that met equal distances
 SEARCH_HEAP_ORDER = 32  # KDB_SEARCH_HEAP_ORDER: such walks are repeated with the reference's two heaps
+BY_ID_DROP_SELF = 256    # KDB_BY_ID_DROP_SELF: a by-id answer without the source's own id
 VACUUM_ELECT_TOP_LEVEL = 1  # KDB_VACUUM_ELECT_TOP_LEVEL
 COUNT_TIED = 0x80000000
 COUNT_MASK = 0x7fffffff
@@ -409,6 +410,85 @@ class HipIndex:
                                             _tptr(d_out), C.c_void_p(stream) if stream else None),
               "kdb_distance_batch_dev")
 
+    # ---- stored rows as queries (GetNodeData / VGetMany + SearchWithScores, on the device) -------------------------
+    def decode_rows(self, ids):
+        """GetNodeData(id).Vector (hnsw_index.go:2909-2959) for every id -> (vectors [n, dim] f32, found [n] bool): float32 rows as
+        stored, float16 widened, int8 dequantised; an id that is 0, above count or deleted: a zero row, found False"""
+        self._live()
+        a = np.ascontiguousarray(ids, dtype=np.uint32).ravel()
+        out = np.zeros((a.size, self.dim), dtype=np.float32)
+        found = np.zeros(a.size, dtype=np.uint8)
+        check(self.L.kdb_index_decode_rows(self.h, _ptr(a), a.size, _ptr(out), _ptr(found)), "kdb_index_decode_rows")
+        return out, found.astype(bool)
+
+    def decode_rows_dev(self, d_ids, d_out, d_found=None, stream=None):
+        """torch device tensors: d_ids [n] int32 / uint32, d_out [n, dim] float32, d_found [n] uint8 or None"""
+        self._live()
+        _ready(stream)
+        check(self.L.kdb_index_decode_rows_dev(self.h, _tptr(d_ids), int(d_ids.shape[0]), _tptr(d_out), _tptr(d_found),
+                                               C.c_void_p(stream) if stream else None), "kdb_index_decode_rows_dev")
+
+    def _by_id_flags(self, fail_on_drop=False, dist64=False, tie_flag=False, heap_order=False, drop_self=False):
+        return (self._flags() | (4 if fail_on_drop else 0) | (SEARCH_DIST_F64 if dist64 else 0) | (SEARCH_TIE_FLAG if tie_flag else 0)
+                | (SEARCH_HEAP_ORDER if heap_order else 0) | (BY_ID_DROP_SELF if drop_self else 0))
+
+    def search_by_id(self, ids, k: int, ef: int = 0, allow_bits=None, trace: bool = False, fail_on_drop: bool = False, dist64: bool = False,
+                     tie_flag: bool = False, heap_order: bool = False, drop_self: bool = False, flags: int = 0):
+        """search_batch with the stored rows of `ids` as the queries (kdb_search_by_id): what search_batch(decode_rows(ids)[0], ...)
+        returns, bit for bit, with 4 bytes per query crossing the bus; a source id that is not found gets count 0.
+        drop_self: the answer without the source's own id (the call runs with k + 1).  flags: further raw KDB_SEARCH_* bits"""
+        self._live()
+        a = np.ascontiguousarray(ids, dtype=np.uint32).ravel()
+        B = a.size
+        out_ids = np.zeros((B, k), dtype=np.uint32)
+        dist = np.full((B, k), np.inf, dtype=np.float64 if dist64 else np.float32)
+        cnt = np.zeros(B, dtype=np.uint32)
+        ab = None if allow_bits is None else np.ascontiguousarray(allow_bits, dtype=np.uint64)
+        nd = nh = None
+        if trace:
+            nd = np.zeros(B, dtype=np.uint32)
+            nh = np.zeros(B, dtype=np.uint32)
+            check(self.L.kdb_search_set_trace(self.h, _ptr(nd), _ptr(nh), 0), "set_trace")
+        try:
+            check(self.L.kdb_search_by_id(self.h, _ptr(a), B, k, ef, _ptr(ab),
+                                          self._by_id_flags(fail_on_drop, dist64, tie_flag, heap_order, drop_self) | int(flags),
+                                          _ptr(out_ids), _ptr(dist), _ptr(cnt)), "kdb_search_by_id")
+        finally:
+            if trace:
+                self.L.kdb_search_set_trace(self.h, None, None, 0)
+        if trace:
+            return out_ids, dist, cnt, (nd, nh)
+        return out_ids, dist, cnt
+
+    def search_by_id_dev(self, d_ids, k: int, ef: int, d_out_ids, d_out_dist, d_out_count, d_allow=None, stream=None, dist64=False,
+                         tie_flag=False, heap_order=False, drop_self=False):
+        """torch device tensors in (d_ids [B] int32 / uint32), asynchronous on `stream` (kdb_search_by_id_dev)"""
+        self._live()
+        _ready(stream)
+        check(self.L.kdb_search_by_id_dev(self.h, _tptr(d_ids), int(d_ids.shape[0]), k, ef, _tptr(d_allow),
+                                          self._by_id_flags(False, dist64, tie_flag, heap_order, drop_self), _tptr(d_out_ids), _tptr(d_out_dist),
+                                          _tptr(d_out_count), C.c_void_p(stream) if stream else None), "kdb_search_by_id_dev")
+
+    def flat_scan_by_id(self, ids, k: int, allow_bits=None, dist64: bool = False, drop_self: bool = False, flags: int = 0):
+        """flat_scan_batch with the stored rows of `ids` as the queries (kdb_flat_scan_by_id)"""
+        self._live()
+        a = np.ascontiguousarray(ids, dtype=np.uint32).ravel()
+        B = a.size
+        out_ids = np.zeros((B, k), dtype=np.uint32)
+        dist = np.full((B, k), np.inf, dtype=np.float64 if dist64 else np.float32)
+        cnt = np.zeros(B, dtype=np.uint32)
+        ab = None if allow_bits is None else np.ascontiguousarray(allow_bits, dtype=np.uint64)
+        check(self.L.kdb_flat_scan_by_id(self.h, _ptr(a), B, k, _ptr(ab), self._by_id_flags(dist64=dist64, drop_self=drop_self) | int(flags),
+                                         _ptr(out_ids), _ptr(dist), _ptr(cnt)), "kdb_flat_scan_by_id")
+        return out_ids, dist, cnt
+
+    def flat_scan_by_id_dev(self, d_ids, k: int, d_out_ids, d_out_dist, d_out_count, d_allow=None, stream=None, dist64=False, drop_self=False):
+        self._live()
+        _ready(stream)
+        check(self.L.kdb_flat_scan_by_id_dev(self.h, _tptr(d_ids), int(d_ids.shape[0]), k, _tptr(d_allow),
+                                             self._by_id_flags(dist64=dist64, drop_self=drop_self), _tptr(d_out_ids), _tptr(d_out_dist),
+                                             _tptr(d_out_count), C.c_void_p(stream) if stream else None), "kdb_flat_scan_by_id_dev")
+
     def counters(self):
         c = _lib.Counters()
         check(self.L.kdb_get_counters(self.h, C.byref(c)), "get_counters")
@@ -510,6 +590,19 @@ class HipIndex:
             return []  # the reference logs and returns an empty slice (:356-359)
         n = int(cnt[0])
         return [SearchResult(int(ids[0, i]), self.score(dist[0, i])) for i in range(n)]
+
+    def VSearchSimilar(self, ids, k: int, allowList=None, efSearch: int = 0, dropSelf: bool = False) -> List[List[SearchResult]]:
+        """One page of the Gardener's loop (pkg/cognitive/gardener.go:803-869: VGetMany, then VSearchWithScores with every
+        vData.Vector) as one call: per id the list SearchWithScores(GetNodeData(id).Vector, k, allowList, efSearch) returns;
+        an id that is not found gets an empty list (VGetMany does not return it).  dropSelf: without the id itself."""
+        a = np.ascontiguousarray(ids, dtype=np.uint32).ravel()
+        if self._closed:
+            return [[] for _ in range(a.size)]
+        try:
+            out, dist, cnt = self.search_by_id(a, k, efSearch, allowList, dist64=(self.precision == I8), drop_self=dropSelf)
+        except KdbError:
+            return [[] for _ in range(a.size)]  # the reference logs and returns an empty slice (:356-359)
+        return [[SearchResult(int(out[b, i]), self.score(dist[b, i])) for i in range(int(cnt[b]))] for b in range(a.size)]
 
 
 def merge_topk(metric: int, ids, dist, count, k: int, id_base=None, precision: int = F32):
