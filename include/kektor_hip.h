@@ -35,6 +35,10 @@
  *                           Gardener.findRedundantClusters (pkg/cognitive/gardener.go:803-869; again at :915, :1362, :2348) --
  *                           as ONE call in which the rows never leave the device
  *   kdb_flat_scan_by_id     the same in front of the exact scan (BruteForceIndex.SearchWithScores)
+ *   kdb_consensus_batch     CalculateConsensus (pkg/engine/epistemic_types.go:126-178) over the stored vectors of id lists, with the
+ *                           per-node similarity of Engine.VBeliefState (pkg/engine/epistemic.go:22-182, :81): centroid, distances to
+ *                           it, pair distances and the score in ONE kernel, about 40 bytes per list back
+ *   kdb_belief_batch        the search of VBeliefState (:45) and that consensus as one call: the k result rows never leave the device
  *   kdb_merge_topk          the merge step of the id-range shard (no reference
  *                           counterpart -- the reference is single process)
  *   kdb_sharded_search_batch  the same path over every GPU of a node from ONE process: fan-out,
@@ -360,6 +364,63 @@ KDB_API int kdb_flat_scan_by_id(kdb_index *idx, const uint32_t *ids, uint32_t B,
                                 uint32_t flags, uint32_t *out_ids, float *out_dist, uint32_t *out_count);
 KDB_API int kdb_flat_scan_by_id_dev(kdb_index *idx, const uint32_t *d_ids, uint32_t B, uint32_t k, const uint64_t *d_allow_bits,
                                     uint32_t flags, uint32_t *d_out_ids, float *d_out_dist, uint32_t *d_out_count, void *stream);
+
+/* CalculateConsensus ON THE DEVICE for B id lists (consensus.hip) -- the arithmetic half of Engine.VBeliefState
+ * (pkg/engine/epistemic.go:22-182; the Gardener calls it per reflection, pkg/cognitive/gardener.go:3358-3421), which searches, reads
+ * the k result vectors back with VGet and runs CalculateConsensus (pkg/engine/epistemic_types.go:126-178) on them.
+ * A LIST: list b is ids[b][0 .. counts[b] & KDB_COUNT_MASK) of the array ids[B][stride]; a search call's out_count can be passed
+ * straight in, tie bit included.  counts == NULL: every list has `stride` entries.  stride <= KDB_CONSENSUS_MAX_K and every count
+ * <= stride, else KDB_ERR_INVALID (the _dev form cannot see device counts: it clamps a count to stride).  Ids may repeat; each
+ * occurrence is a node.
+ * A NODE'S VECTOR is what kdb_index_decode_rows gives for the id (float32 as stored, float16 widened, int8 dequantised; the same
+ * device routine, kdb_decode.cuh).  An id that is 0, above count or deleted is skipped, as the `continue` at epistemic.go:56 does;
+ * every id is range-checked before an address is formed.  The metric of the index plays no part: the reference calls
+ * CosineDistance (epistemic_types.go:299-320) whatever the index is.
+ * active_bits: NULL (all active) or a bitset laid out like an allow list ((count >> 6) + 1 words, bit id).  Found nodes whose bit is
+ * clear are the historical ones (epistemic.go:104-111): they count in n_found and get a similarity, and take no part in the
+ * consensus.
+ * THE CONSENSUS, over the active nodes in list order (:126-178):
+ *   n_active == 0   score 0, variance 0, max_pair 0, a zero centroid; the call still returns KDB_OK;
+ *   n_active == 1   score 1, variance 0, max_pair 0, the centroid is that vector, bit for bit;
+ *   otherwise       the centroid is accumulated per column in float32 from 0, node after node, then divided by float32(n) (correctly
+ *                   rounded); variance = (sum over the nodes, in order, of CosineDistance(node, centroid)^2) / n; max_pair = the
+ *                   largest CosineDistance of a pair (maxVar: a NaN never wins, `d > maxVar` is false for it); score = 1 when
+ *                   max_pair < 1e-10, else 1 - math.Min(variance / (max_pair * max_pair), 1).
+ *   CosineDistance  dot, |a|^2 and |b|^2 are float64 sums over the columns in ascending order of products of widened float32
+ *                   values (exact in float64, so fused and unfused multiply-add agree); a zero norm gives 1; otherwise
+ *                   1 - max(0, min(1, dot / (sqrt(|a|^2) * sqrt(|b|^2)))) with Go's math.Max / math.Min: a NaN stays a NaN.
+ * out_similarity: NULL or [B][stride] doubles: 1 - CosineDistance(vector_i, queries[b]) with the raw query, not normalised (:81), for
+ * every found entry, active or not; -1.0 for an entry that was not found or lies beyond the count.  queries (float32 [B][dim]) may
+ * be NULL only if out_similarity is NULL, else KDB_ERR_INVALID.
+ * out_centroid: NULL or [B][dim] float32.  out_gram: NULL or [B][stride + 1][stride + 1] doubles, the raw accumulators: entry
+ * (i, j) is the dot product of list entries i and j, the diagonal holds the squared norms, index `stride` is the centroid; rows
+ * and columns of entries that are not active (not found, historical, beyond the count) are zero.
+ * The Gardener's centroid of stored ids (gardener.go:3403-3412) is out_centroid of a call on that list.
+ * flags must be 0.  B == 0: KDB_OK.  Nothing is written to the index: ordered like a search.  The host-pointer form takes turns on
+ * the index's staging buffer like kdb_search_by_id and synchronises once.                                                          */
+#define KDB_CONSENSUS_MAX_K 64u          /* the reference caps k at 50 (epistemic.go:31) */
+typedef struct kdb_consensus {           /* 32 bytes */
+    double score, variance, max_pair;    /* CalculateConsensus's score, variance, maxVar */
+    uint32_t n_found;                    /* len(nodes): list entries whose row was found */
+    uint32_t n_active;                   /* len(activeNodes) */
+} kdb_consensus;
+KDB_API int kdb_consensus_batch(kdb_index *idx, const uint32_t *ids, const uint32_t *counts, uint32_t B, uint32_t stride,
+                                const float *queries, const uint64_t *active_bits, uint32_t flags, kdb_consensus *out,
+                                double *out_similarity, float *out_centroid, double *out_gram);
+KDB_API int kdb_consensus_batch_dev(kdb_index *idx, const uint32_t *d_ids, const uint32_t *d_counts, uint32_t B, uint32_t stride,
+                                    const float *d_queries, const uint64_t *d_active_bits, uint32_t flags, kdb_consensus *d_out,
+                                    double *d_out_similarity, float *d_out_centroid, double *d_out_gram, void *stream);
+/* VBeliefState's search and consensus as ONE call, a composition like the by-id calls: kdb_search_batch[_dev] runs unchanged with
+ * (k <= KDB_CONSENSUS_MAX_K, ef, allow list, flags) -- out_ids, out_dist, out_count, the trace and the counters are exactly its own
+ * -- and the consensus kernel then runs on those id lists and counts with the same queries (stride = k).  out_similarity: NULL or
+ * [B][k].  KDB_SEARCH_PREPARED is refused: the similarity is defined on the raw query.  The host-pointer form takes turns on the
+ * staging buffer like kdb_search_by_id and is never combined with other callers' queries.                                         */
+KDB_API int kdb_belief_batch(kdb_index *idx, const float *queries, uint32_t B, uint32_t k, uint32_t ef, const uint64_t *allow_bits,
+                             const uint64_t *active_bits, uint32_t flags, uint32_t *out_ids, float *out_dist, uint32_t *out_count,
+                             kdb_consensus *out, double *out_similarity);
+KDB_API int kdb_belief_batch_dev(kdb_index *idx, const float *d_queries, uint32_t B, uint32_t k, uint32_t ef,
+                                 const uint64_t *d_allow_bits, const uint64_t *d_active_bits, uint32_t flags, uint32_t *d_out_ids,
+                                 float *d_out_dist, uint32_t *d_out_count, kdb_consensus *d_out, double *d_out_similarity, void *stream);
 
 /* B queries x C candidate ids each (ids[B][C], id 0 = skip -> +inf): raw accumulates out[B][C].   */
 KDB_API int kdb_distance_batch(kdb_index *idx, const float *queries, uint32_t B, const uint32_t *ids, uint32_t C,

@@ -12,6 +12,7 @@
 #include <atomic>
 #include <chrono>
 #include <climits>
+#include <cmath>
 #include <condition_variable>
 #include <cstdint>
 #include <cstring>
@@ -60,6 +61,103 @@ struct AllowList {
     void Add(uint32_t id) { words[id >> 6] |= 1ull << (id & 63); }
     bool Contains(uint32_t id) const { return (id >> 6) < words.size() && ((words[id >> 6] >> (id & 63)) & 1ull); }
 };
+
+// CalculateConsensus (pkg/engine/epistemic_types.go:126-178) with the per-node similarity of Engine.VBeliefState (epistemic.go:81) for n
+// vectors that are in host memory already, all of them active: the arithmetic of kdb_consensus_batch restated on the host (kektor_hip.h
+// has the definition), bit for bit -- float32 centroid accumulated node after node from 0 and divided once, every dot product and
+// squared norm a float64 sum over the columns in ascending order (each norm is summed once instead of once per CosineDistance call:
+// the same additions in the same order).  gram (optional): (n + 1) x (n + 1), index n the centroid, as out_gram.
+struct ConsensusResult {
+    kdb_consensus rec{};
+    std::vector<float> centroid;    // dim floats (zeros for n == 0)
+    std::vector<double> similarity; // n doubles; empty without a query
+    std::vector<double> gram;       // filled when asked for
+};
+namespace detail {
+inline double cosine_distance(double dot, double na, double nb) { // :299-320 from its three sums
+    if (na == 0.0 || nb == 0.0) return 1.0;
+    double sim = dot / (std::sqrt(na) * std::sqrt(nb));
+    if (sim > 1.0) sim = 1.0;   // math.Min(1, sim): a NaN stays
+    if (sim <= 0.0) sim = 0.0;  // math.Max(0, sim): -0 becomes +0, a NaN stays
+    return 1.0 - sim;
+}
+// out[j] = sum over the columns, ascending, of a[c] * rows[j][c] for j in [j0, j1): four independent chains at a time
+inline void dots(const float *a, const float *rows, size_t dim, size_t j0, size_t j1, double *out) {
+    size_t j = j0;
+    for (; j + 4 <= j1; j += 4) {
+        const float *r0 = rows + j * dim, *r1 = r0 + dim, *r2 = r1 + dim, *r3 = r2 + dim;
+        double s0 = 0, s1 = 0, s2 = 0, s3 = 0;
+        for (size_t c = 0; c < dim; c++) {
+            const double x = (double)a[c];
+            s0 += x * (double)r0[c];
+            s1 += x * (double)r1[c];
+            s2 += x * (double)r2[c];
+            s3 += x * (double)r3[c];
+        }
+        out[j] = s0, out[j + 1] = s1, out[j + 2] = s2, out[j + 3] = s3;
+    }
+    for (; j < j1; j++) {
+        const float *r = rows + j * dim;
+        double s0 = 0;
+        for (size_t c = 0; c < dim; c++) s0 += (double)a[c] * (double)r[c];
+        out[j] = s0;
+    }
+}
+} // namespace detail
+inline ConsensusResult consensus_host(const float *rows, uint32_t n, uint32_t dim, const float *query = nullptr, bool wantGram = false) {
+    ConsensusResult r;
+    r.rec.n_found = r.rec.n_active = n;
+    r.centroid.assign(dim, 0.f);
+    const size_t N = n, D = dim, W = N + 1;
+    std::vector<double> g(W * W, 0.0); // dots of the n rows and (index n) the centroid
+    if (n == 1) std::memcpy(r.centroid.data(), rows, D * 4); // "return 1.0, 0.0, nodes[0].Vector"
+    else if (n > 1) {
+        for (size_t i = 0; i < N; i++)
+            for (size_t c = 0; c < D; c++) r.centroid[c] += rows[i * D + c];
+        for (size_t c = 0; c < D; c++) r.centroid[c] /= (float)n;
+    }
+    std::vector<double> tmp(N + 1);
+    for (size_t i = 0; i < N; i++) { // row i against rows i .. n - 1
+        detail::dots(rows + i * D, rows, D, i, N, tmp.data());
+        for (size_t j = i; j < N; j++) g[i * W + j] = g[j * W + i] = tmp[j];
+    }
+    if (n) {
+        detail::dots(r.centroid.data(), rows, D, 0, N, tmp.data());
+        for (size_t j = 0; j < N; j++) g[N * W + j] = g[j * W + N] = tmp[j];
+        detail::dots(r.centroid.data(), r.centroid.data(), D, 0, 1, &g[N * W + N]);
+    }
+    if (query) {
+        r.similarity.resize(N);
+        double qq = 0;
+        detail::dots(query, query, D, 0, 1, &qq);
+        detail::dots(query, rows, D, 0, N, tmp.data());
+        for (size_t i = 0; i < N; i++) r.similarity[i] = 1.0 - detail::cosine_distance(tmp[i], g[i * W + i], qq);
+    }
+    if (n == 1) r.rec.score = 1.0;
+    else if (n > 1) {
+        double sum = 0.0;
+        for (size_t i = 0; i < N; i++) {
+            const double d = detail::cosine_distance(g[i * W + N], g[i * W + i], g[N * W + N]);
+            sum += d * d;
+        }
+        r.rec.variance = sum / (double)n;
+        double mv = 0.0;
+        for (size_t i = 0; i < N; i++)
+            for (size_t j = i + 1; j < N; j++) {
+                const double d = detail::cosine_distance(g[i * W + j], g[i * W + i], g[j * W + j]);
+                if (d > mv) mv = d;
+            }
+        r.rec.max_pair = mv;
+        if (mv < 1e-10) r.rec.score = 1.0;
+        else {
+            double q = r.rec.variance / (mv * mv);
+            if (q > 1.0) q = 1.0; // math.Min(q, 1): a NaN stays
+            r.rec.score = 1.0 - q;
+        }
+    }
+    if (wantGram) r.gram = std::move(g);
+    return r;
+}
 
 namespace hnsw {
 
@@ -233,6 +331,48 @@ class Index {
         for (uint32_t b = 0; b < B; b++)
             for (uint32_t i = 0; i < cnt[b]; i++) out[b].push_back({rid[(size_t)b * k + i], score(dist, (size_t)b * k + i)});
         return out;
+    }
+    // CalculateConsensus (pkg/engine/epistemic_types.go:126-178) over the stored vectors of B id lists of `stride` entries each, on the
+    // device (kdb_consensus_batch): counts / queries / activeList may be null; similarity (optional) receives B x stride doubles
+    std::vector<kdb_consensus> Consensus(const uint32_t *ids, uint32_t B, uint32_t stride, const uint32_t *counts = nullptr, const float *queries = nullptr,
+                                         const AllowList *activeList = nullptr, std::vector<double> *similarity = nullptr,
+                                         std::vector<float> *centroid = nullptr) const {
+        std::vector<kdb_consensus> out(B);
+        if (similarity) similarity->assign(queries ? (size_t)B * stride : 0, -1.0);
+        if (centroid) centroid->assign((size_t)B * dim_, 0.f);
+        if (!h_ || B == 0) return out;
+        check(kdb_consensus_batch(h_, ids, counts, B, stride, queries, activeList ? activeList->words.data() : nullptr, 0, out.data(),
+                                  similarity && queries ? similarity->data() : nullptr, centroid ? centroid->data() : nullptr, nullptr), "consensus");
+        return out;
+    }
+    // The vector half of Engine.VBeliefState (pkg/engine/epistemic.go:22-182) as one call (kdb_belief_batch): the search (k capped at
+    // 50 as :31 does, efSearch 100 as :45) and CalculateConsensus over its active results; activeList: the ids that are NOT historical.
+    // ok is false where the reference returns an error: no candidates, or no active node.
+    struct Belief {
+        bool ok = false;
+        kdb_consensus consensus{};
+        std::vector<SearchResult> nodes;
+        std::vector<double> similarities;
+    };
+    Belief BeliefState(const std::vector<float> &query, int k, const AllowList *allowList = nullptr, const AllowList *activeList = nullptr,
+                       int efSearch = 100) const {
+        Belief r;
+        if (k <= 0) k = 10;
+        if (k > 50) k = 50;
+        if (!h_ || query.size() != dim_) return r;
+        std::vector<uint32_t> ids((size_t)k), cnt(1);
+        std::vector<double> sim((size_t)k);
+        DistBuf dist((size_t)k, wide());
+        int rc = kdb_belief_batch(h_, query.data(), 1, (uint32_t)k, (uint32_t)(efSearch > 0 ? efSearch : 0), allowList ? allowList->words.data() : nullptr,
+                                  activeList ? activeList->words.data() : nullptr, flags(), ids.data(), dist.ptr(), cnt.data(), &r.consensus, sim.data());
+        if (rc) return r;
+        for (uint32_t i = 0; i < (cnt[0] & KDB_COUNT_MASK); i++)
+            if (sim[i] != -1.0) {
+                r.nodes.push_back({ids[i], score(dist, i)});
+                r.similarities.push_back(sim[i]);
+            }
+        r.ok = r.consensus.n_active > 0;
+        return r;
     }
     kdb_index *handle() const { return h_; }
     // concurrent kdb_search_batch calls of a few queries share launches inside the library (kektor_hip.h, "Conventions"): a

@@ -28,6 +28,7 @@ ABI_SYMBOLS = [
     "kdb_cluster_comm_info", "kdb_cluster_debug_fail_next", "kdb_index_reserve", "kdb_index_drop_f16_shadow", "kdb_probe_gather", "kdb_probe_stream", "kdb_probe_poison_lds", "kdb_index_caller_stats", "kdb_merge_topk_f64", "kdb_index_refine",
     "kdb_index_vacuum", "kdb_index_dead_link_scan", "kdb_index_drop_walk_planes", "kdb_index_add",
     "kdb_index_decode_rows", "kdb_index_decode_rows_dev", "kdb_search_by_id", "kdb_search_by_id_dev", "kdb_flat_scan_by_id", "kdb_flat_scan_by_id_dev",
+    "kdb_consensus_batch", "kdb_consensus_batch_dev", "kdb_belief_batch", "kdb_belief_batch_dev",
 ]
 
 
@@ -50,6 +51,11 @@ class GraphView(C.Structure):
 class Counters(C.Structure):
     _fields_ = [("n_dist", C.c_uint64), ("n_hops", C.c_uint64), ("bytes", C.c_uint64),
                 ("last_kernel_ms", C.c_double), ("n_dropped", C.c_uint64), ("n_tied", C.c_uint64)]
+
+
+class Consensus(C.Structure):  # kdb_consensus, 32 bytes
+    _fields_ = [("score", C.c_double), ("variance", C.c_double), ("max_pair", C.c_double), ("n_found", C.c_uint32),
+                ("n_active", C.c_uint32)]
 
 
 class BuildParams(C.Structure):
@@ -148,6 +154,10 @@ def load():
     L.kdb_search_by_id_dev.argtypes = [vp, vp, u32, u32, u32, vp, u32, vp, vp, vp, vp]
     L.kdb_flat_scan_by_id.argtypes = [vp, vp, u32, u32, vp, u32, vp, vp, vp]
     L.kdb_flat_scan_by_id_dev.argtypes = [vp, vp, u32, u32, vp, u32, vp, vp, vp, vp]
+    L.kdb_consensus_batch.argtypes = [vp, vp, vp, u32, u32, vp, vp, u32, vp, vp, vp, vp]
+    L.kdb_consensus_batch_dev.argtypes = [vp, vp, vp, u32, u32, vp, vp, u32, vp, vp, vp, vp, vp]
+    L.kdb_belief_batch.argtypes = [vp, vp, u32, u32, u32, vp, vp, u32, vp, vp, vp, vp, vp]
+    L.kdb_belief_batch_dev.argtypes = [vp, vp, u32, u32, u32, vp, vp, u32, vp, vp, vp, vp, vp, vp]
     L.kdb_distance_batch_dev.argtypes = [vp, vp, u32, vp, u32, u32, vp, vp]
     L.kdb_index_build.argtypes = [vp, u32, C.POINTER(BuildParams)]
     L.kdb_index_add_batch.argtypes = [vp, u32, u32, vp, u32, u32]

@@ -10,6 +10,7 @@
 //
 // Nothing here computes a distance: the walk and the scan are the existing ones, fed from the decode buffer.
 #include "kdb_internal.h"
+#include "kdb_decode.cuh"
 
 namespace {
 
@@ -18,58 +19,26 @@ namespace {
 // 16-byte boundaries for every precision (ld is a multiple of 16 elements).  The output has no padding: row i starts at
 // out + i * dim, so it is written as float4 only when dim is a multiple of 4 (then every row start is 16-byte aligned with the
 // base), column by column otherwise; either way the 16 lanes of a row write one contiguous run.
-// int8: (float(v) / 127.0f) * abs_max in that order.  The division must be the correctly rounded one: hipcc's default
-// (-fhip-fp32-correctly-rounded-divide-sqrt); the Makefile passes neither its negation nor -ffast-math, and -ffp-contract=off keeps the
-// multiply from being fused with anything.
+// The 16 bytes become floats in kdb_decode16 (kdb_decode.cuh), which the consensus kernel shares.
 template <int PREC>
 __global__ void __launch_bounds__(256)
 decode_rows_kernel(KdbView v, const uint32_t *__restrict__ ids, uint32_t n, float *__restrict__ out, uint8_t *__restrict__ found,
                    uint32_t miss_bits, int vec_out) {
-    constexpr uint32_t E = PREC == KDB_PREC_F32 ? 4u : PREC == KDB_PREC_F16 ? 8u : 16u; // elements per 16-byte load
+    constexpr uint32_t E = KdbDecode<PREC>::E; // elements per 16-byte load
     const uint32_t t = threadIdx.x & 15u;
     const uint32_t r = blockIdx.x * 16u + (threadIdx.x >> 4);
     if (r >= n) return;
     const uint32_t id = ids[r];
-    bool ok = id - 1u < v.count; // 1 <= id <= count
-    if (ok) ok = ((v.deleted[id >> 5] >> (id & 31u)) & 1u) == 0u;
+    const bool ok = kdb_row_found(v, id); // 1 <= id <= count, not deleted
     if (t == 0 && found) found[r] = ok ? 1 : 0;
     float *const o = out + (size_t)r * v.dim;
     const float miss = __uint_as_float(miss_bits);
     const uint4 *row = nullptr;
-    if (ok) row = reinterpret_cast<const uint4 *>(reinterpret_cast<const unsigned char *>(v.rows) + (size_t)id * v.ld * (16u / E));
+    if (ok) row = kdb_row_ptr16<PREC>(v, id);
     for (uint32_t c = t * E; c < v.ld; c += 16u * E) {
         float x[E];
         if (ok) {
-            const uint4 w = row[c / E];
-            if constexpr (PREC == KDB_PREC_F32) {
-                x[0] = __uint_as_float(w.x);
-                x[1] = __uint_as_float(w.y);
-                x[2] = __uint_as_float(w.z);
-                x[3] = __uint_as_float(w.w);
-            } else if constexpr (PREC == KDB_PREC_F16) {
-                const uint32_t ws[4] = {w.x, w.y, w.z, w.w};
-#pragma unroll
-                for (uint32_t j = 0; j < 4; j++) {
-                    _Float16 lo, hi;
-                    const uint16_t l16 = (uint16_t)(ws[j] & 0xffffu), h16 = (uint16_t)(ws[j] >> 16);
-                    __builtin_memcpy(&lo, &l16, 2);
-                    __builtin_memcpy(&hi, &h16, 2);
-                    x[2 * j] = (float)lo;
-                    x[2 * j + 1] = (float)hi;
-                }
-            } else {
-                const uint32_t ws[4] = {w.x, w.y, w.z, w.w};
-#pragma unroll
-                for (uint32_t j = 0; j < 16; j++) {
-                    const int8_t q = (int8_t)((ws[j >> 2] >> (8u * (j & 3u))) & 0xffu);
-                    float y = 0.f;
-                    if (v.q_absmax != 0.f) { // an untrained quantizer dequantizes to zeros
-                        const float d = (float)q / 127.0f;
-                        y = d * v.q_absmax;
-                    }
-                    x[j] = y;
-                }
-            }
+            kdb_decode16<PREC>(row[c / E], v.q_absmax, x);
         } else {
 #pragma unroll
             for (uint32_t j = 0; j < E; j++) x[j] = miss;

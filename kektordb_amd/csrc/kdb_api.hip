@@ -2238,6 +2238,214 @@ extern "C" int kdb_index_decode_rows(kdb_index *idx, const uint32_t *ids, uint32
     return KDB_OK;
 }
 
+// ---------------------------------------------------------------------------------------------
+// CalculateConsensus for id lists (consensus.hip) and VBeliefState's search + consensus as one call.  The consensus kernel reads
+// the lists, the rows and the queries where they are and needs no scratch; kdb_belief_batch is a COMPOSITION like the by-id calls:
+// search_dev_locked unchanged, then the kernel on its answers.
+// ---------------------------------------------------------------------------------------------
+static int consensus_check(const char *who, uint32_t B, uint32_t stride, uint32_t flags, const void *ids, const void *queries, const void *out,
+                           const void *out_similarity) {
+    if (stride > KDB_CONSENSUS_MAX_K) {
+        kdb_set_error("%s: %u entries per list, above KDB_CONSENSUS_MAX_K (%u)", who, stride, KDB_CONSENSUS_MAX_K);
+        return KDB_ERR_INVALID;
+    }
+    if (flags) {
+        kdb_set_error("%s: flags must be 0", who);
+        return KDB_ERR_INVALID;
+    }
+    if (!queries && out_similarity) {
+        kdb_set_error("%s: out_similarity needs the queries", who);
+        return KDB_ERR_INVALID;
+    }
+    if (B && ((!ids && stride) || !out)) {
+        kdb_set_error("%s: null buffer", who);
+        return KDB_ERR_INVALID;
+    }
+    return KDB_OK;
+}
+
+extern "C" int kdb_consensus_batch_dev(kdb_index *idx, const uint32_t *d_ids, const uint32_t *d_counts, uint32_t B, uint32_t stride,
+                                       const float *d_queries, const uint64_t *d_active_bits, uint32_t flags, kdb_consensus *d_out,
+                                       double *d_out_similarity, float *d_out_centroid, double *d_out_gram, void *stream) {
+    KDB_CHECK_IDX(idx);
+    int rc = consensus_check("consensus", B, stride, flags, d_ids, d_queries, d_out, d_out_similarity);
+    if (rc) return rc;
+    if (B == 0) return KDB_OK;
+    std::lock_guard<std::mutex> lk(idx->mu);
+    KDB_HIP(hipSetDevice(idx->device));
+    return kdb_launch_consensus(kdb_make_view(idx), d_ids, d_counts, B, stride, d_queries, reinterpret_cast<const uint32_t *>(d_active_bits), d_out,
+                                d_out_similarity, d_out_centroid, d_out_gram, stream ? (hipStream_t)stream : idx->stream);
+}
+
+// the shared frame of the two host-pointer forms: one such call at a time on the index's staging buffer (big_mu), idx->mu only around
+// the enqueue, the writers' protocol (writers_waiting / inflight) -- as by_id_host_call
+struct HostTurn {
+    kdb_index *idx;
+    std::lock_guard<std::mutex> big;
+    std::unique_lock<std::mutex> lk;
+    bool counted = false;
+    explicit HostTurn(kdb_index *i) : idx(i), big(i->big_mu), lk(i->mu) {
+        close_expired_session(idx);
+        if (idx->writers_waiting) idx->slot_cv.wait(lk, [&] { return idx->writers_waiting == 0; });
+    }
+    void begin() {
+        idx->inflight++;
+        counted = true;
+    }
+    ~HostTurn() { // every exit: the stream is idle (queued copies touch the CALLER's buffers) and the call no longer counts
+        if (!counted) return;
+        if (lk.owns_lock()) lk.unlock();
+        (void)hipStreamSynchronize(idx->stream);
+        lk.lock();
+        idx->inflight--;
+        if (idx->inflight == 0 && idx->writers_waiting) idx->slot_cv.notify_all();
+    }
+};
+
+extern "C" int kdb_consensus_batch(kdb_index *idx, const uint32_t *ids, const uint32_t *counts, uint32_t B, uint32_t stride, const float *queries,
+                                   const uint64_t *active_bits, uint32_t flags, kdb_consensus *out, double *out_similarity, float *out_centroid,
+                                   double *out_gram) {
+    KDB_CHECK_IDX(idx);
+    int rc = consensus_check("consensus", B, stride, flags, ids, queries, out, out_similarity);
+    if (rc) return rc;
+    if (counts)
+        for (uint32_t b = 0; b < B; b++)
+            if ((counts[b] & KDB_COUNT_MASK) > stride) {
+                kdb_set_error("consensus: list %u has %u entries, more than the stride %u", b, counts[b] & KDB_COUNT_MASK, stride);
+                return KDB_ERR_INVALID;
+            }
+    if (B == 0) return KDB_OK;
+    KDB_HIP(hipSetDevice(idx->device));
+    HostTurn turn(idx);
+    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    const size_t dim = idx->desc.dim, gw = (size_t)stride + 1;
+    const size_t aw = active_bits ? ((size_t)(idx->count >> 6) + 1) * 8 : 0;
+    const size_t o_cnt = al((size_t)B * stride * 4), o_q = o_cnt + al(counts ? (size_t)B * 4 : 0), o_act = o_q + al(queries ? (size_t)B * dim * 4 : 0),
+                 o_out = o_act + al(aw), o_sim = o_out + al((size_t)B * sizeof(kdb_consensus)), o_cen = o_sim + al(out_similarity ? (size_t)B * stride * 8 : 0),
+                 o_gram = o_cen + al(out_centroid ? (size_t)B * dim * 4 : 0), total = o_gram + al(out_gram ? (size_t)B * gw * gw * 8 : 0);
+    rc = ensure_iobuf(idx, total);
+    if (rc) return rc;
+    turn.begin();
+    unsigned char *const d = reinterpret_cast<unsigned char *>(idx->d_iobuf);
+    hipStream_t s = idx->stream;
+    const KdbView v = kdb_make_view(idx); // (inflight > 0 keeps writers out: count, rows and deleted bits cannot move)
+    turn.lk.unlock();
+    if (stride) KDB_HIP(hipMemcpyAsync(d, ids, (size_t)B * stride * 4, hipMemcpyHostToDevice, s));
+    if (counts) KDB_HIP(hipMemcpyAsync(d + o_cnt, counts, (size_t)B * 4, hipMemcpyHostToDevice, s));
+    if (queries) KDB_HIP(hipMemcpyAsync(d + o_q, queries, (size_t)B * dim * 4, hipMemcpyHostToDevice, s));
+    if (active_bits) KDB_HIP(hipMemcpyAsync(d + o_act, active_bits, aw, hipMemcpyHostToDevice, s));
+    rc = kdb_launch_consensus(v, reinterpret_cast<uint32_t *>(d), counts ? reinterpret_cast<uint32_t *>(d + o_cnt) : nullptr, B, stride,
+                              queries ? reinterpret_cast<float *>(d + o_q) : nullptr, active_bits ? reinterpret_cast<uint32_t *>(d + o_act) : nullptr,
+                              reinterpret_cast<kdb_consensus *>(d + o_out), out_similarity ? reinterpret_cast<double *>(d + o_sim) : nullptr,
+                              out_centroid ? reinterpret_cast<float *>(d + o_cen) : nullptr, out_gram ? reinterpret_cast<double *>(d + o_gram) : nullptr, s);
+    if (rc) return rc;
+    KDB_HIP(hipMemcpyAsync(out, d + o_out, (size_t)B * sizeof(kdb_consensus), hipMemcpyDeviceToHost, s));
+    if (out_similarity && stride) KDB_HIP(hipMemcpyAsync(out_similarity, d + o_sim, (size_t)B * stride * 8, hipMemcpyDeviceToHost, s));
+    if (out_centroid) KDB_HIP(hipMemcpyAsync(out_centroid, d + o_cen, (size_t)B * dim * 4, hipMemcpyDeviceToHost, s));
+    if (out_gram) KDB_HIP(hipMemcpyAsync(out_gram, d + o_gram, (size_t)B * gw * gw * 8, hipMemcpyDeviceToHost, s));
+    KDB_HIP(hipStreamSynchronize(s));
+    return KDB_OK;
+}
+
+static int belief_check(uint32_t B, uint32_t k, uint32_t flags, const void *queries, const void *out_ids, const void *out_dist, const void *out_count,
+                        const void *out) {
+    if (k == 0 || k > KDB_CONSENSUS_MAX_K) {
+        kdb_set_error("belief: k = %u outside 1..KDB_CONSENSUS_MAX_K (%u)", k, KDB_CONSENSUS_MAX_K);
+        return KDB_ERR_INVALID;
+    }
+    if (flags & KDB_SEARCH_PREPARED) {
+        kdb_set_error("belief: KDB_SEARCH_PREPARED is not accepted (the similarities are defined on the raw query, epistemic.go:81)");
+        return KDB_ERR_INVALID;
+    }
+    if (B && (!queries || !out_ids || !out_dist || !out_count || !out)) {
+        kdb_set_error("belief: null buffer");
+        return KDB_ERR_INVALID;
+    }
+    return KDB_OK;
+}
+
+static int belief_dev_locked(kdb_index *idx, const float *d_queries, uint32_t B, uint32_t k, uint32_t ef, const uint64_t *d_allow_bits,
+                             const uint64_t *d_active_bits, uint32_t flags, uint32_t *d_out_ids, float *d_out_dist, uint32_t *d_out_count,
+                             kdb_consensus *d_out, double *d_out_similarity, hipStream_t s) {
+    int rc = search_dev_locked(idx, d_queries, B, k, ef, d_allow_bits, flags, d_out_ids, d_out_dist, d_out_count, s);
+    if (rc) return rc;
+    return kdb_launch_consensus(kdb_make_view(idx), d_out_ids, d_out_count, B, k, d_queries, reinterpret_cast<const uint32_t *>(d_active_bits), d_out,
+                                d_out_similarity, nullptr, nullptr, s);
+}
+
+extern "C" int kdb_belief_batch_dev(kdb_index *idx, const float *d_queries, uint32_t B, uint32_t k, uint32_t ef, const uint64_t *d_allow_bits,
+                                    const uint64_t *d_active_bits, uint32_t flags, uint32_t *d_out_ids, float *d_out_dist, uint32_t *d_out_count,
+                                    kdb_consensus *d_out, double *d_out_similarity, void *stream) {
+    KDB_CHECK_IDX(idx);
+    int rc = belief_check(B, k, flags, d_queries, d_out_ids, d_out_dist, d_out_count, d_out);
+    if (rc) return rc;
+    if (B == 0) return KDB_OK;
+    std::lock_guard<std::mutex> lk(idx->mu);
+    KDB_HIP(hipSetDevice(idx->device));
+    hipStream_t s = stream ? (hipStream_t)stream : idx->stream;
+    KdbLaneGuard lane(idx, s);
+    if (lane.rc) return lane.rc;
+    return belief_dev_locked(idx, d_queries, B, k, ef, d_allow_bits, d_active_bits, flags, d_out_ids, d_out_dist, d_out_count, d_out, d_out_similarity, s);
+}
+
+extern "C" int kdb_belief_batch(kdb_index *idx, const float *queries, uint32_t B, uint32_t k, uint32_t ef, const uint64_t *allow_bits,
+                                const uint64_t *active_bits, uint32_t flags, uint32_t *out_ids, float *out_dist, uint32_t *out_count, kdb_consensus *out,
+                                double *out_similarity) {
+    KDB_CHECK_IDX(idx);
+    int rc = belief_check(B, k, flags, queries, out_ids, out_dist, out_count, out);
+    if (rc) return rc;
+    if (B == 0) return KDB_OK;
+    KDB_HIP(hipSetDevice(idx->device));
+    HostTurn turn(idx);
+    const size_t db = (flags & KDB_SEARCH_DIST_F64) ? 8 : 4;
+    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    const size_t bw = ((size_t)(idx->count >> 6) + 1) * 8;
+    const size_t o_allow = al((size_t)B * idx->desc.dim * 4), o_act = o_allow + al(allow_bits ? bw : 0), o_ids = o_act + al(active_bits ? bw : 0),
+                 o_dist = o_ids + al((size_t)B * k * 4), o_cnt = o_dist + al((size_t)B * k * db), o_out = o_cnt + al((size_t)B * 4),
+                 o_sim = o_out + al((size_t)B * sizeof(kdb_consensus)), total = o_sim + al(out_similarity ? (size_t)B * k * 8 : 0);
+    rc = ensure_iobuf(idx, total);
+    if (rc) return rc;
+    turn.begin();
+    unsigned char *const d = reinterpret_cast<unsigned char *>(idx->d_iobuf);
+    hipStream_t s = idx->stream;
+    const uint32_t n_deleted = idx->n_deleted;
+    turn.lk.unlock();
+    KDB_HIP(hipMemcpyAsync(d, queries, (size_t)B * idx->desc.dim * 4, hipMemcpyHostToDevice, s));
+    if (allow_bits) KDB_HIP(hipMemcpyAsync(d + o_allow, allow_bits, bw, hipMemcpyHostToDevice, s));
+    if (active_bits) KDB_HIP(hipMemcpyAsync(d + o_act, active_bits, bw, hipMemcpyHostToDevice, s));
+    turn.lk.lock();
+    uint64_t seq = 0;
+    int kind = 0;
+    {
+        KdbLaneGuard lane(idx, s);
+        if (lane.rc) return lane.rc;
+        rc = belief_dev_locked(idx, reinterpret_cast<float *>(d), B, k, ef, allow_bits ? reinterpret_cast<uint64_t *>(d + o_allow) : nullptr,
+                               active_bits ? reinterpret_cast<uint64_t *>(d + o_act) : nullptr, flags & ~(uint32_t)KDB_SEARCH_FAIL_ON_DROP,
+                               reinterpret_cast<uint32_t *>(d + o_ids), reinterpret_cast<float *>(d + o_dist), reinterpret_cast<uint32_t *>(d + o_cnt),
+                               reinterpret_cast<kdb_consensus *>(d + o_out), out_similarity ? reinterpret_cast<double *>(d + o_sim) : nullptr, s);
+        seq = idx->launch_seq;
+        kind = idx->last_kind;
+    }
+    turn.lk.unlock();
+    if (rc) return rc;
+    KDB_HIP(hipMemcpyAsync(out_ids, d + o_ids, (size_t)B * k * 4, hipMemcpyDeviceToHost, s));
+    KDB_HIP(hipMemcpyAsync(out_dist, d + o_dist, (size_t)B * k * db, hipMemcpyDeviceToHost, s));
+    KDB_HIP(hipMemcpyAsync(out_count, d + o_cnt, (size_t)B * 4, hipMemcpyDeviceToHost, s));
+    KDB_HIP(hipMemcpyAsync(out, d + o_out, (size_t)B * sizeof(kdb_consensus), hipMemcpyDeviceToHost, s));
+    if (out_similarity) KDB_HIP(hipMemcpyAsync(out_similarity, d + o_sim, (size_t)B * k * 8, hipMemcpyDeviceToHost, s));
+    KDB_HIP(hipStreamSynchronize(s));
+    if ((flags & KDB_SEARCH_FAIL_ON_DROP) && n_deleted > 2047u && seq > 0 && kind == 1) { // as kdb_search_batch (staged_big_call)
+        unsigned long long c[4] = {0, 0, 0, 0};
+        KDB_HIP(hipMemcpy(c, idx->d_ctr + (size_t)((seq - 1) % kdb_index::RING) * 4, 32, hipMemcpyDeviceToHost));
+        if (c[3]) {
+            kdb_set_error("belief: %llu pending traversal-only candidates were discarded (more than 2047 deleted nodes waiting in one walk): answers "
+                          "may differ from the reference's", c[3]);
+            return KDB_ERR_DIVERGED;
+        }
+    }
+    return KDB_OK;
+}
+
 extern "C" int kdb_index_build(kdb_index *idx, uint32_t count, const kdb_build_params *params) {
     KDB_CHECK_IDX(idx);
     KdbWriteLock wl(idx); // excludes host-pointer calls in flight

@@ -382,6 +382,9 @@ int kdb_launch_decode_rows(const KdbView &v, const uint32_t *d_ids, uint32_t n, 
 int kdb_launch_by_id_finish(const uint32_t *d_src_ids, const uint8_t *d_found, uint32_t B, uint32_t k, uint32_t kin, uint32_t dist_words,
                             const uint32_t *d_in_ids, const void *d_in_dist, const uint32_t *d_in_cnt, uint32_t *d_out_ids, void *d_out_dist,
                             uint32_t *d_out_cnt, hipStream_t s);
+// consensus.hip: CalculateConsensus for B id lists, one workgroup per list (everything optional may be null)
+int kdb_launch_consensus(const KdbView &v, const uint32_t *d_ids, const uint32_t *d_counts, uint32_t B, uint32_t stride, const float *d_queries,
+                         const uint32_t *d_active, kdb_consensus *d_out, double *d_sim, float *d_centroid, double *d_gram, hipStream_t s);
 // build.hip
 int kdb_build_graph(kdb_index *idx, uint32_t count, const kdb_build_params *p);
 int kdb_add_batch_ref(kdb_index *idx, uint32_t first_id, uint32_t n, const uint8_t *levels, uint32_t ef_construction);

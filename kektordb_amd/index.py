@@ -29,6 +29,9 @@ BY_ID_DROP_SELF = 256    # KDB_BY_ID_DROP_SELF: a by-id answer without the sourc
 VACUUM_ELECT_TOP_LEVEL = 1  # KDB_VACUUM_ELECT_TOP_LEVEL
 COUNT_TIED = 0x80000000
 COUNT_MASK = 0x7fffffff
+CONSENSUS_MAX_K = 64  # KDB_CONSENSUS_MAX_K
+# kdb_consensus: CalculateConsensus's score, variance and maxVar, len(nodes), len(activeNodes)
+CONSENSUS_DTYPE = np.dtype([("score", "<f8"), ("variance", "<f8"), ("max_pair", "<f8"), ("n_found", "<u4"), ("n_active", "<u4")])
 
 _ELEM = {F32: np.float32, F16: np.uint16, I8: np.int8}
 
@@ -489,6 +492,83 @@ class HipIndex:
                                              self._by_id_flags(dist64=dist64, drop_self=drop_self), _tptr(d_out_ids), _tptr(d_out_dist),
                                              _tptr(d_out_count), C.c_void_p(stream) if stream else None), "kdb_flat_scan_by_id_dev")
 
+    # ---- CalculateConsensus / VBeliefState on the device (consensus.hip) -------------------------------------------
+    def consensus(self, ids, counts=None, queries=None, active_bits=None, want_centroid=False, want_gram=False, flags: int = 0):
+        """CalculateConsensus (pkg/engine/epistemic_types.go:126-178) over the stored vectors of B id lists (kdb_consensus_batch).
+        ids [B, stride] (stride <= 64); counts [B] or None (every list full; bit 31 of a search's count is ignored); queries [B, dim]
+        or None; active_bits: dense uint64 bitset over ids, clear = historical (epistemic.go:104-111), None = all active.
+        Returns a dict: rec (CONSENSUS_DTYPE [B]: score, variance, max_pair, n_found, n_active), similarity ([B, stride] f64, -1.0 =
+        no node; None without queries), centroid ([B, dim] f32 or None), gram ([B, stride + 1, stride + 1] f64 or None)"""
+        self._live()
+        ii = np.ascontiguousarray(ids, dtype=np.uint32)
+        assert ii.ndim == 2
+        B, stride = ii.shape
+        cn = None if counts is None else np.ascontiguousarray(counts, dtype=np.uint32).ravel()
+        assert cn is None or cn.size == B
+        q = None if queries is None else np.ascontiguousarray(queries, dtype=np.float32)
+        assert q is None or q.shape == (B, self.dim)
+        ab = None if active_bits is None else np.ascontiguousarray(active_bits, dtype=np.uint64)
+        rec = np.zeros(B, dtype=CONSENSUS_DTYPE)
+        sim = None if q is None else np.zeros((B, stride), dtype=np.float64)
+        cen = np.zeros((B, self.dim), dtype=np.float32) if want_centroid else None
+        gram = np.zeros((B, stride + 1, stride + 1), dtype=np.float64) if want_gram else None
+        check(self.L.kdb_consensus_batch(self.h, _ptr(ii), _ptr(cn), B, stride, _ptr(q), _ptr(ab), int(flags), _ptr(rec), _ptr(sim), _ptr(cen),
+                                         _ptr(gram)), "kdb_consensus_batch")
+        return {"rec": rec, "similarity": sim, "centroid": cen, "gram": gram}
+
+    def consensus_dev(self, d_ids, d_out, d_counts=None, d_queries=None, d_active=None, d_similarity=None, d_centroid=None, d_gram=None,
+                      stream=None):
+        """torch device tensors: d_ids [B, stride] int32, d_out [B, 32] uint8 (kdb_consensus records: view as CONSENSUS_DTYPE on the
+        host), d_counts [B] int32, d_queries [B, dim] f32, d_similarity [B, stride] f64, d_centroid [B, dim] f32,
+        d_gram [B, stride + 1, stride + 1] f64; asynchronous on `stream` (kdb_consensus_batch_dev)"""
+        self._live()
+        _ready(stream)
+        B, stride = int(d_ids.shape[0]), int(d_ids.shape[1])
+        check(self.L.kdb_consensus_batch_dev(self.h, _tptr(d_ids), _tptr(d_counts), B, stride, _tptr(d_queries), _tptr(d_active), 0, _tptr(d_out),
+                                             _tptr(d_similarity), _tptr(d_centroid), _tptr(d_gram), C.c_void_p(stream) if stream else None),
+              "kdb_consensus_batch_dev")
+
+    def belief(self, queries, k: int, ef: int = 100, allow_bits=None, active_bits=None, trace: bool = False, fail_on_drop: bool = False,
+               dist64: bool = False, tie_flag: bool = False, heap_order: bool = False):
+        """The search of Engine.VBeliefState (pkg/engine/epistemic.go:45) and the consensus of its results as one call
+        (kdb_belief_batch): (ids, dist, count) exactly as search_batch returns them, then rec [B] and similarity [B, k] as consensus
+        returns them for (ids, count, queries, active_bits)[, (n_dist, n_hops)]"""
+        self._live()
+        q = np.ascontiguousarray(queries, dtype=np.float32)
+        assert q.ndim == 2 and q.shape[1] == self.dim
+        B = q.shape[0]
+        ids = np.zeros((B, k), dtype=np.uint32)
+        dist = np.full((B, k), np.inf, dtype=np.float64 if dist64 else np.float32)
+        cnt = np.zeros(B, dtype=np.uint32)
+        rec = np.zeros(B, dtype=CONSENSUS_DTYPE)
+        sim = np.zeros((B, k), dtype=np.float64)
+        ab = None if allow_bits is None else np.ascontiguousarray(allow_bits, dtype=np.uint64)
+        act = None if active_bits is None else np.ascontiguousarray(active_bits, dtype=np.uint64)
+        nd = nh = None
+        if trace:
+            nd = np.zeros(B, dtype=np.uint32)
+            nh = np.zeros(B, dtype=np.uint32)
+            check(self.L.kdb_search_set_trace(self.h, _ptr(nd), _ptr(nh), 0), "set_trace")
+        try:
+            check(self.L.kdb_belief_batch(self.h, _ptr(q), B, k, ef, _ptr(ab), _ptr(act), self._by_id_flags(fail_on_drop, dist64, tie_flag, heap_order),
+                                          _ptr(ids), _ptr(dist), _ptr(cnt), _ptr(rec), _ptr(sim)), "kdb_belief_batch")
+        finally:
+            if trace:
+                self.L.kdb_search_set_trace(self.h, None, None, 0)
+        if trace:
+            return ids, dist, cnt, rec, sim, (nd, nh)
+        return ids, dist, cnt, rec, sim
+
+    def belief_dev(self, d_queries, k: int, ef: int, d_out_ids, d_out_dist, d_out_count, d_out, d_similarity=None, d_allow=None, d_active=None,
+                   stream=None, dist64=False, tie_flag=False, heap_order=False):
+        """torch device tensors in, asynchronous on `stream` (kdb_belief_batch_dev); d_out [B, 32] uint8 as in consensus_dev"""
+        self._live()
+        _ready(stream)
+        check(self.L.kdb_belief_batch_dev(self.h, _tptr(d_queries), int(d_queries.shape[0]), k, ef, _tptr(d_allow), _tptr(d_active),
+                                          self._by_id_flags(False, dist64, tie_flag, heap_order), _tptr(d_out_ids), _tptr(d_out_dist),
+                                          _tptr(d_out_count), _tptr(d_out), _tptr(d_similarity), C.c_void_p(stream) if stream else None),
+              "kdb_belief_batch_dev")
+
     def counters(self):
         c = _lib.Counters()
         check(self.L.kdb_get_counters(self.h, C.byref(c)), "get_counters")
@@ -603,6 +683,32 @@ class HipIndex:
         except KdbError:
             return [[] for _ in range(a.size)]  # the reference logs and returns an empty slice (:356-359)
         return [[SearchResult(int(out[b, i]), self.score(dist[b, i])) for i in range(int(cnt[b]))] for b in range(a.size)]
+
+
+    def BeliefState(self, query, k: int = 10, allowList=None, activeList=None, efSearch: int = 100) -> Optional[dict]:
+        """The vector half of Engine.VBeliefState (pkg/engine/epistemic.go:22-182): search (k capped at 50, ef 100), then
+        CalculateConsensus over the active results.  Returns None where the reference returns an error (no candidates, no active
+        node), else {"score", "variance", "sources", "nodes": [SearchResult], "similarities": [float]}.
+        activeList: dense uint64 bitset of the ids that are NOT historical (None: all)."""
+        if self._closed:
+            return None
+        if k <= 0:
+            k = 10
+        k = min(k, 50)
+        q = np.asarray(query, dtype=np.float32)
+        if q.ndim != 1 or q.shape[0] != self.dim:
+            return None
+        try:
+            ids, dist, cnt, rec, sim = self.belief(q[None, :], k, efSearch, allowList, activeList, dist64=(self.precision == I8))
+        except KdbError:
+            return None
+        n = int(cnt[0]) & int(COUNT_MASK)
+        if n == 0 or int(rec["n_found"][0]) == 0 or int(rec["n_active"][0]) == 0:
+            return None
+        found = [i for i in range(n) if sim[0, i] != -1.0]
+        return {"score": float(rec["score"][0]), "variance": float(rec["variance"][0]), "sources": int(rec["n_found"][0]),
+                "nodes": [SearchResult(int(ids[0, i]), self.score(dist[0, i])) for i in found],
+                "similarities": [float(sim[0, i]) for i in found]}
 
 
 def merge_topk(metric: int, ids, dist, count, k: int, id_base=None, precision: int = F32):
