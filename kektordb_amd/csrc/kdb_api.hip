@@ -7,6 +7,7 @@
 //   levels   (cap+1) uint8;  deleted: bitset;  norms: (cap+1) f32 (int8 norms / L2 row norms)
 //   visited  one bitset of (cap>>5)+1 words per resident search wave
 #include "kdb_internal.h"
+#include "kdb_stage.h"
 #include <stdarg.h>
 #include <stdio.h>
 #include <string.h>
@@ -885,11 +886,12 @@ extern "C" int kdb_index_patch_adjacency(kdb_index *idx, uint32_t level, uint32_
     hipStream_t s = idx->stream;
     KdbLaneGuard lane(idx, s);
     if (lane.rc) return lane.rc;
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    int rc = kdb_ensure_scratch(idx, al(rows.size() * 4) + al((size_t)n * 4) + 256);
+    KdbCarver cv;
+    const size_t o_rows = cv.take(rows.size() * 4), o_slots = cv.take((size_t)n * 4);
+    int rc = kdb_ensure_scratch(idx, cv.total() + 256);
     if (rc) return rc;
-    uint32_t *d_rows = reinterpret_cast<uint32_t *>(idx->d_scratch);
-    uint32_t *d_slots = reinterpret_cast<uint32_t *>(reinterpret_cast<unsigned char *>(idx->d_scratch) + al(rows.size() * 4));
+    unsigned char *const b = reinterpret_cast<unsigned char *>(idx->d_scratch);
+    uint32_t *d_rows = reinterpret_cast<uint32_t *>(b + o_rows), *d_slots = reinterpret_cast<uint32_t *>(b + o_slots);
     KDB_HIP(hipMemcpyAsync(d_rows, rows.data(), rows.size() * 4, hipMemcpyHostToDevice, s));
     KDB_HIP(hipMemcpyAsync(d_slots, slots.data(), (size_t)n * 4, hipMemcpyHostToDevice, s));
     rc = kdb_launch_adj_scatter(level == 0 ? idx->d_adj0 : idx->d_adj_up, deg, n, d_slots, d_rows, s);
@@ -996,10 +998,12 @@ static size_t qrow_bytes(const kdb_index *idx) {
 static int prepare_queries(kdb_index *idx, const KdbView &v, const float *d_queries, uint32_t B, uint32_t Bpad,
                            uint32_t flags, void **d_q, float **d_qnorm, hipStream_t s) {
     const size_t qb = qrow_bytes(idx);
-    int rc = ensure_qbuf(idx, (size_t)Bpad * qb + (size_t)Bpad * 4 + 256);
+    KdbCarver cv;
+    const size_t o_q = cv.take((size_t)Bpad * qb), o_qnorm = cv.take((size_t)Bpad * 4);
+    int rc = ensure_qbuf(idx, cv.total() + 256);
     if (rc) return rc;
-    *d_q = idx->d_qbuf;
-    *d_qnorm = reinterpret_cast<float *>(reinterpret_cast<unsigned char *>(idx->d_qbuf) + (((size_t)Bpad * qb + 255) & ~(size_t)255));
+    *d_q = reinterpret_cast<unsigned char *>(idx->d_qbuf) + o_q;
+    *d_qnorm = reinterpret_cast<float *>(reinterpret_cast<unsigned char *>(idx->d_qbuf) + o_qnorm);
     if (Bpad > B) KDB_HIP(hipMemsetAsync(reinterpret_cast<unsigned char *>(idx->d_qbuf) + (size_t)B * qb, 0, (size_t)(Bpad - B) * qb, s));
     return kdb_launch_prep_queries(v, d_queries, B, *d_q, *d_qnorm, (flags & KDB_SEARCH_PREPARED) ? 0 : 1, s);
 }
@@ -1120,6 +1124,25 @@ static int search_dev_locked(kdb_index *idx, const float *d_queries, uint32_t B,
     return KDB_OK;
 }
 
+// The frame of a device-pointer (_dev) call: idx->mu, the index's device, the caller's stream (null: the index's own) and, unless
+// the call needs no scratch, a scratch lane of that stream -- given back before the lock is.
+struct DevCall {
+    kdb_index *idx;
+    std::lock_guard<std::mutex> lk;
+    hipStream_t s;
+    bool laned = false;
+    int rc;
+    DevCall(kdb_index *i, void *stream, bool lane = true) : idx(i), lk(i->mu), s(stream ? (hipStream_t)stream : i->stream), rc(enter(lane)) {}
+    ~DevCall() { if (laned) (void)kdb_lane_release(idx, s); }
+    int enter(bool lane) {
+        KDB_HIP(hipSetDevice(idx->device));
+        if (!lane) return KDB_OK;
+        const int r = kdb_lane_acquire(idx, s);
+        laned = r == KDB_OK;
+        return r;
+    }
+};
+
 extern "C" int kdb_search_batch_dev(kdb_index *idx, const float *d_queries, uint32_t B, uint32_t k, uint32_t ef,
                                     const uint64_t *d_allow_bits, uint32_t flags, uint32_t *d_out_ids,
                                     float *d_out_dist, uint32_t *d_out_count, void *stream) {
@@ -1128,12 +1151,9 @@ extern "C" int kdb_search_batch_dev(kdb_index *idx, const float *d_queries, uint
         kdb_set_error("search: null buffer");
         return KDB_ERR_INVALID;
     }
-    std::lock_guard<std::mutex> lk(idx->mu);
-    KDB_HIP(hipSetDevice(idx->device));
-    hipStream_t s = stream ? (hipStream_t)stream : idx->stream;
-    KdbLaneGuard lane(idx, s);
-    if (lane.rc) return lane.rc;
-    return search_dev_locked(idx, d_queries, B, k, ef, d_allow_bits, flags, d_out_ids, d_out_dist, d_out_count, s);
+    DevCall call(idx, stream);
+    if (call.rc) return call.rc;
+    return search_dev_locked(idx, d_queries, B, k, ef, d_allow_bits, flags, d_out_ids, d_out_dist, d_out_count, call.s);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1148,8 +1168,8 @@ extern "C" int kdb_search_batch_dev(kdb_index *idx, const float *d_queries, uint
 //     (nobody is woken for it); the kernel reads the queries from the slot's page-locked buffer, writes the answers there and
 //     publishes a completion word per query; every member watches its own words and leaves when ITS walk is done;
 //   * writers wait until no such call is in flight and hold new ones back meanwhile (KdbWriteLock);
-//   * calls too large for a slot (KDB_HOST_PIN_MAX), traced calls and KDB_SEARCH_FAIL_ON_DROP take turns on the index's own
-//     staging buffer (big_mu), still without holding idx->mu while they wait.
+//   * everything else -- calls too large for a slot (KDB_HOST_PIN_MAX), traced calls, KDB_SEARCH_FAIL_ON_DROP, distances, by-id calls,
+//     decode, consensus, belief -- takes a turn on the index's own staging buffer: HostTurn, below, is that protocol.
 // ---------------------------------------------------------------------------------------------
 struct StagedLayout { // one call's (or group's) buffers inside a slot: the same offsets on the device and in page-locked memory
     size_t qbytes, aw, o_allow, o_ids, o_dist, o_cnt, out_span, total;
@@ -1158,7 +1178,7 @@ static StagedLayout staged_layout(const kdb_index *idx, uint32_t B, uint32_t k, 
     auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
     StagedLayout L;
     L.qbytes = (size_t)B * idx->desc.dim * 4;
-    L.aw = allow ? ((size_t)(idx->count >> 6) + 1) * 8 : 0;
+    L.aw = allow ? kdb_bits_bytes(idx->count) : 0;
     L.o_allow = al(L.qbytes);
     L.o_ids = L.o_allow + al(L.aw);
     L.o_dist = L.o_ids + (((size_t)B * k * 4 + 7) & ~(size_t)7); // 8-byte aligned: may hold doubles
@@ -1198,6 +1218,11 @@ static int slot_ensure(kdb_index *idx, kdb_slot &sl, size_t bytes) {
 static size_t host_pin_max() { // calls whose buffers exceed this go through the index's own staging buffer, from / to pageable memory
     static const size_t v = [] { const char *e = getenv("KDB_HOST_PIN_MAX"); return e ? (size_t)atoll(e) : (size_t)4 << 20; }();
     return v;
+}
+
+// an upper bound of what a call needs in a slot (the allow list is sized by the count the caller saw: at most the capacity's)
+static bool fits_a_slot(const kdb_index *idx, uint32_t B, uint32_t k, bool allow, size_t dist_bytes) {
+    return (size_t)B * idx->desc.dim * 4 + (allow ? kdb_bits_bytes(idx->cap) : 0) + (size_t)B * k * (4 + dist_bytes) + (size_t)B * 4 + 4096 <= host_pin_max();
 }
 
 static uint64_t now_ns() {
@@ -1562,64 +1587,95 @@ static int staged_slot_call(kdb_index *idx, const float *queries, uint32_t B, ui
     return rc;
 }
 
-// Calls that do not fit a slot: the index's own staging buffer, copies from / to the caller's pageable memory (they hold the
-// calling thread), one such call at a time (big_mu) -- idx->mu only around the enqueue.  Traced calls and KDB_SEARCH_FAIL_ON_DROP
-// come here too (the trace arrays and the "last launch" belong to one call at a time).
+// ---- turns on the index's own staging buffer ----------------------------------------------------
+// Calls that do not fit a slot, traced calls, KDB_SEARCH_FAIL_ON_DROP and every host-pointer call that is not a search or a scan of
+// queries (distances, by-id, decode, consensus, belief) stage through idx->d_iobuf with copies from / to the caller's pageable
+// memory, one such call at a time.  HostTurn is that turn, and its only implementation:
+//   * the constructor takes big_mu, then idx->mu, closes an open launch whose window has passed and waits while writers wait;
+//   * stage() sizes the buffer and counts the call (inflight: writers stay out until it has left, so count, capacity, rows and
+//     deleted bits cannot move) -- after it the caller drops and re-takes `lk` as it likes: copies outside it, enqueues under it;
+//   * the destructor runs on EVERY exit, the error returns too: it waits for the stream(s) -- queued copies read and write the
+//     CALLER's buffers -- and only then stops counting the call and wakes a waiting writer.
+// A KdbLaneGuard lives in an inner scope of the caller: it is gone before the destructor drops idx->mu.
+struct HostTurn {
+    kdb_index *idx;
+    std::lock_guard<std::mutex> big;
+    std::unique_lock<std::mutex> lk;
+    const bool both_streams; // the call also enqueues on idx->stream2
+    bool counted = false;
+    int rc = KDB_OK;
+    explicit HostTurn(kdb_index *i, bool stream2_too = false) : idx(i), big(i->big_mu), lk(i->mu), both_streams(stream2_too) {
+        close_expired_session(idx);
+        if (idx->writers_waiting) idx->slot_cv.wait(lk, [&] { return idx->writers_waiting == 0; });
+    }
+    unsigned char *stage(size_t bytes) { // under lk; null: rc and the error are set, nothing is counted
+        if ((rc = ensure_iobuf(idx, bytes)) != KDB_OK) return nullptr;
+        idx->inflight++;
+        counted = true;
+        return reinterpret_cast<unsigned char *>(idx->d_iobuf);
+    }
+    ~HostTurn() {
+        if (!counted) return;
+        if (lk.owns_lock()) lk.unlock();
+        (void)hipStreamSynchronize(idx->stream);
+        if (both_streams) (void)hipStreamSynchronize(idx->stream2);
+        lk.lock();
+        idx->inflight--;
+        if (idx->inflight == 0 && idx->writers_waiting) idx->slot_cv.notify_all();
+    }
+};
+
+// KDB_SEARCH_FAIL_ON_DROP: which launch the call's walk was and how many deleted nodes it could meet (note(): under idx->mu, right
+// behind the enqueue) and, once the stream is idle, whether that walk discarded pending candidates
+struct DropWatch {
+    uint32_t n_deleted = 0;
+    uint64_t seq = 0;
+    int kind = 0;
+    void note(const kdb_index *idx) {
+        n_deleted = idx->n_deleted;
+        seq = idx->launch_seq;
+        kind = idx->last_kind;
+    }
+    int check(const kdb_index *idx, const char *who) const {
+        if (n_deleted <= 2047u || seq == 0 || kind != 1) return KDB_OK;
+        unsigned long long c[4] = {0, 0, 0, 0};
+        KDB_HIP(hipMemcpy(c, idx->d_ctr + (size_t)((seq - 1) % kdb_index::RING) * 4, 32, hipMemcpyDeviceToHost));
+        if (!c[3]) return KDB_OK;
+        kdb_set_error("%s: %llu pending traversal-only candidates were discarded (more than 2047 deleted nodes waiting in one "
+                      "walk): answers may differ from the reference's", who, c[3]);
+        return KDB_ERR_DIVERGED;
+    }
+};
+
+// A search or an exact scan of queries on a turn: run(d_q, d_allow, d_ids, d_dist, d_cnt, stream, B) as for staged_slot_call.
 template <typename F>
 static int staged_big_call(kdb_index *idx, const float *queries, uint32_t B, uint32_t k, const uint64_t *allow_bits, uint32_t *out_ids, void *out_dist,
                            uint32_t *out_count, size_t dist_bytes, bool fail_on_drop, F run) {
-    std::lock_guard<std::mutex> big(idx->big_mu);
-    std::unique_lock<std::mutex> lk(idx->mu);
-    close_expired_session(idx);
-    if (idx->writers_waiting) idx->slot_cv.wait(lk, [&] { return idx->writers_waiting == 0; });
+    HostTurn turn(idx);
     const StagedLayout L = staged_layout(idx, B, k, allow_bits != nullptr, dist_bytes);
-    int rc = ensure_iobuf(idx, L.total);
-    if (rc) return rc;
-    idx->inflight++;
-    struct Done { // every exit: the stream is idle (queued copies touch the CALLER's buffers) and the call no longer counts
-        kdb_index *i;
-        std::unique_lock<std::mutex> &l;
-        ~Done() {
-            if (l.owns_lock()) l.unlock();
-            (void)hipStreamSynchronize(i->stream);
-            l.lock();
-            i->inflight--;
-            if (i->inflight == 0 && i->writers_waiting) i->slot_cv.notify_all();
-        }
-    } done{idx, lk};
-    unsigned char *const d = reinterpret_cast<unsigned char *>(idx->d_iobuf);
+    unsigned char *const d = turn.stage(L.total);
+    if (!d) return turn.rc;
     hipStream_t s = idx->stream;
-    const uint32_t n_deleted = idx->n_deleted;
-    lk.unlock();
+    turn.lk.unlock();
     KDB_HIP(hipMemcpyAsync(d, queries, L.qbytes, hipMemcpyHostToDevice, s));
     if (allow_bits) KDB_HIP(hipMemcpyAsync(d + L.o_allow, allow_bits, L.aw, hipMemcpyHostToDevice, s));
-    lk.lock();
-    uint64_t seq = 0;
-    int kind = 0;
+    turn.lk.lock();
+    DropWatch drops;
+    int rc;
     {
         KdbLaneGuard lane(idx, s);
         if (lane.rc) return lane.rc;
         rc = run(reinterpret_cast<float *>(d), allow_bits ? reinterpret_cast<uint64_t *>(d + L.o_allow) : nullptr, reinterpret_cast<uint32_t *>(d + L.o_ids),
                  reinterpret_cast<float *>(d + L.o_dist), reinterpret_cast<uint32_t *>(d + L.o_cnt), s, B);
-        seq = idx->launch_seq;
-        kind = idx->last_kind;
+        drops.note(idx);
     }
-    lk.unlock();
+    turn.lk.unlock();
     if (rc) return rc;
     KDB_HIP(hipMemcpyAsync(out_ids, d + L.o_ids, (size_t)B * k * 4, hipMemcpyDeviceToHost, s));
     KDB_HIP(hipMemcpyAsync(out_dist, d + L.o_dist, (size_t)B * k * dist_bytes, hipMemcpyDeviceToHost, s));
     KDB_HIP(hipMemcpyAsync(out_count, d + L.o_cnt, (size_t)B * 4, hipMemcpyDeviceToHost, s));
     KDB_HIP(hipStreamSynchronize(s));
-    if (fail_on_drop && n_deleted > 2047u && seq > 0 && kind == 1) {
-        unsigned long long c[4] = {0, 0, 0, 0};
-        KDB_HIP(hipMemcpy(c, idx->d_ctr + (size_t)((seq - 1) % kdb_index::RING) * 4, 32, hipMemcpyDeviceToHost));
-        if (c[3]) {
-            kdb_set_error("search: %llu pending traversal-only candidates were discarded (more than 2047 deleted nodes waiting in one "
-                          "walk): answers may differ from the reference's", c[3]);
-            return KDB_ERR_DIVERGED;
-        }
-    }
-    return KDB_OK;
+    return fail_on_drop ? drops.check(idx, "search") : KDB_OK;
 }
 
 // Host-pointer search of a large batch in chunks that alternate between two streams (and two scratch lanes): the
@@ -1627,39 +1683,23 @@ static int staged_big_call(kdb_index *idx, const float *queries, uint32_t B, uin
 // one chunk's launch start on the next.  SURVEY 8d counts the copies into the QPS of this entry point.
 static int search_staged_chunks(kdb_index *idx, const float *queries, uint32_t B, uint32_t k, uint32_t ef, const uint64_t *allow_bits,
                                 uint32_t flags, uint32_t *out_ids, float *out_dist, uint32_t *out_count, uint32_t chunk) {
-    std::lock_guard<std::mutex> big(idx->big_mu);
-    std::unique_lock<std::mutex> lk(idx->mu);
-    if (idx->writers_waiting) idx->slot_cv.wait(lk, [&] { return idx->writers_waiting == 0; });
+    HostTurn turn(idx, true); // (both streams: the destructor waits for stream2 as well)
     const size_t dist_bytes = (flags & KDB_SEARCH_DIST_F64) ? 8 : 4;
     const size_t dim = idx->desc.dim;
-    const size_t qbytes = (size_t)B * dim * 4;
-    const size_t aw = allow_bits ? ((size_t)(idx->count >> 6) + 1) * 8 : 0;
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const size_t ids_bytes = al((size_t)B * k * 4), dst_bytes = al((size_t)B * k * dist_bytes), cnt_bytes = al((size_t)B * 4);
-    int rc = ensure_iobuf(idx, al(qbytes) + al(aw) + ids_bytes + dst_bytes + cnt_bytes + 1024);
-    if (rc) return rc;
-    idx->inflight++;
-    // every exit -- the error paths too -- waits for both streams: queued copies read and write the CALLER's host buffers
-    struct Done {
-        kdb_index *i;
-        std::unique_lock<std::mutex> &l;
-        ~Done() {
-            if (l.owns_lock()) l.unlock();
-            (void)hipStreamSynchronize(i->stream);
-            (void)hipStreamSynchronize(i->stream2);
-            l.lock();
-            i->inflight--;
-            if (i->inflight == 0 && i->writers_waiting) i->slot_cv.notify_all();
-        }
-    } done{idx, lk};
-    unsigned char *p = reinterpret_cast<unsigned char *>(idx->d_iobuf);
-    float *d_q = reinterpret_cast<float *>(p);
-    uint64_t *d_allow = allow_bits ? reinterpret_cast<uint64_t *>(p + al(qbytes)) : nullptr;
-    uint32_t *d_ids = reinterpret_cast<uint32_t *>(p + al(qbytes) + al(aw));
-    unsigned char *d_dist = p + al(qbytes) + al(aw) + ids_bytes;
-    uint32_t *d_cnt = reinterpret_cast<uint32_t *>(d_dist + dst_bytes);
+    const size_t aw = allow_bits ? kdb_bits_bytes(idx->count) : 0;
+    KdbCarver cv;
+    const size_t o_q = cv.take((size_t)B * dim * 4), o_allow = cv.take(aw), o_ids = cv.take((size_t)B * k * 4), o_dist = cv.take((size_t)B * k * dist_bytes),
+                 o_cnt = cv.take((size_t)B * 4);
+    unsigned char *const p = turn.stage(cv.total() + 1024);
+    if (!p) return turn.rc;
+    int rc = KDB_OK;
+    float *d_q = reinterpret_cast<float *>(p + o_q);
+    uint64_t *d_allow = allow_bits ? reinterpret_cast<uint64_t *>(p + o_allow) : nullptr;
+    uint32_t *d_ids = reinterpret_cast<uint32_t *>(p + o_ids);
+    unsigned char *d_dist = p + o_dist;
+    uint32_t *d_cnt = reinterpret_cast<uint32_t *>(p + o_cnt);
     hipStream_t s1 = idx->stream, s2 = idx->stream2;
-    lk.unlock();
+    turn.lk.unlock();
     if (allow_bits) {
         KDB_HIP(hipMemcpyAsync(d_allow, allow_bits, aw, hipMemcpyHostToDevice, s1));
         KDB_HIP(hipEventRecord(idx->ev_io, s1));
@@ -1719,11 +1759,9 @@ extern "C" int kdb_search_batch_multi_dev(kdb_index *idx, const float *d_queries
         kdb_set_error("search_multi: KDB_SEARCH_DIST_F64 is an option of kdb_search_batch[_dev] and kdb_flat_scan_batch[_dev]");
         return KDB_ERR_INVALID;
     }
-    std::lock_guard<std::mutex> lk(idx->mu);
-    KDB_HIP(hipSetDevice(idx->device));
-    hipStream_t s = stream ? (hipStream_t)stream : idx->stream;
-    KdbLaneGuard lane(idx, s);
-    if (lane.rc) return lane.rc;
+    DevCall call(idx, stream);
+    if (call.rc) return call.rc;
+    hipStream_t s = call.s;
     if (G == 0 || !d_allow_lists || !d_allow_of_query) // no lists: the plain batch
         return search_dev_locked(idx, d_queries, B, k, ef, nullptr, flags, d_out_ids, d_out_dist, d_out_count, s);
     if (words_per_list < ((uint64_t)(idx->count >> 6) + 1)) {
@@ -1759,9 +1797,7 @@ extern "C" int kdb_search_batch(kdb_index *idx, const float *queries, uint32_t B
     auto run = [&](float *d_q, uint64_t *d_allow, uint32_t *d_ids, float *d_dist, uint32_t *d_cnt, hipStream_t s, uint32_t nq) {
         return search_dev_locked(idx, d_q, nq, k, ef, d_allow, flags, d_ids, d_dist, d_cnt, s);
     };
-    // (an upper bound of the layout: the allow list is sized by the count the caller saw)
-    const size_t need = (size_t)B * idx->desc.dim * 4 + (allow_bits ? ((size_t)(idx->cap >> 6) + 1) * 8 : 0) + (size_t)B * k * (4 + dist_bytes) + (size_t)B * 4 + 4096;
-    if (traced || (flags & KDB_SEARCH_FAIL_ON_DROP) || need > host_pin_max())
+    if (traced || (flags & KDB_SEARCH_FAIL_ON_DROP) || !fits_a_slot(idx, B, k, allow_bits != nullptr, dist_bytes))
         return staged_big_call(idx, queries, B, k, allow_bits, out_ids, out_dist, out_count, dist_bytes, (flags & KDB_SEARCH_FAIL_ON_DROP) != 0, run);
     static const uint32_t combine_max_b = [] { const char *e = getenv("KDB_COMBINE_MAX_B"); return e ? (uint32_t)atoi(e) : 16u; }();
     if (!allow_bits && B <= combine_max_b && B <= KDB_GROUP_CAP) return combined_search_call(idx, queries, B, k, ef, flags, out_ids, out_dist, out_count);
@@ -1873,11 +1909,9 @@ extern "C" int kdb_flat_scan_groups_dev(kdb_index *idx, const float *d_queries, 
         kdb_set_error("flat_scan_groups: KDB_SEARCH_DIST_F64 is an option of kdb_search_batch[_dev] and kdb_flat_scan_batch[_dev]");
         return KDB_ERR_INVALID;
     }
-    std::lock_guard<std::mutex> lk(idx->mu);
-    KDB_HIP(hipSetDevice(idx->device));
-    hipStream_t s = stream ? (hipStream_t)stream : idx->stream;
-    KdbLaneGuard lane(idx, s);
-    if (lane.rc) return lane.rc;
+    DevCall call(idx, stream);
+    if (call.rc) return call.rc;
+    hipStream_t s = call.s;
     if (words_per_list < ((uint64_t)(idx->count >> 6) + 1)) {
         kdb_set_error("flat_scan_groups: words_per_list %llu < (count>>6)+1", (unsigned long long)words_per_list);
         return KDB_ERR_INVALID;
@@ -1909,12 +1943,9 @@ extern "C" int kdb_flat_scan_batch_dev(kdb_index *idx, const float *d_queries, u
         kdb_set_error("flat_scan: null buffer");
         return KDB_ERR_INVALID;
     }
-    std::lock_guard<std::mutex> lk(idx->mu);
-    KDB_HIP(hipSetDevice(idx->device));
-    hipStream_t s = stream ? (hipStream_t)stream : idx->stream;
-    KdbLaneGuard lane(idx, s);
-    if (lane.rc) return lane.rc;
-    return flat_dev_locked(idx, d_queries, B, k, d_allow_bits, flags, d_out_ids, d_out_dist, d_out_count, s);
+    DevCall call(idx, stream);
+    if (call.rc) return call.rc;
+    return flat_dev_locked(idx, d_queries, B, k, d_allow_bits, flags, d_out_ids, d_out_dist, d_out_count, call.s);
 }
 
 extern "C" int kdb_flat_scan_batch(kdb_index *idx, const float *queries, uint32_t B, uint32_t k,
@@ -1931,8 +1962,7 @@ extern "C" int kdb_flat_scan_batch(kdb_index *idx, const float *queries, uint32_
     auto run = [&](float *d_q, uint64_t *d_allow, uint32_t *d_ids, float *d_dist, uint32_t *d_cnt, hipStream_t s, uint32_t nq) {
         return flat_dev_locked(idx, d_q, nq, k, d_allow, flags, d_ids, d_dist, d_cnt, s);
     };
-    const size_t need = (size_t)B * idx->desc.dim * 4 + (allow_bits ? ((size_t)(idx->cap >> 6) + 1) * 8 : 0) + (size_t)B * k * (4 + dist_bytes) + (size_t)B * 4 + 4096;
-    if (need > host_pin_max()) return staged_big_call(idx, queries, B, k, allow_bits, out_ids, out_dist, out_count, dist_bytes, false, run);
+    if (!fits_a_slot(idx, B, k, allow_bits != nullptr, dist_bytes)) return staged_big_call(idx, queries, B, k, allow_bits, out_ids, out_dist, out_count, dist_bytes, false, run);
     return staged_slot_call(idx, queries, B, k, allow_bits, out_ids, out_dist, out_count, dist_bytes, false, run);
 }
 
@@ -1959,11 +1989,9 @@ extern "C" int kdb_distance_batch_dev(kdb_index *idx, const float *d_queries, ui
         kdb_set_error("distance_batch: null buffer");
         return KDB_ERR_INVALID;
     }
-    std::lock_guard<std::mutex> lk(idx->mu);
-    KDB_HIP(hipSetDevice(idx->device));
-    KdbLaneGuard lane(idx, stream ? (hipStream_t)stream : idx->stream);
-    if (lane.rc) return lane.rc;
-    return distance_dev_locked(idx, d_queries, B, d_ids, C, flags, d_out, stream ? (hipStream_t)stream : idx->stream);
+    DevCall call(idx, stream);
+    if (call.rc) return call.rc;
+    return distance_dev_locked(idx, d_queries, B, d_ids, C, flags, d_out, call.s);
 }
 
 extern "C" int kdb_distance_batch(kdb_index *idx, const float *queries, uint32_t B, const uint32_t *ids, uint32_t C,
@@ -1975,41 +2003,26 @@ extern "C" int kdb_distance_batch(kdb_index *idx, const float *queries, uint32_t
         return KDB_ERR_INVALID;
     }
     KDB_HIP(hipSetDevice(idx->device));
-    // the index's own staging buffer, one such call at a time (big_mu); idx->mu only around the enqueue
-    std::lock_guard<std::mutex> big(idx->big_mu);
-    std::unique_lock<std::mutex> lk(idx->mu);
-    if (idx->writers_waiting) idx->slot_cv.wait(lk, [&] { return idx->writers_waiting == 0; });
-    const size_t qbytes = ((size_t)B * idx->desc.dim * 4 + 255) & ~(size_t)255;
-    const size_t ibytes = ((size_t)B * C * 4 + 255) & ~(size_t)255;
-    int rc = ensure_iobuf(idx, qbytes + 2 * ibytes + 256);
-    if (rc) return rc;
-    idx->inflight++;
-    struct Done {
-        kdb_index *i;
-        std::unique_lock<std::mutex> &l;
-        ~Done() {
-            if (l.owns_lock()) l.unlock();
-            (void)hipStreamSynchronize(i->stream);
-            l.lock();
-            i->inflight--;
-            if (i->inflight == 0 && i->writers_waiting) i->slot_cv.notify_all();
-        }
-    } done{idx, lk};
-    unsigned char *p = reinterpret_cast<unsigned char *>(idx->d_iobuf);
-    float *d_q = reinterpret_cast<float *>(p);
-    uint32_t *d_ids = reinterpret_cast<uint32_t *>(p + qbytes);
-    float *d_out = reinterpret_cast<float *>(p + qbytes + ibytes);
+    HostTurn turn(idx);
+    KdbCarver cv;
+    const size_t o_q = cv.take((size_t)B * idx->desc.dim * 4), o_ids = cv.take((size_t)B * C * 4), o_out = cv.take((size_t)B * C * 4);
+    unsigned char *const p = turn.stage(cv.total() + 256);
+    if (!p) return turn.rc;
+    float *d_q = reinterpret_cast<float *>(p + o_q);
+    uint32_t *d_ids = reinterpret_cast<uint32_t *>(p + o_ids);
+    float *d_out = reinterpret_cast<float *>(p + o_out);
     hipStream_t s = idx->stream;
-    lk.unlock();
+    turn.lk.unlock();
     KDB_HIP(hipMemcpyAsync(d_q, queries, (size_t)B * idx->desc.dim * 4, hipMemcpyHostToDevice, s));
     KDB_HIP(hipMemcpyAsync(d_ids, ids, (size_t)B * C * 4, hipMemcpyHostToDevice, s));
-    lk.lock();
+    turn.lk.lock();
+    int rc;
     {
         KdbLaneGuard lane(idx, s);
         if (lane.rc) return lane.rc;
         rc = distance_dev_locked(idx, d_q, B, d_ids, C, flags, d_out, s);
     }
-    lk.unlock();
+    turn.lk.unlock();
     if (rc) return rc;
     KDB_HIP(hipMemcpyAsync(out, d_out, (size_t)B * C * 4, hipMemcpyDeviceToHost, s));
     KDB_HIP(hipStreamSynchronize(s));
@@ -2046,13 +2059,13 @@ static int by_id_dev_locked(kdb_index *idx, bool flat, const uint32_t *d_ids, ui
     }
     const uint32_t kin = drop ? k + 1u : k;
     const size_t db = (flags & KDB_SEARCH_DIST_F64) ? 8 : 4;
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const size_t o_found = al((size_t)B * idx->desc.dim * 4), o_ids = o_found + al(B), o_dist = o_ids + al(drop ? (size_t)B * kin * 4 : 0),
-                 o_cnt = o_dist + al(drop ? (size_t)B * kin * db : 0), total = o_cnt + al(drop ? (size_t)B * 4 : 0);
-    int rc = ensure_byid(idx, total);
+    KdbCarver cv; // decoded rows | found flags | with drop: the inner call's k + 1 answers
+    const size_t o_q = cv.take((size_t)B * idx->desc.dim * 4), o_found = cv.take(B), o_ids = cv.take(drop ? (size_t)B * kin * 4 : 0),
+                 o_dist = cv.take(drop ? (size_t)B * kin * db : 0), o_cnt = cv.take(drop ? (size_t)B * 4 : 0);
+    int rc = ensure_byid(idx, cv.total());
     if (rc) return rc;
     unsigned char *const p = reinterpret_cast<unsigned char *>(idx->d_byid);
-    float *const d_q = reinterpret_cast<float *>(p);
+    float *const d_q = reinterpret_cast<float *>(p + o_q);
     uint8_t *const d_found = p + o_found;
     uint32_t *const i_ids = drop ? reinterpret_cast<uint32_t *>(p + o_ids) : d_out_ids;
     float *const i_dist = drop ? reinterpret_cast<float *>(p + o_dist) : d_out_dist;
@@ -2079,12 +2092,9 @@ static int by_id_dev_call(kdb_index *idx, bool flat, const uint32_t *d_ids, uint
         kdb_set_error("%s: null buffer", flat ? "flat_scan_by_id" : "search_by_id");
         return KDB_ERR_INVALID;
     }
-    std::lock_guard<std::mutex> lk(idx->mu);
-    KDB_HIP(hipSetDevice(idx->device));
-    hipStream_t s = stream ? (hipStream_t)stream : idx->stream;
-    KdbLaneGuard lane(idx, s);
-    if (lane.rc) return lane.rc;
-    return by_id_dev_locked(idx, flat, d_ids, B, k, ef, d_allow_bits, flags, d_out_ids, d_out_dist, d_out_count, s);
+    DevCall call(idx, stream);
+    if (call.rc) return call.rc;
+    return by_id_dev_locked(idx, flat, d_ids, B, k, ef, d_allow_bits, flags, d_out_ids, d_out_dist, d_out_count, call.s);
 }
 
 extern "C" int kdb_search_by_id_dev(kdb_index *idx, const uint32_t *d_ids, uint32_t B, uint32_t k, uint32_t ef, const uint64_t *d_allow_bits,
@@ -2096,9 +2106,8 @@ extern "C" int kdb_flat_scan_by_id_dev(kdb_index *idx, const uint32_t *d_ids, ui
     return by_id_dev_call(idx, true, d_ids, B, k, 0, d_allow_bits, flags, d_out_ids, d_out_dist, d_out_count, stream);
 }
 
-// Host pointers, modelled on kdb_distance_batch: the index's own staging buffer, one such call at a time (big_mu), idx->mu only
-// around the enqueue, the writers' protocol (writers_waiting / inflight).  What crosses the bus: 4 bytes per query in, the
-// answers out.  Never part of a combined group (the ids are not queries a group's kernel could read).
+// Host pointers: a turn on the staging buffer (HostTurn).  What crosses the bus: 4 bytes per query in, the answers out.  Never part
+// of a combined group (the ids are not queries a group's kernel could read).
 static int by_id_host_call(kdb_index *idx, bool flat, const uint32_t *ids, uint32_t B, uint32_t k, uint32_t ef, const uint64_t *allow_bits,
                            uint32_t flags, uint32_t *out_ids, void *out_dist, uint32_t *out_count) {
     KDB_CHECK_IDX(idx);
@@ -2108,62 +2117,36 @@ static int by_id_host_call(kdb_index *idx, bool flat, const uint32_t *ids, uint3
         return KDB_ERR_INVALID;
     }
     KDB_HIP(hipSetDevice(idx->device));
-    std::lock_guard<std::mutex> big(idx->big_mu);
-    std::unique_lock<std::mutex> lk(idx->mu);
-    close_expired_session(idx);
-    if (idx->writers_waiting) idx->slot_cv.wait(lk, [&] { return idx->writers_waiting == 0; });
+    HostTurn turn(idx);
     const size_t db = (flags & KDB_SEARCH_DIST_F64) ? 8 : 4;
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const size_t aw = allow_bits ? ((size_t)(idx->count >> 6) + 1) * 8 : 0;
-    const size_t o_allow = al((size_t)B * 4), o_ids = o_allow + al(aw), o_dist = o_ids + al((size_t)B * k * 4), o_cnt = o_dist + al((size_t)B * k * db);
-    int rc = ensure_iobuf(idx, o_cnt + al((size_t)B * 4));
-    if (rc) return rc;
-    idx->inflight++;
-    struct Done { // every exit: the stream is idle (queued copies touch the CALLER's buffers) and the call no longer counts
-        kdb_index *i;
-        std::unique_lock<std::mutex> &l;
-        ~Done() {
-            if (l.owns_lock()) l.unlock();
-            (void)hipStreamSynchronize(i->stream);
-            l.lock();
-            i->inflight--;
-            if (i->inflight == 0 && i->writers_waiting) i->slot_cv.notify_all();
-        }
-    } done{idx, lk};
-    unsigned char *const d = reinterpret_cast<unsigned char *>(idx->d_iobuf);
+    const size_t aw = allow_bits ? kdb_bits_bytes(idx->count) : 0;
+    KdbCarver cv;
+    const size_t o_src = cv.take((size_t)B * 4), o_allow = cv.take(aw), o_ids = cv.take((size_t)B * k * 4), o_dist = cv.take((size_t)B * k * db),
+                 o_cnt = cv.take((size_t)B * 4);
+    unsigned char *const d = turn.stage(cv.total());
+    if (!d) return turn.rc;
     hipStream_t s = idx->stream;
-    const uint32_t n_deleted = idx->n_deleted;
-    lk.unlock();
-    KDB_HIP(hipMemcpyAsync(d, ids, (size_t)B * 4, hipMemcpyHostToDevice, s));
+    turn.lk.unlock();
+    KDB_HIP(hipMemcpyAsync(d + o_src, ids, (size_t)B * 4, hipMemcpyHostToDevice, s));
     if (allow_bits) KDB_HIP(hipMemcpyAsync(d + o_allow, allow_bits, aw, hipMemcpyHostToDevice, s));
-    lk.lock();
-    uint64_t seq = 0;
-    int kind = 0;
+    turn.lk.lock();
+    DropWatch drops;
+    int rc;
     {
         KdbLaneGuard lane(idx, s);
         if (lane.rc) return lane.rc;
-        rc = by_id_dev_locked(idx, flat, reinterpret_cast<uint32_t *>(d), B, k, ef, allow_bits ? reinterpret_cast<uint64_t *>(d + o_allow) : nullptr,
+        rc = by_id_dev_locked(idx, flat, reinterpret_cast<uint32_t *>(d + o_src), B, k, ef, allow_bits ? reinterpret_cast<uint64_t *>(d + o_allow) : nullptr,
                               flags & ~(uint32_t)KDB_SEARCH_FAIL_ON_DROP, reinterpret_cast<uint32_t *>(d + o_ids), reinterpret_cast<float *>(d + o_dist),
                               reinterpret_cast<uint32_t *>(d + o_cnt), s);
-        seq = idx->launch_seq;
-        kind = idx->last_kind;
+        drops.note(idx);
     }
-    lk.unlock();
+    turn.lk.unlock();
     if (rc) return rc;
     KDB_HIP(hipMemcpyAsync(out_ids, d + o_ids, (size_t)B * k * 4, hipMemcpyDeviceToHost, s));
     KDB_HIP(hipMemcpyAsync(out_dist, d + o_dist, (size_t)B * k * db, hipMemcpyDeviceToHost, s));
     KDB_HIP(hipMemcpyAsync(out_count, d + o_cnt, (size_t)B * 4, hipMemcpyDeviceToHost, s));
     KDB_HIP(hipStreamSynchronize(s));
-    if (!flat && (flags & KDB_SEARCH_FAIL_ON_DROP) && n_deleted > 2047u && seq > 0 && kind == 1) { // as kdb_search_batch (staged_big_call)
-        unsigned long long c[4] = {0, 0, 0, 0};
-        KDB_HIP(hipMemcpy(c, idx->d_ctr + (size_t)((seq - 1) % kdb_index::RING) * 4, 32, hipMemcpyDeviceToHost));
-        if (c[3]) {
-            kdb_set_error("search_by_id: %llu pending traversal-only candidates were discarded (more than 2047 deleted nodes waiting in one "
-                          "walk): answers may differ from the reference's", c[3]);
-            return KDB_ERR_DIVERGED;
-        }
-    }
-    return KDB_OK;
+    return !flat && (flags & KDB_SEARCH_FAIL_ON_DROP) ? drops.check(idx, "search_by_id") : KDB_OK;
 }
 
 extern "C" int kdb_search_by_id(kdb_index *idx, const uint32_t *ids, uint32_t B, uint32_t k, uint32_t ef, const uint64_t *allow_bits, uint32_t flags,
@@ -2183,9 +2166,9 @@ extern "C" int kdb_index_decode_rows_dev(kdb_index *idx, const uint32_t *d_ids, 
         kdb_set_error("decode_rows: null buffer");
         return KDB_ERR_INVALID;
     }
-    std::lock_guard<std::mutex> lk(idx->mu);
-    KDB_HIP(hipSetDevice(idx->device));
-    return kdb_launch_decode_rows(kdb_make_view(idx), d_ids, n, d_out, d_out_found, 0u, stream ? (hipStream_t)stream : idx->stream);
+    DevCall call(idx, stream, false);
+    if (call.rc) return call.rc;
+    return kdb_launch_decode_rows(kdb_make_view(idx), d_ids, n, d_out, d_out_found, 0u, call.s);
 }
 
 extern "C" int kdb_index_decode_rows(kdb_index *idx, const uint32_t *ids, uint32_t n, float *out, uint8_t *out_found) {
@@ -2196,40 +2179,25 @@ extern "C" int kdb_index_decode_rows(kdb_index *idx, const uint32_t *ids, uint32
         return KDB_ERR_INVALID;
     }
     KDB_HIP(hipSetDevice(idx->device));
-    std::lock_guard<std::mutex> big(idx->big_mu);
-    std::unique_lock<std::mutex> lk(idx->mu);
-    close_expired_session(idx);
-    if (idx->writers_waiting) idx->slot_cv.wait(lk, [&] { return idx->writers_waiting == 0; });
+    HostTurn turn(idx);
     // in pieces of at most 64 MiB of vectors (VGetMany pages 500 ids; a caller that asks for a million rows must not make the
     // staging buffer as large as the index)
     const size_t row_b = (size_t)idx->desc.dim * 4;
     size_t per = ((size_t)64 << 20) / row_b;
     if (per < 1) per = 1;
     if (per > n) per = n;
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const size_t o_rows = al(per * 4), o_found = o_rows + al(per * row_b);
-    int rc = ensure_iobuf(idx, o_found + al(per));
-    if (rc) return rc;
-    idx->inflight++;
-    struct Done {
-        kdb_index *i;
-        std::unique_lock<std::mutex> &l;
-        ~Done() {
-            if (l.owns_lock()) l.unlock();
-            (void)hipStreamSynchronize(i->stream);
-            l.lock();
-            i->inflight--;
-            if (i->inflight == 0 && i->writers_waiting) i->slot_cv.notify_all();
-        }
-    } done{idx, lk};
-    unsigned char *const d = reinterpret_cast<unsigned char *>(idx->d_iobuf);
+    KdbCarver cv;
+    const size_t o_ids = cv.take(per * 4), o_rows = cv.take(per * row_b), o_found = cv.take(per);
+    unsigned char *const d = turn.stage(cv.total());
+    if (!d) return turn.rc;
     hipStream_t s = idx->stream;
-    const KdbView v = kdb_make_view(idx); // (inflight > 0 keeps writers out: count, rows and deleted bits cannot move)
-    lk.unlock();
+    const KdbView v = kdb_make_view(idx); // (the call is counted: writers stay out, count, rows and deleted bits cannot move)
+    turn.lk.unlock();
+    int rc;
     for (size_t i0 = 0; i0 < n; i0 += per) {
         const uint32_t m = (uint32_t)(n - i0 < per ? n - i0 : per);
-        KDB_HIP(hipMemcpyAsync(d, ids + i0, (size_t)m * 4, hipMemcpyHostToDevice, s));
-        rc = kdb_launch_decode_rows(v, reinterpret_cast<uint32_t *>(d), m, reinterpret_cast<float *>(d + o_rows), d + o_found, 0u, s);
+        KDB_HIP(hipMemcpyAsync(d + o_ids, ids + i0, (size_t)m * 4, hipMemcpyHostToDevice, s));
+        rc = kdb_launch_decode_rows(v, reinterpret_cast<uint32_t *>(d + o_ids), m, reinterpret_cast<float *>(d + o_rows), d + o_found, 0u, s);
         if (rc) return rc;
         KDB_HIP(hipMemcpyAsync(out + i0 * idx->desc.dim, d + o_rows, (size_t)m * row_b, hipMemcpyDeviceToHost, s));
         if (out_found) KDB_HIP(hipMemcpyAsync(out_found + i0, d + o_found, m, hipMemcpyDeviceToHost, s));
@@ -2271,36 +2239,11 @@ extern "C" int kdb_consensus_batch_dev(kdb_index *idx, const uint32_t *d_ids, co
     int rc = consensus_check("consensus", B, stride, flags, d_ids, d_queries, d_out, d_out_similarity);
     if (rc) return rc;
     if (B == 0) return KDB_OK;
-    std::lock_guard<std::mutex> lk(idx->mu);
-    KDB_HIP(hipSetDevice(idx->device));
+    DevCall call(idx, stream, false);
+    if (call.rc) return call.rc;
     return kdb_launch_consensus(kdb_make_view(idx), d_ids, d_counts, B, stride, d_queries, reinterpret_cast<const uint32_t *>(d_active_bits), d_out,
-                                d_out_similarity, d_out_centroid, d_out_gram, stream ? (hipStream_t)stream : idx->stream);
+                                d_out_similarity, d_out_centroid, d_out_gram, call.s);
 }
-
-// the shared frame of the two host-pointer forms: one such call at a time on the index's staging buffer (big_mu), idx->mu only around
-// the enqueue, the writers' protocol (writers_waiting / inflight) -- as by_id_host_call
-struct HostTurn {
-    kdb_index *idx;
-    std::lock_guard<std::mutex> big;
-    std::unique_lock<std::mutex> lk;
-    bool counted = false;
-    explicit HostTurn(kdb_index *i) : idx(i), big(i->big_mu), lk(i->mu) {
-        close_expired_session(idx);
-        if (idx->writers_waiting) idx->slot_cv.wait(lk, [&] { return idx->writers_waiting == 0; });
-    }
-    void begin() {
-        idx->inflight++;
-        counted = true;
-    }
-    ~HostTurn() { // every exit: the stream is idle (queued copies touch the CALLER's buffers) and the call no longer counts
-        if (!counted) return;
-        if (lk.owns_lock()) lk.unlock();
-        (void)hipStreamSynchronize(idx->stream);
-        lk.lock();
-        idx->inflight--;
-        if (idx->inflight == 0 && idx->writers_waiting) idx->slot_cv.notify_all();
-    }
-};
 
 extern "C" int kdb_consensus_batch(kdb_index *idx, const uint32_t *ids, const uint32_t *counts, uint32_t B, uint32_t stride, const float *queries,
                                    const uint64_t *active_bits, uint32_t flags, kdb_consensus *out, double *out_similarity, float *out_centroid,
@@ -2317,24 +2260,22 @@ extern "C" int kdb_consensus_batch(kdb_index *idx, const uint32_t *ids, const ui
     if (B == 0) return KDB_OK;
     KDB_HIP(hipSetDevice(idx->device));
     HostTurn turn(idx);
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
     const size_t dim = idx->desc.dim, gw = (size_t)stride + 1;
-    const size_t aw = active_bits ? ((size_t)(idx->count >> 6) + 1) * 8 : 0;
-    const size_t o_cnt = al((size_t)B * stride * 4), o_q = o_cnt + al(counts ? (size_t)B * 4 : 0), o_act = o_q + al(queries ? (size_t)B * dim * 4 : 0),
-                 o_out = o_act + al(aw), o_sim = o_out + al((size_t)B * sizeof(kdb_consensus)), o_cen = o_sim + al(out_similarity ? (size_t)B * stride * 8 : 0),
-                 o_gram = o_cen + al(out_centroid ? (size_t)B * dim * 4 : 0), total = o_gram + al(out_gram ? (size_t)B * gw * gw * 8 : 0);
-    rc = ensure_iobuf(idx, total);
-    if (rc) return rc;
-    turn.begin();
-    unsigned char *const d = reinterpret_cast<unsigned char *>(idx->d_iobuf);
+    const size_t aw = active_bits ? kdb_bits_bytes(idx->count) : 0;
+    KdbCarver cv;
+    const size_t o_ids = cv.take((size_t)B * stride * 4), o_cnt = cv.take(counts ? (size_t)B * 4 : 0), o_q = cv.take(queries ? (size_t)B * dim * 4 : 0),
+                 o_act = cv.take(aw), o_out = cv.take((size_t)B * sizeof(kdb_consensus)), o_sim = cv.take(out_similarity ? (size_t)B * stride * 8 : 0),
+                 o_cen = cv.take(out_centroid ? (size_t)B * dim * 4 : 0), o_gram = cv.take(out_gram ? (size_t)B * gw * gw * 8 : 0);
+    unsigned char *const d = turn.stage(cv.total());
+    if (!d) return turn.rc;
     hipStream_t s = idx->stream;
-    const KdbView v = kdb_make_view(idx); // (inflight > 0 keeps writers out: count, rows and deleted bits cannot move)
+    const KdbView v = kdb_make_view(idx); // (the call is counted: writers stay out, count, rows and deleted bits cannot move)
     turn.lk.unlock();
-    if (stride) KDB_HIP(hipMemcpyAsync(d, ids, (size_t)B * stride * 4, hipMemcpyHostToDevice, s));
+    if (stride) KDB_HIP(hipMemcpyAsync(d + o_ids, ids, (size_t)B * stride * 4, hipMemcpyHostToDevice, s));
     if (counts) KDB_HIP(hipMemcpyAsync(d + o_cnt, counts, (size_t)B * 4, hipMemcpyHostToDevice, s));
     if (queries) KDB_HIP(hipMemcpyAsync(d + o_q, queries, (size_t)B * dim * 4, hipMemcpyHostToDevice, s));
     if (active_bits) KDB_HIP(hipMemcpyAsync(d + o_act, active_bits, aw, hipMemcpyHostToDevice, s));
-    rc = kdb_launch_consensus(v, reinterpret_cast<uint32_t *>(d), counts ? reinterpret_cast<uint32_t *>(d + o_cnt) : nullptr, B, stride,
+    rc = kdb_launch_consensus(v, reinterpret_cast<uint32_t *>(d + o_ids), counts ? reinterpret_cast<uint32_t *>(d + o_cnt) : nullptr, B, stride,
                               queries ? reinterpret_cast<float *>(d + o_q) : nullptr, active_bits ? reinterpret_cast<uint32_t *>(d + o_act) : nullptr,
                               reinterpret_cast<kdb_consensus *>(d + o_out), out_similarity ? reinterpret_cast<double *>(d + o_sim) : nullptr,
                               out_centroid ? reinterpret_cast<float *>(d + o_cen) : nullptr, out_gram ? reinterpret_cast<double *>(d + o_gram) : nullptr, s);
@@ -2380,12 +2321,10 @@ extern "C" int kdb_belief_batch_dev(kdb_index *idx, const float *d_queries, uint
     int rc = belief_check(B, k, flags, d_queries, d_out_ids, d_out_dist, d_out_count, d_out);
     if (rc) return rc;
     if (B == 0) return KDB_OK;
-    std::lock_guard<std::mutex> lk(idx->mu);
-    KDB_HIP(hipSetDevice(idx->device));
-    hipStream_t s = stream ? (hipStream_t)stream : idx->stream;
-    KdbLaneGuard lane(idx, s);
-    if (lane.rc) return lane.rc;
-    return belief_dev_locked(idx, d_queries, B, k, ef, d_allow_bits, d_active_bits, flags, d_out_ids, d_out_dist, d_out_count, d_out, d_out_similarity, s);
+    DevCall call(idx, stream);
+    if (call.rc) return call.rc;
+    return belief_dev_locked(idx, d_queries, B, k, ef, d_allow_bits, d_active_bits, flags, d_out_ids, d_out_dist, d_out_count, d_out, d_out_similarity,
+                             call.s);
 }
 
 extern "C" int kdb_belief_batch(kdb_index *idx, const float *queries, uint32_t B, uint32_t k, uint32_t ef, const uint64_t *allow_bits,
@@ -2398,33 +2337,28 @@ extern "C" int kdb_belief_batch(kdb_index *idx, const float *queries, uint32_t B
     KDB_HIP(hipSetDevice(idx->device));
     HostTurn turn(idx);
     const size_t db = (flags & KDB_SEARCH_DIST_F64) ? 8 : 4;
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const size_t bw = ((size_t)(idx->count >> 6) + 1) * 8;
-    const size_t o_allow = al((size_t)B * idx->desc.dim * 4), o_act = o_allow + al(allow_bits ? bw : 0), o_ids = o_act + al(active_bits ? bw : 0),
-                 o_dist = o_ids + al((size_t)B * k * 4), o_cnt = o_dist + al((size_t)B * k * db), o_out = o_cnt + al((size_t)B * 4),
-                 o_sim = o_out + al((size_t)B * sizeof(kdb_consensus)), total = o_sim + al(out_similarity ? (size_t)B * k * 8 : 0);
-    rc = ensure_iobuf(idx, total);
-    if (rc) return rc;
-    turn.begin();
-    unsigned char *const d = reinterpret_cast<unsigned char *>(idx->d_iobuf);
+    const size_t bw = kdb_bits_bytes(idx->count);
+    KdbCarver cv;
+    const size_t o_q = cv.take((size_t)B * idx->desc.dim * 4), o_allow = cv.take(allow_bits ? bw : 0), o_act = cv.take(active_bits ? bw : 0),
+                 o_ids = cv.take((size_t)B * k * 4), o_dist = cv.take((size_t)B * k * db), o_cnt = cv.take((size_t)B * 4),
+                 o_out = cv.take((size_t)B * sizeof(kdb_consensus)), o_sim = cv.take(out_similarity ? (size_t)B * k * 8 : 0);
+    unsigned char *const d = turn.stage(cv.total());
+    if (!d) return turn.rc;
     hipStream_t s = idx->stream;
-    const uint32_t n_deleted = idx->n_deleted;
     turn.lk.unlock();
-    KDB_HIP(hipMemcpyAsync(d, queries, (size_t)B * idx->desc.dim * 4, hipMemcpyHostToDevice, s));
+    KDB_HIP(hipMemcpyAsync(d + o_q, queries, (size_t)B * idx->desc.dim * 4, hipMemcpyHostToDevice, s));
     if (allow_bits) KDB_HIP(hipMemcpyAsync(d + o_allow, allow_bits, bw, hipMemcpyHostToDevice, s));
     if (active_bits) KDB_HIP(hipMemcpyAsync(d + o_act, active_bits, bw, hipMemcpyHostToDevice, s));
     turn.lk.lock();
-    uint64_t seq = 0;
-    int kind = 0;
+    DropWatch drops;
     {
         KdbLaneGuard lane(idx, s);
         if (lane.rc) return lane.rc;
-        rc = belief_dev_locked(idx, reinterpret_cast<float *>(d), B, k, ef, allow_bits ? reinterpret_cast<uint64_t *>(d + o_allow) : nullptr,
+        rc = belief_dev_locked(idx, reinterpret_cast<float *>(d + o_q), B, k, ef, allow_bits ? reinterpret_cast<uint64_t *>(d + o_allow) : nullptr,
                                active_bits ? reinterpret_cast<uint64_t *>(d + o_act) : nullptr, flags & ~(uint32_t)KDB_SEARCH_FAIL_ON_DROP,
                                reinterpret_cast<uint32_t *>(d + o_ids), reinterpret_cast<float *>(d + o_dist), reinterpret_cast<uint32_t *>(d + o_cnt),
                                reinterpret_cast<kdb_consensus *>(d + o_out), out_similarity ? reinterpret_cast<double *>(d + o_sim) : nullptr, s);
-        seq = idx->launch_seq;
-        kind = idx->last_kind;
+        drops.note(idx);
     }
     turn.lk.unlock();
     if (rc) return rc;
@@ -2434,16 +2368,7 @@ extern "C" int kdb_belief_batch(kdb_index *idx, const float *queries, uint32_t B
     KDB_HIP(hipMemcpyAsync(out, d + o_out, (size_t)B * sizeof(kdb_consensus), hipMemcpyDeviceToHost, s));
     if (out_similarity) KDB_HIP(hipMemcpyAsync(out_similarity, d + o_sim, (size_t)B * k * 8, hipMemcpyDeviceToHost, s));
     KDB_HIP(hipStreamSynchronize(s));
-    if ((flags & KDB_SEARCH_FAIL_ON_DROP) && n_deleted > 2047u && seq > 0 && kind == 1) { // as kdb_search_batch (staged_big_call)
-        unsigned long long c[4] = {0, 0, 0, 0};
-        KDB_HIP(hipMemcpy(c, idx->d_ctr + (size_t)((seq - 1) % kdb_index::RING) * 4, 32, hipMemcpyDeviceToHost));
-        if (c[3]) {
-            kdb_set_error("belief: %llu pending traversal-only candidates were discarded (more than 2047 deleted nodes waiting in one walk): answers "
-                          "may differ from the reference's", c[3]);
-            return KDB_ERR_DIVERGED;
-        }
-    }
-    return KDB_OK;
+    return (flags & KDB_SEARCH_FAIL_ON_DROP) ? drops.check(idx, "belief") : KDB_OK;
 }
 
 extern "C" int kdb_index_build(kdb_index *idx, uint32_t count, const kdb_build_params *params) {
@@ -2544,22 +2469,22 @@ extern "C" int kdb_test_select_neighbors(kdb_index *idx, uint32_t n_lists, uint3
                 return KDB_ERR_INVALID;
             }
     }
-    std::lock_guard<std::mutex> lk(idx->mu);
-    KDB_HIP(hipSetDevice(idx->device));
-    hipStream_t s = idx->stream;
-    KdbLaneGuard lane(idx, s);
-    if (lane.rc) return lane.rc;
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    DevCall call(idx, nullptr);
+    if (call.rc) return call.rc;
+    hipStream_t s = call.s;
     const size_t nb = (size_t)n_lists * stride * 4;
     const size_t kb = (size_t)n_lists * stride * (idx->desc.precision == KDB_PREC_I8 ? 8 : 4); // int8: float64 distances
-    int rc = kdb_ensure_scratch(idx, al(nb) + al(kb) + al((size_t)n_lists * 4) * 2 + al((size_t)n_lists * maxm * 4) + 256);
+    KdbCarver cv;
+    const size_t o_keys = cv.take(kb), o_ids = cv.take(nb), o_cnt = cv.take((size_t)n_lists * 4), o_ocnt = cv.take((size_t)n_lists * 4), // (8-byte keys first)
+                 o_oid = cv.take((size_t)n_lists * maxm * 4);
+    int rc = kdb_ensure_scratch(idx, cv.total() + 256);
     if (rc) return rc;
     unsigned char *b = reinterpret_cast<unsigned char *>(idx->d_scratch);
-    void *d_keys = b; // (8-byte keys first)
-    uint32_t *d_ids = reinterpret_cast<uint32_t *>(b + al(kb));
-    uint32_t *d_cnt = reinterpret_cast<uint32_t *>(b + al(kb) + al(nb));
-    uint32_t *d_ocnt = reinterpret_cast<uint32_t *>(b + al(kb) + al(nb) + al((size_t)n_lists * 4));
-    uint32_t *d_oid = reinterpret_cast<uint32_t *>(b + al(kb) + al(nb) + 2 * al((size_t)n_lists * 4));
+    void *d_keys = b + o_keys;
+    uint32_t *d_ids = reinterpret_cast<uint32_t *>(b + o_ids);
+    uint32_t *d_cnt = reinterpret_cast<uint32_t *>(b + o_cnt);
+    uint32_t *d_ocnt = reinterpret_cast<uint32_t *>(b + o_ocnt);
+    uint32_t *d_oid = reinterpret_cast<uint32_t *>(b + o_oid);
     KDB_HIP(hipMemcpyAsync(d_ids, cand_ids, nb, hipMemcpyHostToDevice, s));
     KDB_HIP(hipMemcpyAsync(d_keys, cand_keys, kb, hipMemcpyHostToDevice, s));
     KDB_HIP(hipMemcpyAsync(d_cnt, cand_cnt, (size_t)n_lists * 4, hipMemcpyHostToDevice, s));
@@ -2639,9 +2564,9 @@ extern "C" int kdb_merge_topk_dev(kdb_index *idx, uint32_t G, uint32_t B, uint32
                                   const float *d_in_dist, const uint32_t *d_in_count, const uint32_t *d_id_base,
                                   uint32_t *d_out_ids, float *d_out_dist, uint32_t *d_out_count, void *stream) {
     KDB_CHECK_IDX(idx);
-    std::lock_guard<std::mutex> lk(idx->mu);
-    KDB_HIP(hipSetDevice(idx->device));
-    hipStream_t s = stream ? (hipStream_t)stream : idx->stream;
+    DevCall call(idx, stream, false);
+    if (call.rc) return call.rc;
+    hipStream_t s = call.s;
     const int negate = idx->desc.metric == KDB_METRIC_COSINE && idx->desc.precision == KDB_PREC_F32;
     return kdb_launch_merge_topk(negate, G, B, k, d_in_ids, d_in_dist, d_in_count, 0, 0, d_id_base, d_out_ids, d_out_dist,
                                  d_out_count, s);
@@ -2657,9 +2582,9 @@ extern "C" int kdb_merge_topk_packed_dev(kdb_index *idx, uint32_t G, uint32_t B,
                       (unsigned long long)block);
         return KDB_ERR_INVALID;
     }
-    std::lock_guard<std::mutex> lk(idx->mu);
-    KDB_HIP(hipSetDevice(idx->device));
-    hipStream_t s = stream ? (hipStream_t)stream : idx->stream;
+    DevCall call(idx, stream, false);
+    if (call.rc) return call.rc;
+    hipStream_t s = call.s;
     const int negate = idx->desc.metric == KDB_METRIC_COSINE && idx->desc.precision == KDB_PREC_F32;
     const size_t bk = (size_t)B * k;
     return kdb_launch_merge_topk(negate, G, B, k, d_packed, reinterpret_cast<const float *>(d_packed + bk), d_packed + 2 * bk,
@@ -2678,9 +2603,9 @@ extern "C" int kdb_merge_topk_packed_f64_dev(kdb_index *idx, uint32_t G, uint32_
                       (unsigned long long)block);
         return KDB_ERR_INVALID;
     }
-    std::lock_guard<std::mutex> lk(idx->mu);
-    KDB_HIP(hipSetDevice(idx->device));
-    hipStream_t s = stream ? (hipStream_t)stream : idx->stream;
+    DevCall call(idx, stream, false);
+    if (call.rc) return call.rc;
+    hipStream_t s = call.s;
     const size_t bk = (size_t)B * k;
     return kdb_launch_merge_topk_f64(G, B, k, d_packed + 2 * bk, reinterpret_cast<const double *>(d_packed), d_packed + 3 * bk, (size_t)stride_words,
                                      (size_t)stride_words / 2, (size_t)stride_words, d_id_base, d_out_ids, d_out_dist, 1, d_out_count, s);

@@ -98,6 +98,19 @@ def test_micro_batcher_against_oracle(tmp_path, oracle):
     assert r.stdout.strip().splitlines()[-1].startswith("ok"), r.stdout   # (the lines before it report the direct callers' launches)
 
 
+def test_staging_buffer_layout_under_address_and_ub_sanitizers(tmp_path):
+    """the carver that lays out every staging buffer (kektordb_amd/csrc/kdb_stage.h), alone in a program of its own: regions aligned,
+    in order, never overlapping, empty ones free, 64-bit offsets exact, and the bitset size equal to the expression it replaced"""
+    exe = str(tmp_path / "stage_layout_test")
+    cmd = ["g++", "-std=c++17", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+           "-I", os.path.join(ROOT, "kektordb_amd", "csrc"), os.path.join(ROOT, "tests", "cpp", "stage_layout_test.cpp"), "-o", exe]
+    p = subprocess.run(cmd, capture_output=True, text=True)
+    assert p.returncode == 0, p.stderr
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
+    assert r.stdout.strip() == "ok" and not r.stderr, (r.stdout, r.stderr[-4000:])
+
+
 def test_micro_batcher_logic_under_thread_sanitizer(tmp_path):
     """the batcher's grouping / leader / turn-taking / Stop() logic on a test double, built with -fsanitize=thread
     (the reference runs its concurrency tests under the race detector): no report, every caller gets

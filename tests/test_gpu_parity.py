@@ -1516,6 +1516,44 @@ def test_dropped_candidates_are_reported(oracle, hip):
     assert np.array_equal(a[0], b[0])
 
 
+def test_dropped_candidates_fail_search_by_id_and_belief(oracle, hip):
+    """KDB_SEARCH_FAIL_ON_DROP on the two other host-pointer entry points that honour it, on the index of
+    test_dropped_candidates_are_reported: kdb_search_by_id with 32 live ids as the sources, kdb_belief_batch with their stored
+    rows as the queries"""
+    n, dim, k, ef = 12000, 16, 10, 300
+    X = make_corpus(n, dim, "normal", seed=77)
+    rng = np.random.default_rng(78)
+    idx = hip.HipIndex(dim, 0, 0, 16, 40, capacity=n + 8)
+    idx.upload_rows(X, 1)
+    idx.build(n, batch=512, ef_construction=40, seed=3)
+    levels = idx.download_graph()[3]
+    lvl0 = np.nonzero(levels[1:n + 1] == 0)[0] + 1
+    deleted = rng.choice(lvl0, lvl0.size - 300, replace=False)
+    idx.Delete(deleted.tolist())
+    live = np.setdiff1d(np.arange(1, n + 1), deleted)
+    src = rng.choice(live, 32, replace=False).astype(np.uint32)
+    Q = X[src - 1]
+    # the precondition: the walks do discard candidates (a quiet index would let a missing check pass)
+    ids, dist, cnt = idx.search_by_id(src, k, ef)
+    assert np.all(cnt == k) and not (set(ids.flatten().tolist()) & set(deleted.tolist()))
+    assert idx.counters()["n_dropped"] > 0
+    with pytest.raises(hip.KdbError) as e:
+        idx.search_by_id(src, k, ef, fail_on_drop=True)
+    assert "status -7" in str(e.value) and "discarded" in str(e.value)
+    with pytest.raises(hip.KdbError) as e:
+        idx.belief(Q, k, ef, fail_on_drop=True)
+    assert "status -7" in str(e.value) and "discarded" in str(e.value)
+    # walks that stay below the limit: the flag changes nothing
+    a = idx.search_by_id(src, k, 40, fail_on_drop=True)
+    assert idx.counters()["n_dropped"] == 0
+    b = idx.search_by_id(src, k, 40)
+    assert np.array_equal(a[0], b[0])
+    a = idx.belief(Q, k, 40, fail_on_drop=True)
+    assert idx.counters()["n_dropped"] == 0
+    b = idx.belief(Q, k, 40)
+    assert np.array_equal(a[0], b[0])
+
+
 @pytest.mark.parametrize("metric,prec,dim", [(0, 0, 128), (1, 0, 768), (0, 1, 40), (1, 2, 96)])
 def test_flat_scan_k_above_128(oracle, hip, metric, prec, dim):
     """BruteForceIndex.SearchWithScores has no bound on k (vector_index.go:104-140); round 3 stopped at 128.  k = 129 .. 1024 take

@@ -10,7 +10,8 @@ answer is that of the existing entry point for that float32 vector.  So the bars
      not-found sources are checked against "count 0, zero ids" instead;
   3. = the oracle's search of the decoded vector under ARITH_HIP_WAVE, ids, distance bits and per-query counters: the 203-id lists
      with n_tied == 0, every id in one call under KDB_SEARCH_HEAP_ORDER (float32 distances collide somewhere among thousands of walks);
-  4. not-found sources; 5. KDB_BY_ID_DROP_SELF = the host-side composition of the k + 1 call; 6. concurrent callers.
+  4. not-found sources; 5. KDB_BY_ID_DROP_SELF = the host-side composition of the k + 1 call; 6. concurrent callers, and a writer
+     against the calls that take turns on the index's staging buffer.
 
 Graphs come from OracleIndex.add (tests/test_gpu_refine.py's Case: m = 8, efC = 40, unique rows), built once per process."""
 import functools
@@ -394,6 +395,61 @@ def test_concurrent_by_id_and_query_callers_on_one_handle():
     for t in th:
         t.join()
     assert not bad, bad[:5]
+
+
+def test_writers_against_the_calls_that_take_turns_on_the_staging_buffer():
+    """four readers x 200 rounds of distance_batch, decode_rows, consensus and flat_scan_by_id (each takes a turn on the index's
+    staging buffer) while a writer alternates mark_deleted and upload_norms: every answer is the one computed before the threads
+    started, bit for bit, and nobody is left waiting.  The writer's ids are deleted already and it uploads the norms they have, so
+    the index of the other tests stays as it was; the readers' ids are live ones."""
+    S = setup("D")
+    idx, c = S.idx, S.case
+    rng = np.random.default_rng(12)
+    mine = rng.choice(S.live, 24, replace=False).astype(np.uint32)
+    theirs = S.dead[:6]
+    Q = (S.wide[mine[:3]] + np.float32(0.01)).astype(np.float32)
+    calls = [lambda: (idx.distance_batch(Q, mine.reshape(3, 8)),),
+             lambda: idx.decode_rows(mine),
+             lambda: tuple(v for v in idx.consensus(mine.reshape(3, 8), None, Q, None, want_centroid=True).values() if v is not None),
+             lambda: idx.flat_scan_by_id(mine[:8], 5)]
+    want = [call() for call in calls]
+    assert S.idx.decode_rows(mine)[1].all() and not S.found(theirs).any()
+    bad, stop = [], threading.Event()
+
+    def reader(t):
+        try:
+            for it in range(200):
+                for j in range(len(calls)):
+                    if not all(same(a, b) for a, b in zip(calls[j](), want[j])):
+                        bad.append(("reader", t, it, j))
+        except Exception as e:                                  # (a thread's exception must fail the test, not vanish)
+            bad.append(("reader", t, repr(e)))
+
+    def writer():
+        try:
+            it = 0
+            while not stop.is_set():
+                d = int(theirs[it % len(theirs)])
+                if it & 1:
+                    idx.upload_norms(c.norms[d:d + 1], d)
+                else:
+                    idx.Delete(theirs[it % 3:it % 3 + 3].tolist())
+                it += 1
+        except Exception as e:
+            bad.append(("writer", repr(e)))
+
+    rd = [threading.Thread(target=reader, args=(t,), daemon=True) for t in range(4)]
+    wr = threading.Thread(target=writer, daemon=True)
+    wr.start()
+    for t in rd:
+        t.start()
+    for t in rd:
+        t.join(60)
+    stop.set()
+    wr.join(60)
+    assert not any(t.is_alive() for t in rd + [wr])
+    assert not bad, bad[:5]
+    assert all(all(same(a, b) for a, b in zip(calls[j](), want[j])) for j in range(len(calls)))   # and serially afterwards
 
 
 def test_vsearchsimilar_is_searchwithscores_per_id():
