@@ -692,6 +692,17 @@ KDB_API int kdb_probe_stream(kdb_index *idx, int which, float *ms, uint64_t *byt
  * waits.  LDS keeps what the previous kernel left; called between launches it makes a kernel that reads LDS it never wrote show
  * (the parity tests of the exact scan use it: a race of that kind survived the suite until HBM and LDS were poisoned).  Blocking. */
 KDB_API int kdb_probe_poison_lds(kdb_index *idx, uint32_t pattern);
+/* TEST HOOK: which kernel the last `last_n` (<= 64) launches ran, oldest first -- the same launches, in the same order, as
+ * kdb_get_launch_stats.  out[last_n][KDB_LAUNCH_SHAPE_WORDS], all zero for a launch that was not a graph search:
+ *   [0] 1 = a graph search                     [1] precision   [2] metric
+ *   [3] row-width unroll NCH (ld = 64 * NCH; 0 = any width)     [4] beam slots BS (1 / 2 / 4 in registers, 0 = the LDS beam)
+ *   [5] words of the LDS visited hash (0 = the HBM bitset alone) [6] waves per query (1 / 2 / 4)
+ *   [7] 1 = the planes kernel                  [8] 1 = heap-order pass armed (KDB_SEARCH_HEAP_ORDER)
+ *   [9] that pass's NCH   [10] its LDS hash words   [11] 1 = its result heap in registers   [12] 1 = it runs beside the search kernel
+ *   [13] workgroups of the search kernel       [14] its LDS bytes per workgroup      [15] queries
+ * Host-side bookkeeping only: the tests use it to assert that a case reached the template instantiation it was written for.   */
+#define KDB_LAUNCH_SHAPE_WORDS 16u
+KDB_API int kdb_probe_launch_shape(kdb_index *idx, uint32_t last_n, uint32_t *out);
 
 KDB_API int kdb_get_counters(kdb_index *idx, kdb_counters *out);
 /* Statistics of the last `last_n` (<= 64) search / flat-scan / distance launches, oldest first: each

@@ -208,6 +208,7 @@ unsigned long long *kdb_stats_begin(kdb_index *idx, int kind, uint32_t B, uint32
     idx->ring_timed[slot] = kind != 1 || idx->time_launches;
     idx->ring_B[slot] = B;
     idx->ring_C[slot] = C;
+    memset(idx->ring_shape[slot], 0, sizeof idx->ring_shape[slot]);
     idx->last_kind = kind;
     idx->last_B = B;
     idx->last_C = C;
@@ -2669,6 +2670,21 @@ extern "C" int kdb_get_launch_stats(kdb_index *idx, uint32_t last_n, kdb_counter
         const uint64_t seq = idx->launch_seq - last_n + i;
         int rc = stats_of_slot(idx, (uint32_t)(seq % kdb_index::RING), out + i);
         if (rc) return rc;
+    }
+    return KDB_OK;
+}
+
+// TEST HOOK: the launch shapes of the same slots (host words, written under mu by the launch itself: nothing to wait for)
+extern "C" int kdb_probe_launch_shape(kdb_index *idx, uint32_t last_n, uint32_t *out) {
+    KDB_CHECK_IDX(idx);
+    std::lock_guard<std::mutex> lk(idx->mu);
+    if (!out || last_n == 0 || last_n > kdb_index::RING || last_n > idx->launch_seq) {
+        kdb_set_error("probe_launch_shape: last_n must be 1..min(%u, launches so far)", kdb_index::RING);
+        return KDB_ERR_INVALID;
+    }
+    for (uint32_t i = 0; i < last_n; i++) {
+        const uint64_t seq = idx->launch_seq - last_n + i;
+        memcpy(out + (size_t)i * KDB_LAUNCH_SHAPE_WORDS, idx->ring_shape[seq % kdb_index::RING], sizeof idx->ring_shape[0]);
     }
     return KDB_OK;
 }

@@ -207,6 +207,9 @@ struct kdb_index {
     bool ring_timed[RING] = {};
     bool time_launches = true;  // HIP events around the graph-search kernel (kdb_index_set_launch_timing)
     uint32_t ring_B[RING] = {}, ring_C[RING] = {};
+    // which hnsw_search_kernel (and heap_walk_kernel) a graph-search launch took: the words of kdb_probe_launch_shape (test hook),
+    // written by launch_search_bs / kdb_launch_heap_walk for the slot kdb_stats_begin has just opened; zero for every other kind
+    uint32_t ring_shape[RING][KDB_LAUNCH_SHAPE_WORDS] = {};
     uint64_t launch_seq = 0;
     std::mutex mu;
     // concurrent host-pointer calls (see kdb_slot): all guarded by mu
@@ -288,6 +291,8 @@ int kdb_ensure_visited(kdb_index *idx, uint32_t slots, hipStream_t s);
 int kdb_ensure_group_entries(kdb_index *idx, uint32_t n);
 // start a new statistics slot: selects ring events (idx->ev0/ev1) and returns the slot's counter words
 unsigned long long *kdb_stats_begin(kdb_index *idx, int kind, uint32_t B, uint32_t C);
+// the launch-shape words of the slot kdb_stats_begin opened last (kdb_probe_launch_shape); under idx->mu like the slot itself
+inline uint32_t *kdb_stats_shape(kdb_index *idx) { return idx->ring_shape[(idx->launch_seq - 1) % kdb_index::RING]; }
 
 // ---- kernel launchers (each defined next to its kernels) --------------------------------------
 // search.hip

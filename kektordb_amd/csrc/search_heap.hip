@@ -710,11 +710,12 @@ int heap_occupancy(K kern, size_t lds) { // resident workgroups per CU: asked on
     return nb;
 }
 
-// the kernel for an index: row width unrolled where the fast walk unrolls it (the same device functions: the same distance bits)
+// the kernel for an index: row width unrolled where the fast walk unrolls it (the same device functions: the same distance bits);
+// f(kernel, its NCH)
 template <typename F>
 int heap_dispatch(const KdbView &v, bool hash, bool reg, bool ov, F f) {
 #define KDB_HW(P, M, N) (ov ? KDB_HW1(P, M, N, 1) : KDB_HW1(P, M, N, 0))
-#define KDB_HW1(P, M, N, O) (hash ? (reg ? f(heap_walk_kernel<P, M, N, 1, 1, O>) : f(heap_walk_kernel<P, M, N, 1, 0, O>)) : f(heap_walk_kernel<P, M, N, 0, 0, O>))
+#define KDB_HW1(P, M, N, O) (hash ? (reg ? f(heap_walk_kernel<P, M, N, 1, 1, O>, N) : f(heap_walk_kernel<P, M, N, 1, 0, O>, N)) : f(heap_walk_kernel<P, M, N, 0, 0, O>, N))
     if (v.precision == KDB_PREC_I8) return KDB_HW(KDB_PREC_I8, KDB_METRIC_COSINE, 0);
     if (v.precision == KDB_PREC_F16) return KDB_HW(KDB_PREC_F16, KDB_METRIC_L2, 0);
     if (v.metric == KDB_METRIC_COSINE) {
@@ -766,7 +767,7 @@ int kdb_heap_walk_plan(kdb_index *idx, const KdbView &v, uint32_t ef, uint32_t k
         kdb_set_error("heap-order walk: ef=%u needs %zu bytes of LDS per wave (limit 160 KiB)", eff, p.lds);
         return KDB_ERR_UNSUPPORTED;
     }
-    const int occ = heap_dispatch(v, p.hsize != 0, p.reg_results != 0, false, [&](auto kern) { return heap_occupancy(kern, p.lds); });
+    const int occ = heap_dispatch(v, p.hsize != 0, p.reg_results != 0, false, [&](auto kern, int) { return heap_occupancy(kern, p.lds); });
     const uint32_t room = (uint32_t)idx->n_cu * (uint32_t)(occ < 1 ? 1 : occ);
     p.grid = B < room ? B : room;
     p.tail_bytes = (size_t)p.grid * (size_t)(p.cap_c - p.nl_c) * 12u;
@@ -807,7 +808,11 @@ int kdb_launch_heap_walk(kdb_index *idx, const KdbView &v, const void *d_q, cons
     a.out_count = d_out_count;
     a.tr_ndist = d_tr_ndist;
     a.tr_nhops = d_tr_nhops;
-    return heap_dispatch(v, plan.hsize != 0, plan.reg_results != 0, mode != 0u, [&](auto kern) -> int {
+    return heap_dispatch(v, plan.hsize != 0, plan.reg_results != 0, mode != 0u, [&](auto kern, int nch) -> int {
+        if (mode != 2u) { // test hook (kdb_probe_launch_shape): the pass's kernel, in the slot of the search launch it belongs to
+            uint32_t *const shp = kdb_stats_shape(idx);
+            shp[9] = (uint32_t)nch, shp[10] = plan.hsize, shp[11] = plan.reg_results, shp[12] = mode != 0u ? 1u : 0u;
+        }
         if (plan.lds > 64 * 1024) KDB_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds));
         hipLaunchKernelGGL(kern, dim3(plan.grid), dim3(64), plan.lds, s, v, a);
         KDB_HIP(hipGetLastError());

@@ -356,7 +356,7 @@ static int launch_search_bs(kdb_index *idx, const KdbView &v, const void *d_q, c
     // two rounds, not three
     const uint32_t hsize_w = hsize ? (hsize * 4u > 16384u ? 16384u : hsize * 4u) : 0u;
     KdbView vk = v; // the search kernel's view: with the walk planes once a planes kernel has been picked (use_planes)
-    auto launch_any = [&](auto kern, uint32_t vis_size, uint32_t waves, size_t lds) -> int {
+    auto launch_any = [&](auto kern, uint32_t vis_size, uint32_t waves, size_t lds, bool planes = false) -> int {
         if (lds > 64 * 1024) KDB_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         uint32_t grid = ncu * (uint32_t)occupancy_blocks(kern, (int)(64u * waves), lds);
         if (grid > B) grid = B;
@@ -439,6 +439,12 @@ static int launch_search_bs(kdb_index *idx, const KdbView &v, const void *d_q, c
             }
         }
         unsigned long long *d_ctr = kdb_stats_begin(idx, 1, B, 0);
+        { // test hook (kdb_probe_launch_shape): the instantiation this launch takes, in the statistics slot just opened
+            uint32_t *const shp = kdb_stats_shape(idx);
+            shp[0] = 1u, shp[1] = (uint32_t)PREC, shp[2] = (uint32_t)METRIC, shp[3] = (uint32_t)NCH, shp[4] = (uint32_t)BS;
+            shp[5] = vis_size, shp[6] = waves, shp[7] = planes ? 1u : 0u, shp[8] = heap_pass ? 1u : 0u;
+            shp[13] = grid, shp[14] = (uint32_t)lds, shp[15] = B;
+        }
         // the launch's accumulators {n_dist, n_hops, work | done, dropped}: zero between launches (see the kernel's end).  They
         // belong to the call's SCRATCH LANE (words 32..41 of its d_work), not to the statistics ring: two launches that share
         // a lane are ordered by the lane protocol (same stream, or an event wait on the previous user), so a launch never
@@ -476,8 +482,8 @@ static int launch_search_bs(kdb_index *idx, const KdbView &v, const void *d_q, c
         if (idx->time_launches) KDB_HIP(hipEventRecord(idx->ev1, s));
         return KDB_OK;
     };
-    auto launch = [&](auto kern, uint32_t vis_size, uint32_t waves = 1u) -> int {
-        return launch_any(kern, vis_size, waves, lds1 + (waves > 1u ? 64u + 512u + (size_t)(hsize_w - hsize) * 4 : 0u));
+    auto launch = [&](auto kern, uint32_t vis_size, uint32_t waves = 1u, bool planes = false) -> int {
+        return launch_any(kern, vis_size, waves, lds1 + (waves > 1u ? 64u + 512u + (size_t)(hsize_w - hsize) * 4 : 0u), planes);
     };
     auto launch_lds = [&](auto kern, uint32_t vis_size, size_t lds) -> int { return launch_any(kern, vis_size, 1u, lds); };
     (void)launch_lds;
@@ -529,7 +535,7 @@ static int launch_search_bs(kdb_index *idx, const KdbView &v, const void *d_q, c
                 bool planes = false;
                 const int rc = use_planes(&planes);
                 if (rc) return rc;
-                if (planes) return launch(hnsw_search_kernel<PREC, METRIC, NCH, BS, 1, 1, 1>, hsize);
+                if (planes) return launch(hnsw_search_kernel<PREC, METRIC, NCH, BS, 1, 1, 1>, hsize, 1u, true);
             }
             return launch(hnsw_search_kernel<PREC, METRIC, NCH, BS, 1>, hsize);
         }

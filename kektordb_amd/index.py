@@ -595,6 +595,17 @@ class HipIndex:
         """test hook: every CU's LDS filled with `pattern` (0 = pseudo-random words) -- a kernel that reads LDS it never wrote shows"""
         check(self.L.kdb_probe_poison_lds(self.h, int(pattern) & 0xffffffff), "kdb_probe_poison_lds")
 
+    LAUNCH_SHAPE_FIELDS = ("search", "prec", "metric", "nch", "bs", "vis_hash_words", "waves", "planes", "heap_pass", "heap_nch",
+                           "heap_hash_words", "heap_reg_results", "heap_overlap", "grid", "lds_bytes", "B")
+
+    def launch_shape(self, last_n: int = 1):
+        """test hook: which hnsw_search_kernel instantiation (and heap-order kernel) each of the last `last_n` launches took, oldest
+        first (kdb_probe_launch_shape); a list of dicts over LAUNCH_SHAPE_FIELDS, all zero for a launch that was not a graph search"""
+        nw = len(self.LAUNCH_SHAPE_FIELDS)
+        arr = np.zeros((last_n, nw), dtype=np.uint32)
+        check(self.L.kdb_probe_launch_shape(self.h, last_n, _ptr(arr)), "kdb_probe_launch_shape")
+        return [dict(zip(self.LAUNCH_SHAPE_FIELDS, (int(x) for x in row))) for row in arr]
+
     def probe_stream(self, shadow: bool = False):
         """measurement hook: GB/s of one coalesced pass over this index's rows (or its half-precision copy)"""
         ms, nbytes = C.c_float(), C.c_uint64()

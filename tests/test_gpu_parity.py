@@ -231,40 +231,42 @@ def test_search_edge_cases(oracle, hip):
 
 
 def test_search_f16_and_int8(oracle, hip):
+    """64 columns (the any-width kernels) and 768 (the unrolled NCH 12 loaders of float16 and int8 rows -- what DB.Compress makes of
+    the headline corpus): ids, distance bits and the walk's counters are the oracle's"""
     O = oracle
-    n, dim = 2000, 64
-    X = make_corpus(n, dim, "normal", seed=31)
-    Q = make_corpus(16, dim, "normal", seed=32)
-    # float16 / euclidean
-    orc, idx = build_pair(O, hip, X, 0, precision=O.F16)
-    orc.set_arith(O.ARITH_HIP_WAVE)
-    ids, dist, cnt, (nd, nh) = idx.search_batch(Q, 10, 60, trace=True)
-    for b in range(16):
-        oi, od, (ond, onh) = orc.search(Q[b], 10, ef=60, counters=True)
-        assert np.array_equal(ids[b, :int(cnt[b])], oi)
-        assert np.array_equal(dist[b, :int(cnt[b])].astype(np.float64), od)
-        assert (int(nd[b]), int(nh[b])) == (ond, onh)
-    # int8 / cosine: exact integer dot, f64 scaling; distances compared within tolerance
-    orc = O.OracleIndex(dim, 1, O.I8, 16, 100, seed=7)
-    orc.set_absmax(float(np.quantile(np.abs(X), 0.999)))
-    orc.add_many(X)
-    g = orc.export_graph()
-    idx = hip.HipIndex(dim, 1, O.I8, 16, 100, capacity=n + 8)
-    idx.upload_rows(orc.rows()[1:], 1)
-    idx.upload_norms(orc.norms()[1:], 1)
-    idx.set_quantizer(orc.absmax)
-    idx.upload_graph_obj(g)
-    # the reference computes AND orders these distances as float64 (hnsw_index.go:2429-2454): the beam carries 64-bit keys,
-    # so ids, float64 distances and the walk's counters are the oracle's bit for bit; without the flag the same doubles
-    # arrive rounded to float
-    ids, dist, cnt, (nd, nh) = idx.search_batch(Q, 10, 60, trace=True, dist64=True)
-    ids32, dist32, cnt32 = idx.search_batch(Q, 10, 60)
-    assert dist.dtype == np.float64 and np.array_equal(ids, ids32) and np.array_equal(dist.astype(np.float32), dist32)
-    for b in range(16):
-        oi, od, (ond, onh) = orc.search(Q[b], 10, ef=60, counters=True)
-        assert np.array_equal(ids[b, :int(cnt[b])], oi)
-        assert np.array_equal(dist[b, :int(cnt[b])], od)
-        assert (int(nd[b]), int(nh[b])) == (ond, onh)
+    for n, dim, efc in ((2000, 64, 100), (1500, 768, 20)):   # (efConstruction 20 at 768 columns: the oracle's float16 build is slow)
+        X = make_corpus(n, dim, "normal", seed=31)
+        Q = make_corpus(16, dim, "normal", seed=32)
+        # float16 / euclidean
+        orc, idx = build_pair(O, hip, X, 0, precision=O.F16, efc=efc)
+        orc.set_arith(O.ARITH_HIP_WAVE)
+        ids, dist, cnt, (nd, nh) = idx.search_batch(Q, 10, 60, trace=True)
+        for b in range(16):
+            oi, od, (ond, onh) = orc.search(Q[b], 10, ef=60, counters=True)
+            assert np.array_equal(ids[b, :int(cnt[b])], oi), (dim, b)
+            assert np.array_equal(dist[b, :int(cnt[b])].astype(np.float64), od), (dim, b)
+            assert (int(nd[b]), int(nh[b])) == (ond, onh), (dim, b)
+        # int8 / cosine: exact integer dot, f64 scaling; distances compared within tolerance
+        orc = O.OracleIndex(dim, 1, O.I8, 16, efc, seed=7)
+        orc.set_absmax(float(np.quantile(np.abs(X), 0.999)))
+        orc.add_many(X)
+        g = orc.export_graph()
+        idx = hip.HipIndex(dim, 1, O.I8, 16, efc, capacity=n + 8)
+        idx.upload_rows(orc.rows()[1:], 1)
+        idx.upload_norms(orc.norms()[1:], 1)
+        idx.set_quantizer(orc.absmax)
+        idx.upload_graph_obj(g)
+        # the reference computes AND orders these distances as float64 (hnsw_index.go:2429-2454): the beam carries 64-bit keys,
+        # so ids, float64 distances and the walk's counters are the oracle's bit for bit; without the flag the same doubles
+        # arrive rounded to float
+        ids, dist, cnt, (nd, nh) = idx.search_batch(Q, 10, 60, trace=True, dist64=True)
+        ids32, dist32, cnt32 = idx.search_batch(Q, 10, 60)
+        assert dist.dtype == np.float64 and np.array_equal(ids, ids32) and np.array_equal(dist.astype(np.float32), dist32)
+        for b in range(16):
+            oi, od, (ond, onh) = orc.search(Q[b], 10, ef=60, counters=True)
+            assert np.array_equal(ids[b, :int(cnt[b])], oi), (dim, b)
+            assert np.array_equal(dist[b, :int(cnt[b])], od), (dim, b)
+            assert (int(nd[b]), int(nh[b])) == (ond, onh), (dim, b)
     with pytest.raises(hip.KdbError):  # float64 output is an int8 matter
         build_pair(O, hip, X[:200], 0)[1].search_batch(Q, 10, 60, dist64=True)
 
