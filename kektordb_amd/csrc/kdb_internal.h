@@ -390,12 +390,15 @@ int kdb_launch_by_id_finish(const uint32_t *d_src_ids, const uint8_t *d_found, u
 // consensus.hip: CalculateConsensus for B id lists, one workgroup per list (everything optional may be null)
 int kdb_launch_consensus(const KdbView &v, const uint32_t *d_ids, const uint32_t *d_counts, uint32_t B, uint32_t stride, const float *d_queries,
                          const uint32_t *d_active, kdb_consensus *d_out, double *d_sim, float *d_centroid, double *d_gram, hipStream_t s);
-// build.hip
-int kdb_build_graph(kdb_index *idx, uint32_t count, const kdb_build_params *p);
-int kdb_add_batch_ref(kdb_index *idx, uint32_t first_id, uint32_t n, const uint8_t *levels, uint32_t ef_construction);
+// graph construction (what the three files share: kdb_graph_build.cuh, kdb_walk_lds.h)
+// add.hip: the sequential Add
 int kdb_add_graph(kdb_index *idx, uint32_t first_id, uint32_t n, const uint8_t *levels, uint32_t ef_construction, kdb_add_stats *out);
+// refine.hip: Refine and Vacuum
 int kdb_refine_graph(kdb_index *idx, const uint32_t *ids, uint32_t n, uint32_t ef_construction, uint32_t chunk_nodes, kdb_refine_stats *out);
 int kdb_vacuum_graph(kdb_index *idx, uint32_t ef_construction, uint32_t flags, uint32_t chunk_nodes, kdb_vacuum_stats *out);
 int kdb_dead_link_scan_graph(kdb_index *idx, uint32_t *out_ids, uint32_t cap, uint32_t *n_nodes, uint64_t *n_dead_links, uint64_t *n_dead);
+// build.hip: the fast builder, reference linking, the selectNeighbors test hook
+int kdb_build_graph(kdb_index *idx, uint32_t count, const kdb_build_params *p);
+int kdb_add_batch_ref(kdb_index *idx, uint32_t first_id, uint32_t n, const uint8_t *levels, uint32_t ef_construction);
 int kdb_select_probe(kdb_index *idx, uint32_t n_lists, uint32_t stride, const uint32_t *d_ids, const void *d_keys,
                      const uint32_t *d_cnt, uint32_t maxm, uint32_t *d_out_ids, uint32_t *d_out_cnt, hipStream_t s);

@@ -1894,7 +1894,7 @@ __host__ __device__ inline uint32_t kdb_vis_hash_size_large(uint32_t ef) {
 }
 
 // beam slots needed for ef (the beam never holds more than ef entries); 0 = use the LDS beam
-__host__ __device__ inline int kdb_beam_slots(uint32_t ef) {
+__host__ __device__ constexpr int kdb_beam_slots(uint32_t ef) { // (constexpr: kdb_graph_build.cuh checks the walk plan's rule against it)
     const uint32_t need = ef;
     if (need <= 64) return 1; // one entry per lane: every beam operation stays inside one register
     if (need <= 128) return 2;

@@ -3,6 +3,7 @@
 // file took 8.5 minutes to compile).  Design notes: search.hip.
 #pragma once
 #include "kdb_search_core.cuh"
+#include "kdb_walk_lds.h"
 #include <map>
 #include <tuple>
 #include <mutex>
@@ -334,10 +335,7 @@ static int launch_search_bs(kdb_index *idx, const KdbView &v, const void *d_q, c
                             hipStream_t s) {
     const uint32_t eff = ef < k ? k : ef; // ef = max(efSearch, k) (:2377-2380)
     const uint32_t beam_cap = ((eff + 2) + 63) / 64 * 64; // LDS beam (BS == 0)
-    // traversal-only candidates (NrList): a walk can never hold more of them than the index has deleted nodes (+ the
-    // entry point when a filter excludes it), so up to 2047 deleted nodes the list cannot overflow; beyond that it
-    // holds the 2048 nearest pending ones and counts what it had to drop (kdb_counters.n_dropped)
-    const uint32_t nr_cap = ((idx->n_deleted < 2047u ? idx->n_deleted : 2047u) + 1u + 3u) & ~3u;
+    const uint32_t nr_cap = kdb_nr_cap(idx->n_deleted); // traversal-only candidates (NrList): the rule is kdb_walk_lds.h's, shared with the construction walks
     const size_t qb = PREC == KDB_PREC_I8 ? ((size_t)v.ld + 15) / 16 * 16 : (size_t)v.ld * 4;
     constexpr bool WK = PREC == KDB_PREC_I8; // 64-bit distance keys: one more word per beam / neighbour / pending entry
     const size_t lds_common = qb + (BS == 0 ? (size_t)beam_cap * (WK ? 12 : 8) : 0) + 64 * (WK ? 12 : 8) + (size_t)nr_cap * (WK ? 12 : 8) +

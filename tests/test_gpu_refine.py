@@ -224,6 +224,8 @@ def _case(name):
         "odd": lambda: Case(O, L2, F32, 1000, 200, 16, 60, seed=17),
         "f16": lambda: Case(O, L2, F16, 800, 96, 16, 32, seed=18, deleted_frac=0.10),
         "i8": lambda: Case(O, COSINE, I8, 800, 96, 16, 32, seed=19, deleted_frac=0.10),
+        # every region of a walking wave's LDS live at once: 64-bit keys (the *_lo arrays), the LDS beam (ef > 256), the side list
+        "i8lds": lambda: Case(O, COSINE, I8, 500, 96, 16, 300, seed=20, deleted_frac=0.10),
     }
     return mk[name]()
 
@@ -375,9 +377,10 @@ def test_refine_is_a_snapshot_whatever_the_chunk(oracle, hip):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("name", ["f16", "i8"])
+@pytest.mark.parametrize("name", ["f16", "i8", "i8lds"])
 def test_refine_f16_and_int8(oracle, hip, name):
-    """case 9: float16 (L2) and int8 (cosine), a tenth of the nodes deleted; int8 lists are identical without exception"""
+    """case 9: float16 (L2) and int8 (cosine), a tenth of the nodes deleted; int8 lists are identical without exception
+    (i8lds: int8 at ef 300, the beam in LDS)"""
     _refine_all(hip, name)
 
 
