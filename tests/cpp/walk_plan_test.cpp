@@ -42,7 +42,13 @@ static void check_plan(bool i8, uint32_t ld, uint32_t efc, uint32_t n_deleted) {
     CHECK(end == w.bytes);       // the end of marks is what the host asks for
 }
 
-int main() {
+int main(int argc, char **argv) {
+    // walk_plan_test bs <efConstruction>...: the beam storage KDB_WALK_KERNEL dispatches on (wl.bs), one figure per argument -- the GPU
+    // parity cases of the construction walks assert from it that each runs the <BS> instantiation it was written for
+    if (argc > 1) {
+        for (int i = 2; i < argc; i++) printf("%u\n", kdb_walk_lds(false, 48, (uint32_t)strtoul(argv[i], nullptr, 10), 0).bs);
+        return 0;
+    }
     const Row table[] = {
         {false, 768, 200, 0, 4, 320, 4, 4640},
         {false, 48, 400, 0, 0, 512, 4, 5856},

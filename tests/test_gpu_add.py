@@ -20,9 +20,9 @@ KDB_ERR_INVALID, KDB_ERR_UNSUPPORTED = -1, -6
 STAT_SUMS = ("nodes_added", "forward_lists", "reverse_appended", "reverse_pruned", "tied_nodes", "reverse_skipped")
 
 
-def draw_levels(n, seed):
+def draw_levels(n, seed, m=M):
     rng = np.random.default_rng(seed)
-    return np.minimum(np.floor(-np.log(1.0 - rng.random(n)) / np.log(M)), 6).astype(np.int32)
+    return np.minimum(np.floor(-np.log(1.0 - rng.random(n)) / np.log(m)), 6).astype(np.int32)
 
 
 def corpus(O, n, dim, prec, seed, law="uniform"):
@@ -33,11 +33,11 @@ def corpus(O, n, dim, prec, seed, law="uniform"):
     return X
 
 
-def new_pair(O, hip, X, metric, prec):
+def new_pair(O, hip, X, metric, prec, m=M, efc=EFC):
     n, dim = X.shape
-    orc = O.OracleIndex(dim, metric, prec, M, EFC, seed=5)
+    orc = O.OracleIndex(dim, metric, prec, m, efc, seed=5)
     orc.set_arith(O.ARITH_HIP_WAVE)
-    idx = hip.HipIndex(dim, metric, prec, M, EFC, capacity=n + 8)
+    idx = hip.HipIndex(dim, metric, prec, m, efc, capacity=n + 8)
     if prec == O.I8:
         orc.set_absmax(float(np.abs(X).max()))
         idx.set_quantizer(orc.absmax)
@@ -50,37 +50,37 @@ def oracle_add(orc, X, levels, lo, hi):
         assert orc.add(X[i - 1], level=int(levels[i - 1])) == i
 
 
-def gpu_add(idx, orc, O, prec, levels, lo, hi):
+def gpu_add(idx, orc, O, prec, levels, lo, hi, efc=EFC):
     """the stored form of ids lo..hi goes up, then ONE kdb_index_add call"""
     idx.upload_rows(orc.rows()[lo:hi + 1], lo)
     if prec == O.I8:
         idx.upload_norms(orc.norms()[lo:hi + 1], lo)
-    return idx.add(lo, levels[lo - 1:hi], EFC)
+    return idx.add(lo, levels[lo - 1:hi], efc)
 
 
-def dense(cnt, max_level, offs, nbrs, rows=None):
-    """per level a [rows, 2M] matrix of the lists in stored order, 0-filled"""
+def dense(cnt, max_level, offs, nbrs, rows=None, m=M):
+    """per level a [rows, 2m] matrix of the lists in stored order, 0-filled"""
     rows = cnt + 1 if rows is None else rows
     out = []
     for l in range(max_level + 1):
         off = np.asarray(offs[l][:cnt + 2], dtype=np.int64)
         lens = np.diff(off)
-        assert lens.max(initial=0) <= (2 * M if l == 0 else M), (l, int(lens.max()))
+        assert lens.max(initial=0) <= (2 * m if l == 0 else m), (l, int(lens.max()))
         tot = int(off[cnt + 1])
-        m = np.zeros((rows, 2 * M), dtype=np.uint32)
-        m[np.repeat(np.arange(cnt + 1), lens), np.arange(tot) - np.repeat(off[:cnt + 1], lens)] = np.asarray(nbrs[l][:tot])
-        out.append(m)
+        mat = np.zeros((rows, 2 * m), dtype=np.uint32)
+        mat[np.repeat(np.arange(cnt + 1), lens), np.arange(tot) - np.repeat(off[:cnt + 1], lens)] = np.asarray(nbrs[l][:tot])
+        out.append(mat)
     return out
 
 
-def gpu_dense(idx, rows=None):
+def gpu_dense(idx, rows=None, m=M):
     cnt, entry, mlv, glv, offs, nbrs = idx.download_graph()
-    return (cnt, entry, mlv, glv[:cnt + 1].copy()), dense(cnt, mlv, offs, nbrs, rows)
+    return (cnt, entry, mlv, glv[:cnt + 1].copy()), dense(cnt, mlv, offs, nbrs, rows, m)
 
 
-def orc_dense(orc, rows=None):
+def orc_dense(orc, rows=None, m=M):
     og = orc.export_graph()
-    return og, (og.count, og.entry, og.max_level, og.levels[:og.count + 1].copy()), dense(og.count, og.max_level, og.offsets, og.neighbors, rows)
+    return og, (og.count, og.entry, og.max_level, og.levels[:og.count + 1].copy()), dense(og.count, og.max_level, og.offsets, og.neighbors, rows, m)
 
 
 def lists_differing(a, b):
@@ -99,6 +99,23 @@ def lists_differing(a, b):
 def assert_same_header(gh, oh):
     assert gh[:3] == oh[:3], (gh[:3], oh[:3])
     assert np.array_equal(gh[3][1:], oh[3][1:])
+
+
+def assert_list_invariants(gd, cnt, glv, m=M):
+    """a dense graph of cnt nodes: lists within their width, no id beyond cnt, no own node, no hole, no node twice, nothing above
+    a node's level"""
+    for l, mat in enumerate(gd):
+        width = 2 * m if l == 0 else m
+        assert not mat[:, width:].any()
+        assert mat.max() <= cnt
+        own = np.arange(cnt + 1, dtype=np.uint32)[:, None]
+        assert not np.any((mat == own) & (mat != 0)), "a list names its own node"
+        assert not mat[0].any()
+        lens = np.count_nonzero(mat, axis=1)
+        assert np.all((np.arange(2 * m)[None, :] < lens[:, None]) == (mat != 0)), "a hole inside a list"
+        s = np.sort(mat, axis=1)
+        assert not np.any((s[:, 1:] == s[:, :-1]) & (s[:, 1:] != 0)), "a list names a node twice"
+        assert not mat[glv < l].any()
 
 
 CALLS_EXACT = (1, 1, 1, 5, 17, 64, 300)
@@ -286,18 +303,7 @@ def test_add_ties_are_reported(oracle, hip):
     assert st["nodes_added"] == n and st["tied_nodes"] > 0
     (cnt, entry, mlv, glv), gd = gpu_dense(idx)
     assert cnt == n and 1 <= entry <= n
-    for l, m in enumerate(gd):
-        width = 2 * M if l == 0 else M
-        assert not m[:, width:].any()
-        assert m.max() <= n
-        own = np.arange(cnt + 1, dtype=np.uint32)[:, None]
-        assert not np.any((m == own) & (m != 0)), "a list names its own node"
-        assert not m[0].any()
-        lens = np.count_nonzero(m, axis=1)
-        assert np.all((np.arange(2 * M)[None, :] < lens[:, None]) == (m != 0)), "a hole inside a list"
-        s = np.sort(m, axis=1)
-        assert not np.any((s[:, 1:] == s[:, :-1]) & (s[:, 1:] != 0)), "a list names a node twice"
-        assert not m[glv < l].any()
+    assert_list_invariants(gd, cnt, glv)
     ids, dist, c = idx.search_batch(X, 1, EFC)
     twin = np.arange(1, n + 1)
     twin[0:20], twin[100:120] = np.arange(101, 121), np.arange(1, 21)

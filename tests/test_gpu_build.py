@@ -364,31 +364,27 @@ def test_gpu_builder_vs_restated_batch_insert(oracle, hip):
     print("recall@10 (restated batch path, GPU builder):", out)
 
 
-@pytest.mark.parametrize("metric,prec,n,dim,law", [(0, 0, 6000, 48, "uniform"), (1, 0, 5000, 96, "clustered"), (0, 1, 5000, 64, "clustered"),
-                                                   (1, 2, 5000, 64, "clustered")])
-def test_add_batch_reference_links_list_for_list(oracle, hip, metric, prec, n, dim, law):
-    """kdb_index_add_batch = addBatchInternal with the reference's OWN linking (hnsw_index.go:1864-2060): after every batch
-    the adjacency downloaded from the GPU equals the restated batch insert's (oracle add_batch), list for list and in stored
-    order, at every level.  Start: the first efConstruction nodes inserted one by one (the reference does that itself,
-    :1505-1516) and uploaded.  Levels are drawn once and forced on both sides; the first batch re-uses the last single node's
-    slot (the id arithmetic of :1620 vs :590), which is given level 0 so that no slot has to grow a level.
-    float32 / float16: the two sides sum a distance in different orders only inside selectNeighbors' pair distances
-    (DESIGN 5.4), so a list may differ where a pair distance ties with a centre distance to rounding -- counted, must stay
-    below 0.2 % of the lists; int8 distances are exact integers scaled in float64: every list must be identical."""
-    O = oracle
-    rng = np.random.default_rng(77)
-    efc, m = 60, 16
-    X = make_corpus(n, dim, law, seed=78).astype(np.float32)
-    if prec == O.F16:
-        X = (X * 0.25).astype(np.float32)
-    ml = 1.0 / np.log(m)
-    levels = np.minimum(np.floor(-np.log(1.0 - rng.random(n)) * ml), 6).astype(np.int32)
+def add_batch_list_for_list(O, hip, metric, prec, X, levels, m, efc, batches, dead_frac=0.0, poison=None):
+    """the protocol of test_add_batch_reference_links_list_for_list (its docstring): the oracle's first efc single inserts uploaded as
+    a graph, then `batches` through orc.add_batch / idx.add_batch with the forced levels, every list of every level compared after
+    every batch.  dead_frac: that share of the start graph is soft-deleted on both sides before the first batch, the entry point
+    among them; poison: every CU's LDS is filled with that pattern before each batch.  -> lists compared, lists that differed
+    (int8: none may), the pair and the deleted ids"""
+    n, dim = X.shape
+    levels = levels.copy()
     levels[efc - 1] = 0                                     # the slot the first batch takes over
     orc = O.OracleIndex(dim, metric, prec, m, efc, seed=5)
     if prec == O.I8:
         orc.set_absmax(float(np.abs(X).max()))
     for i in range(efc):
         orc.add(X[i], level=int(levels[i]))
+    dead = []
+    if dead_frac:
+        dead = np.random.default_rng(79).choice(np.arange(1, efc), int(efc * dead_frac), replace=False).tolist()   # (not the re-used slot)
+        if orc.entry not in dead:
+            dead[0] = orc.entry
+        for d in dead:
+            orc.mark_deleted(int(d))
     orc.set_arith(O.ARITH_HIP_WAVE)
     idx = hip.HipIndex(dim, metric, prec, m, efc, capacity=n + 8)
     idx.upload_rows(orc.rows()[1:], 1)
@@ -397,7 +393,7 @@ def test_add_batch_reference_links_list_for_list(oracle, hip, metric, prec, n, d
         idx.set_quantizer(orc.absmax)
     idx.upload_graph_obj(orc.export_graph())
     pos, bad, total = efc, 0, 0
-    for bsz in (400, 1000, 2000, 1500):
+    for bsz in batches:
         if pos >= n:
             break
         bsz = min(bsz, n - pos)
@@ -409,6 +405,8 @@ def test_add_batch_reference_links_list_for_list(oracle, hip, metric, prec, n, d
         idx.upload_rows(rows[start:start + bsz], start)      # stored form (normalised / f16 / quantised) of the new nodes
         if prec == O.I8:
             idx.upload_norms(orc.norms()[start:start + bsz], start)
+        if poison is not None:
+            idx.poison_lds(poison)
         idx.add_batch(start, np.minimum(lb, before + 1), efc)
         cnt, entry, mlv, glv, offs, nbrs = idx.download_graph()
         og = orc.export_graph()
@@ -431,6 +429,30 @@ def test_add_batch_reference_links_list_for_list(oracle, hip, metric, prec, n, d
         if bad:                                              # a rounding tie made the graphs differ: later batches would inherit it
             idx.upload_graph_obj(og)
         pos += bsz
+    return dict(total=total, bad=bad, orc=orc, idx=idx, dead=dead, levels=levels, added=pos)
+
+
+@pytest.mark.parametrize("metric,prec,n,dim,law", [(0, 0, 6000, 48, "uniform"), (1, 0, 5000, 96, "clustered"), (0, 1, 5000, 64, "clustered"),
+                                                   (1, 2, 5000, 64, "clustered")])
+def test_add_batch_reference_links_list_for_list(oracle, hip, metric, prec, n, dim, law):
+    """kdb_index_add_batch = addBatchInternal with the reference's OWN linking (hnsw_index.go:1864-2060): after every batch
+    the adjacency downloaded from the GPU equals the restated batch insert's (oracle add_batch), list for list and in stored
+    order, at every level.  Start: the first efConstruction nodes inserted one by one (the reference does that itself,
+    :1505-1516) and uploaded.  Levels are drawn once and forced on both sides; the first batch re-uses the last single node's
+    slot (the id arithmetic of :1620 vs :590), which is given level 0 so that no slot has to grow a level.
+    float32 / float16: the two sides sum a distance in different orders only inside selectNeighbors' pair distances
+    (DESIGN 5.4), so a list may differ where a pair distance ties with a centre distance to rounding -- counted, must stay
+    below 0.2 % of the lists; int8 distances are exact integers scaled in float64: every list must be identical."""
+    O = oracle
+    rng = np.random.default_rng(77)
+    efc, m = 60, 16
+    X = make_corpus(n, dim, law, seed=78).astype(np.float32)
+    if prec == O.F16:
+        X = (X * 0.25).astype(np.float32)
+    ml = 1.0 / np.log(m)
+    levels = np.minimum(np.floor(-np.log(1.0 - rng.random(n)) * ml), 6).astype(np.int32)
+    r = add_batch_list_for_list(O, hip, metric, prec, X, levels, m, efc, (400, 1000, 2000, 1500))
+    total, bad = r["total"], r["bad"]
     assert total > 3 * n // 4
     assert bad <= max(2, total // 500), (bad, total)
     print(f"add_batch metric {metric} prec {prec}: {total} lists compared, {bad} differed (rounding ties)")

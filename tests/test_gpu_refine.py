@@ -27,15 +27,26 @@ F32, F16, I8 = 0, 1, 2
 
 
 # ---- corpora and start graphs (built once per process, never modified) -------------------------------------------------------
+def wide_rows(rows, prec, absmax):
+    """stored rows as the reference's queryObj: float32 as stored; float16 / int8 widened so that the oracle's conversion gives the
+    stored row back"""
+    if prec == F32:
+        return rows
+    if prec == F16:
+        return rows.view(np.float16).astype(np.float32)
+    return (rows.astype(np.float32) * np.float32(absmax)) / np.float32(127.0)
+
+
 class Case:
-    def __init__(self, O, metric, prec, n, dim, m, ef, seed, deleted_frac=0.0, delete_entry=False, law="clustered", level_cap=6):
+    def __init__(self, O, metric, prec, n, dim, m, ef, seed, deleted_frac=0.0, delete_entry=False, law="clustered", level_cap=6,
+                 level_base=None):
         self.O, self.metric, self.prec, self.n, self.dim, self.m, self.ef = O, metric, prec, n, dim, m, ef
         rng = np.random.default_rng(seed)
         X = make_corpus(n, dim, law, seed=seed + 1).astype(np.float32)
         if prec == F16:
             X = (X * 0.25).astype(np.float32)
         assert np.unique(X, axis=0).shape[0] == n              # no duplicate rows
-        levels = np.minimum(np.floor(-np.log(1.0 - rng.random(n)) / np.log(m)), level_cap).astype(np.int32)
+        levels = np.minimum(np.floor(-np.log(1.0 - rng.random(n)) / np.log(level_base or m)), level_cap).astype(np.int32)
         orc = O.OracleIndex(dim, metric, prec, m, ef, seed=5)
         if prec == I8:
             orc.set_absmax(float(np.abs(X).max()))
@@ -57,13 +68,7 @@ class Case:
         db = self.g.deleted_bits
         self.deleted = np.array([(int(db[i >> 6]) >> (i & 63)) & 1 for i in range(n + 1)], dtype=bool)
         self.lists = [[self._list(l, x) for l in range(int(self.g.levels[x]) + 1)] for x in range(n + 1)]   # [node][level]
-        # the row as the reference's queryObj: float32 as stored; float16 / int8 widened so that the oracle's conversion gives the stored row back
-        if prec == F32:
-            self.wide = self.rows
-        elif prec == F16:
-            self.wide = self.rows.view(np.float16).astype(np.float32)
-        else:
-            self.wide = (self.rows.astype(np.float32) * np.float32(orc.absmax)) / np.float32(127.0)
+        self.wide = wide_rows(self.rows, prec, orc.absmax)
         self._restated = {}
 
     def _list(self, l, x):
@@ -118,7 +123,7 @@ class Case:
         if key in self._restated:
             return self._restated[key]
         sel = range(1, self.count + 1) if ids is None else ids
-        new, facts = {}, {"cur": 0, "appended": 0, "merged_lists": 0, "dead": 0, "short": 0, "nodes": 0}
+        new, facts = {}, {"cur": 0, "appended": 0, "merged_lists": 0, "dead": 0, "short": 0, "short0": 0, "nodes": 0}
         for x in dict.fromkeys(int(i) for i in sel):            # a node named twice: once (same snapshot, same result)
             if self.deleted[x]:                                 # optimizer.go:341
                 continue
@@ -134,6 +139,7 @@ class Case:
                 assert not self.deleted[cid].any()
                 if len(cid) < ef:
                     facts["short"] += 1
+                    facts["short0"] += int(l == 0)              # (level 0 alone: the beam-storage cases ask for a full beam there)
                 have = set(cid.tolist())
                 extra = []
                 for nb in self.lists[x][l]:                     # :497-522
@@ -213,6 +219,15 @@ def check_invariants(case, new, selected):
 def _case(name):
     from oracle import oracle as O
     O.build()
+    if name.startswith("beam/"):            # "beam/<cell>/<efConstruction>[/<deleted nodes>[/up]]": a cell of tests/walk_cells.py; up: its wide upper layers
+        import walk_cells as W
+        part = name.split("/") + ["", ""]
+        metric, prec = {c[0]: c[1:3] for c in W.CELLS}[part[1]]
+        efc = int(part[2])
+        n = W.rows_for(efc)
+        dead = int(part[3]) if part[3] else W.dead_for(n, efc, n // 10)
+        m, base = (W.UP_M, W.UP_LEVEL_BASE) if part[4] == "up" else (W.M, None)
+        return Case(O, metric, prec, n, W.DIM, m, efc, seed=BEAM_SEED, deleted_frac=(dead + 0.5) / n, delete_entry=True, level_base=base)
     mk = {
         "cos": lambda: Case(O, COSINE, F32, 3000, 96, 16, 60, seed=11),
         "l2": lambda: Case(O, L2, F32, 3000, 96, 16, 60, seed=12),
@@ -230,9 +245,13 @@ def _case(name):
     return mk[name]()
 
 
-def _subset(case):
+BEAM_SEED = 30
+
+
+def _subset(case, k=300, live_only=False):
     rng = np.random.default_rng(5)
-    ids = rng.choice(np.arange(1, case.count + 1), 300, replace=False).astype(np.uint32)
+    pool = np.nonzero(~case.deleted[1:])[0] + 1 if live_only else np.arange(1, case.count + 1)
+    ids = rng.choice(pool, k, replace=False).astype(np.uint32)
     dead = np.nonzero(case.deleted)[0]
     if not case.deleted[ids].any():
         ids[7] = dead[0]
