@@ -20,6 +20,7 @@
 // blockIdx -> (stripe, query tile) is XCD-aware: the query tiles of one stripe run on the same XCD so the stripe's
 // rows are fetched from HBM once and shared in L2.
 #include "kdb_device.cuh"
+#include "kdb_flat_plan.h" // tile constants, stripe geometry, seed predicate, LDS sizes, the plan and its scratch layout
 #include <math.h>
 #include <stdlib.h>
 #include <type_traits>
@@ -27,19 +28,13 @@
 
 namespace {
 
-constexpr int FS_TR = 128;          // rows per tile
-constexpr int FS_TQ = 128;          // queries per tile
 constexpr int FS_BK = 32;           // K slab (floats) per stage = 128 B per row
 constexpr int FS_LDS_STRIDE = 40;   // floats per LDS row (160 B)
 constexpr int FS_QPER = 16;         // survivor slots per query per round (per-query mini queues in LDS)
-constexpr int FS_LDS_KL = 16;       // running top-k lists live in LDS up to this length, else in HBM scratch
-constexpr uint32_t FS_MAX_MERGE = 16384; // entries one merge workgroup gathers in LDS (128 KB)
-constexpr uint32_t FS_FIN = 1024;        // finalists one merge workgroup can re-score exactly (band modes)
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-constexpr int FS_PREC_F32R = 3; // internal: float32 rows RANKED on the f16 MFMA (converted while staging), re-scored exactly
 
 struct FsParams {
     const uint32_t *scan_ids; // compacted ids (filter / deletes) or null = identity (id = r+1)
@@ -82,10 +77,7 @@ struct FsParams {
     uint32_t dist64;          // int8: out_dist is a double array (KDB_SEARCH_DIST_F64)
     float *g_pub;             // [n_stripes][qstride] shared thresholds: stripe s publishes the r-th smallest key of its list, r = ceil(kl / n_stripes)
     float *part_thr;          // [n_stripes][qstride] the threshold a stripe ended with: its list is complete for keys <= that
-    uint32_t fb_alt;          // 1: odd tiles walk their slabs backwards
-    uint32_t fb_grow;         // 1: compaction rounds thin out once the thresholds have settled (the host always sets it)
     uint32_t fb_seeded;       // 1: a seed launch published first thresholds into g_pub
-    uint32_t fb_pref;         // 1: threads 0..255 pull the row lines of the slab three steps ahead into L2 (the host never sets it)
     uint32_t fb_seed_nstr;    // the number of stripes the HOST derived when it decided so: both kernels check it against fs_resolve's
     uint32_t fb_slack, fb_period; // compaction rounds every fb_period tiles for lists longer than kl + fb_slack
     uint32_t fb_dbg;          // measurement switches (KDB_FB_DBG): 1 no selection, 2 no DMA after the first slab, 4 no MFMAs
@@ -94,26 +86,12 @@ struct FsParams {
     uint32_t *part_cnt;       // [n_stripes][n_qtiles*FS_TQ]
 };
 
-// Stripe geometry, resolved ON THE DEVICE by every kernel of the scan (same integer arithmetic everywhere): the
-// number of rows that survive the filter is produced by a kernel of the same stream, so the host never waits for it.
-struct FsGeom { uint32_t n_scan, n_stripes, rows_per_stripe; };
-__device__ __forceinline__ FsGeom fs_resolve_n(const FsParams &p, uint32_t n_scan);
-__device__ __forceinline__ FsGeom fs_resolve(const FsParams &p) {
-    return fs_resolve_n(p, p.n_scan_dev ? *p.n_scan_dev : p.n_scan);
+// Stripe geometry (kdb_flat_plan.h) of this launch, for n_scan rows / for the launch's own row count
+__device__ __forceinline__ FsGeom fs_resolve_for(const FsParams &p, uint32_t n_scan) {
+    return fs_resolve_n(n_scan, p.want, p.min_tiles, p.tile_rows ? p.tile_rows : (uint32_t)FS_TR);
 }
-__device__ __forceinline__ FsGeom fs_resolve_n(const FsParams &p, uint32_t n_scan) {
-    FsGeom g;
-    g.n_scan = n_scan;
-    const uint32_t TR = p.tile_rows ? p.tile_rows : (uint32_t)FS_TR;
-    const uint32_t n_tiles = (g.n_scan + TR - 1) / TR;
-    uint32_t ns = p.want;
-    const uint32_t lim = (n_tiles + p.min_tiles - 1) / p.min_tiles;
-    if (ns > lim) ns = lim;
-    if (ns < 1) ns = 1;
-    const uint32_t tiles_per = (n_tiles + ns - 1) / ns;
-    g.n_stripes = tiles_per ? (n_tiles + tiles_per - 1) / tiles_per : 0u;
-    g.rows_per_stripe = tiles_per * TR;
-    return g;
+__device__ __forceinline__ FsGeom fs_resolve(const FsParams &p) {
+    return fs_resolve_for(p, p.n_scan_dev ? *p.n_scan_dev : p.n_scan);
 }
 
 __device__ __forceinline__ bool fs_better(float k1, uint32_t id1, float k2, uint32_t id2) {
@@ -607,20 +585,8 @@ flat_scan_kernel(KdbView v, const float *__restrict__ queries /*[>=n_qtiles*128]
 // whole 128-byte line; 2 x FSS_CH loads per lane are in flight while the previous chunk is multiplied.
 // Same accumulation order as flat_scan_kernel (k = 16s+4g+j), same keys, same total order => same results.
 // Survivors are appended to per-query LDS buffers with an LDS atomic; buffers are compacted by whole waves.
-constexpr int FSS_TQ = 16;     // queries per workgroup
+// (FSS_TQ = 16 queries per workgroup, the buffers' FSS_SLACK and the sizes of the LDS regions: kdb_flat_plan.h)
 constexpr int FSS_CH = 8;      // 16-element K steps per register chunk (128 floats of every row)
-constexpr int FSS_SLACK = 64;  // buffer = kl + one tile of rows + slack entries
-constexpr uint32_t FSS_TAIL = FSS_TQ * 12; // thresholds, counts
-template <int PREC>
-__host__ __device__ inline size_t fss_q_bytes(uint32_t ld);
-__host__ __device__ inline uint32_t fss_qstride(uint32_t ld) { return ld + ((40u + 64u - (ld & 63u)) & 63u); }
-
-template <int PREC>
-__host__ __device__ inline size_t fss_q_bytes(uint32_t ld) {
-    return PREC == KDB_PREC_I8   ? (((size_t)FSS_TQ * (ld + 16u) + 255u) & ~(size_t)255u)
-           : (PREC == FS_PREC_F32R || PREC == KDB_PREC_F16) ? (((size_t)FSS_TQ * (ld * 2u + 16u) + 255u) & ~(size_t)255u)
-                                  : (size_t)FSS_TQ * fss_qstride(ld) * 4u;
-}
 
 // Steps per register chunk.  When the rows cut into an even number of whole chunks of whole 64-byte (RAW) / 16-float steps the
 // kernel is instantiated with CS as a compile-time constant: no clamped addresses, immediate offsets, <= 244 registers (two
@@ -666,7 +632,7 @@ flat_scan_small_kernel(KdbView v, const float *__restrict__ queries, FsParams p,
     const uint32_t S8 = rowb + 16u;
     float *qs = reinterpret_cast<float *>(smem);
     unsigned char *qs8 = smem;
-    float *b_key = reinterpret_cast<float *>(smem + fss_q_bytes<PREC>(v.ld));  // [16][cap_s]
+    float *b_key = reinterpret_cast<float *>(smem + fss_q_bytes(PREC, v.ld));  // [16][cap_s]
     uint32_t *b_id = reinterpret_cast<uint32_t *>(b_key + FSS_TQ * cap_s);    // [16][cap_s]
     float *tau = reinterpret_cast<float *>(b_id + FSS_TQ * cap_s);            // [16]
     uint32_t *tau_id = reinterpret_cast<uint32_t *>(tau + FSS_TQ);            // [16]
@@ -696,7 +662,7 @@ flat_scan_small_kernel(KdbView v, const float *__restrict__ queries, FsParams p,
         q0 = p.g_tile[qt * 3u + 1u];
         nq = p.g_tile[qt * 3u + 2u];
         scan_ids = p.scan_ids + p.g_base[grp];
-        geo = fs_resolve_n(p, p.g_nscan[grp]);
+        geo = fs_resolve_for(p, p.g_nscan[grp]);
     } else {
         geo = fs_resolve(p);
         if (bid == 0 && threadIdx.x == 0 && p.ctr) p.ctr[0] = geo.n_scan;
@@ -1050,7 +1016,7 @@ flat_merge_kernel(KdbView v, const float *__restrict__ queries, const float *__r
     if (tid == 0) { ctl[0] = 0; ctl[1] = 0; }
     __syncthreads();
     const uint32_t qstride = p.n_qtiles * FS_TQ;
-    const uint32_t n_stripes = (p.g_of_query ? fs_resolve_n(p, p.g_nscan[p.g_of_query[q]]) : fs_resolve(p)).n_stripes; // <= p.want
+    const uint32_t n_stripes = (p.g_of_query ? fs_resolve_for(p, p.g_nscan[p.g_of_query[q]]) : fs_resolve(p)).n_stripes; // <= p.want
     uint32_t *sbase = reinterpret_cast<uint32_t *>(qlds + v.ld); // [want] first entry of every stripe's list
     uint32_t *scnt = sbase + p.want;                             // [want]
     float *sworst = reinterpret_cast<float *>(scnt + p.want);    // [want] worst key a stripe kept (band mode)
@@ -1346,11 +1312,7 @@ flat_merge_kernel(KdbView v, const float *__restrict__ queries, const float *__r
 // a grid-stride loop so that the launch costs nothing when the list is empty; a wave scores 4 rows per step
 // (16 lanes per row), appends what beats its threshold to its own LDS buffer and compacts it when it fills; the four
 // buffers are folded into one at the end.  HBM-bound re-read of the stripe's rows: ~3 GB for one query at 1M x 768.
-constexpr uint32_t FSR_BUF = 320; // entries per wave buffer (fs_compact_wave handles up to 320)
-constexpr uint32_t FSR_TQ = 8;    // rescued queries that share one pass over a stripe's rows (ungrouped scans)
-__host__ __device__ inline size_t fsr_lds_bytes(uint32_t ld, uint32_t tq) {
-    return (size_t)tq * ((size_t)ld * 4 + 4 * FSR_BUF * 8 + 4 * 4 + 4 * 8) + 64;
-}
+// (FSR_BUF entries per wave buffer, at most FSR_TQ queries per work item, fsr_lds_bytes: kdb_flat_plan.h)
 template <int METRIC, int PREC>
 __global__ void __launch_bounds__(256)
 flat_rescue_kernel(KdbView v, const float *__restrict__ queries, FsParams p, uint32_t tq_max) {
@@ -1376,7 +1338,7 @@ flat_rescue_kernel(KdbView v, const float *__restrict__ queries, FsParams p, uin
         if (p.g_of_query) {
             const uint32_t grp = p.g_of_query[p.rs_list[r0]];
             scan_ids = p.scan_ids + p.g_base[grp];
-            geo = fs_resolve_n(p, p.g_nscan[grp]);
+            geo = fs_resolve_for(p, p.g_nscan[grp]);
         } else {
             geo = fs_resolve(p);
         }
@@ -1575,8 +1537,7 @@ compact_ids_kernel(const uint32_t *deleted, const uint32_t *allow, const uint32_
 // Every list is cut into FG_NB chunks of whole 256-word slabs; workgroup (b, g) owns chunk b of list g in all three steps,
 // so no step needs an atomic and every id list comes out ASCENDING.  (Round 2 used one workgroup per 256 words and one
 // atomicAdd per wave / workgroup on the group's counter: 100 lists over 10M ids = 490 k atomics on 100 addresses, 3.8 ms of
-// a 9 ms call -- config 5.)
-constexpr uint32_t FG_NB = 64;
+// a 9 ms call -- config 5.)  FG_NB = 64: kdb_flat_plan.h
 __device__ __forceinline__ uint32_t fg_words_per_chunk(uint32_t nwords) { return ((nwords + FG_NB - 1u) / FG_NB + 255u) & ~255u; }
 __device__ __forceinline__ uint32_t fg_mask(const uint32_t *deleted, const uint32_t *allow, uint32_t w, uint32_t nwords, uint32_t count) {
     if (w >= nwords) return 0u;
@@ -1729,20 +1690,6 @@ merge_topk_kernel(int negate, uint32_t G, uint32_t B, uint32_t k, const uint32_t
 
 } // namespace
 
-// Batches of at least this many queries rank with the big-tile kernel.
-constexpr uint32_t FS_BIG_MIN = 33;
-// Batches up to this many queries use flat_scan_small_kernel (the merge layout of the small kernel holds one 128-query tile, so
-// never more than 128).
-constexpr uint32_t FS_SMALL_MAX = 64;
-// One launch = one round of 512 workgroups = (stripes) x (query tiles): with more than 64 query tiles the stripes
-// get so long, and so many workgroups stream the same stripe out of step, that the rows fall out of L2 (32768
-// queries in one launch: 3x slower per query, 150x the HBM traffic).  Larger batches run as 8192-query launches.
-constexpr uint32_t FS_MAX_B = 8192;
-// exact pass, first tier: up to FS_FEW unsettled queries go through the streaming kernel (16 queries per workgroup, the
-// rows read at HBM speed by every CU) -- the tile kernel gives ONE query tile a handful of stripes: a single unsettled
-// query of an 8192-query batch cost 78 ms behind a 12 ms ranking scan (seen once in five calls on the clustered corpus)
-constexpr uint32_t FS_FEW = 64;
-constexpr size_t FS_LDS_MAX = 150u * 1024u; // what a workgroup of the streaming / rescue kernels may ask for
 // the 128 x 128 tile kernel's LDS: both operand tiles, thresholds, the per-query mini queues, the LDS lists
 constexpr size_t FS_TILE_LDS = (size_t)(FS_TR + FS_TQ) * FS_LDS_STRIDE * 4 + FS_TQ * 12 + (size_t)FS_TQ * FS_QPER * 8 +
                                (size_t)FS_TQ * FS_LDS_KL * 8 + (size_t)FS_TQ * 8 + 32;
@@ -1814,16 +1761,9 @@ struct FsCall {
     hipStream_t s;
 };
 
-// Scratch carving: take() returns the next region and advances past it, in whole 256-byte units.
-struct FsBump {
-    unsigned char *at;
-    template <class T>
-    T *take(size_t bytes) {
-        T *r = reinterpret_cast<T *>(at);
-        at += (bytes + 255) & ~(size_t)255;
-        return r;
-    }
-};
+// a region of the scratch buffer, by the offset the plan gives it
+template <class T>
+static T *fs_at(const kdb_index *idx, size_t offset) { return reinterpret_cast<T *>(reinterpret_cast<unsigned char *>(idx->d_scratch) + offset); }
 
 // measurement switches of the `make dbg` build (KDB_FB_DBG: big-tile kernel, KDB_FSS_DBG: small kernel); no other build reads them
 static uint32_t fs_dbg_switches(const char *name) {
@@ -1836,46 +1776,28 @@ static uint32_t fs_dbg_switches(const char *name) {
 #endif
 }
 
-// per-stripe list length: a stripe keeps its k+16 best by the ranking key; the merge kernel checks that no full
-// list reaches into the error band of the k-th key (else the query goes to the exact / rescue pass)
-static uint32_t fs_kl(uint32_t k) { return k + 16 > 144 ? 144 : k + 16; }
-static uint32_t fs_cap_s(uint32_t kl) { return kl + FS_TR + FSS_SLACK; } // a query's buffer in the small kernel
-
-// LDS of the small kernel: 16 queries in the encoding PREC, their buffers, thresholds and counts
-template <int PREC>
-static size_t fs_small_lds_as(uint32_t ld, uint32_t kl) {
-    return fss_q_bytes<PREC>(ld) + (size_t)FSS_TQ * fs_cap_s(kl) * 8 + FSS_TAIL;
-}
-static size_t fs_small_lds(const KdbView &v, uint32_t kl) {
-    return v.precision == KDB_PREC_I8    ? fs_small_lds_as<KDB_PREC_I8>(v.ld, kl)
-           : v.precision == KDB_PREC_F16 ? fs_small_lds_as<KDB_PREC_F16>(v.ld, kl)
-                                         : fs_small_lds_as<KDB_PREC_F32>(v.ld, kl);
-}
-// LDS of the merge kernel: <= FS_MAX_MERGE gathered entries, the finalists, the query, the stripes' counts and thresholds
-static size_t fs_merge_lds(const KdbView &v, uint32_t want, uint32_t kl) {
-    return (size_t)want * kl * 8 + FS_FIN * 8 + 48 + 1024 + (size_t)v.ld * 4 + (size_t)want * 12 + 16;
+// What the plan (kdb_flat_plan.h: fs_plan, fs_group_plan) decides from.  The two environment switches are read per call: tests
+// toggle both inside one process (KDB_FB_SEED_MIN_TILES: the seed path on small cases).
+static FsPlanIn fs_plan_in(const kdb_index *idx, const KdbView &v, uint32_t B, uint32_t k, bool need_ids, bool queries_normalised) {
+    FsPlanIn in{};
+    in.precision = v.precision, in.metric = v.metric;
+    in.ld = v.ld, in.ld16 = idx->ld16, in.dim = v.dim, in.count = v.count;
+    in.has_rows16 = idx->d_rows16 != nullptr;
+    in.max_norm2 = idx->max_norm2;
+    in.B = B, in.k = k;
+    in.need_ids = need_ids;
+    in.queries_normalised = queries_normalised;
+    in.exact_only = getenv("KDB_FLAT_EXACT_ONLY") != nullptr;
+    in.seed_min_tiles = 32u;
+    if (const char *e = getenv("KDB_FB_SEED_MIN_TILES")) in.seed_min_tiles = (uint32_t)atoi(e);
+    return in;
 }
 
-// float32 cosine / L2: rank on the f16 MFMA inside a rigorous error band, settle the rest exactly (only when the library
-// normalised the queries itself and the rows are far from the f16 range limit).  KDB_FLAT_EXACT_ONLY is read per call: a
-// test toggles it inside one process.
-static bool fs_rank16_ok(const kdb_index *idx, const KdbView &v, bool queries_normalised) {
-    return v.precision == KDB_PREC_F32 && (v.metric == KDB_METRIC_L2 || queries_normalised) && idx->max_norm2 > 0.f &&
-           idx->max_norm2 <= 1.0e4f && !getenv("KDB_FLAT_EXACT_ONLY");
-}
-// eps bounds |q.x (wave order) - sum f16(q)f16(x) (MFMA order)| for rows and queries of norm <= 1: f16 rounding
-// of both factors (2^-10 and its square), f32 summation in either order (dim * 2^-23); band = 2 * eps
-// rows of norm R widen it by R (queries are normalised by the preparation step)
-static float fs_band(const kdb_index *idx, const KdbView &v) {
-    const float rmax = v.metric == KDB_METRIC_COSINE ? (idx->max_norm2 > 1.0f ? sqrtf(idx->max_norm2) : 1.0f) : sqrtf(idx->max_norm2);
-    return 2.0f * (9.9e-4f + (float)v.dim * 2.4e-7f) * rmax * 1.001f; // cosine: the band; L2: per unit of ||q|| (x2 in the kernel)
-}
-
-// float32 indexes: the ranking copy has its own row stride (idx->ld16: whole 128-byte slabs, zero pad).  The kernels that
-// read it take a view with that stride (this one) and queries re-laid with it (fs_pad_queries); everything exact keeps v and d_q.
-static KdbView fs_rank_view(const kdb_index *idx, const KdbView &v) {
+// float32 indexes: the kernels that read the ranking copy take a view with its row stride (this one) and queries re-laid with it
+// (fs_pad_queries); everything exact keeps v and d_q.
+static KdbView fs_rank_view(const KdbView &v, uint32_t ld_rank) {
     KdbView vr = v;
-    if (v.precision == KDB_PREC_F32 && idx->d_rows16 != nullptr && idx->ld16 != v.ld) vr.ld = idx->ld16;
+    vr.ld = ld_rank;
     return vr;
 }
 static int fs_pad_queries(const KdbView &v, const KdbView &vr, const void *d_q, size_t n_rows, float *d_qp, hipStream_t s) {
@@ -1907,7 +1829,7 @@ static int fs_launch_tile(const FsCall &c, K kern, const KdbView &vv, const void
 template <class K>
 static int fs_launch_merge(const FsCall &c, K kern, const FsParams &pp, const void *qv) {
     const uint32_t nmax = pp.want * c.kl; // <= FS_MAX_MERGE entries gathered per query
-    const size_t mlds = fs_merge_lds(c.v, pp.want, c.kl);
+    const size_t mlds = fs_merge_lds(c.v.ld, pp.want, c.kl);
     KDB_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mlds));
     hipLaunchKernelGGL(kern, dim3(c.B), dim3(256), mlds, c.s, c.v, reinterpret_cast<const float *>(qv), c.d_qnorm, pp, c.k, nmax, c.d_out_ids,
                        c.d_out_dist, c.d_out_count);
@@ -1977,12 +1899,13 @@ static int flat_scan_anyk(kdb_index *idx, const KdbView &v, const void *d_q, con
     if (chunk_q < 1) chunk_q = 1;
     if (chunk_q > B) chunk_q = B;
     if (chunk_q > 65535u) chunk_q = 65535u;
-    int rc = kdb_ensure_scratch(idx, (ids_b + 255) / 256 * 256 + 256 + (size_t)chunk_q * stride * 8 + 256);
+    KdbCarver scratch; // [scan_ids][n_scan word (256 B)][keys of a chunk of queries]
+    const size_t o_ids = scratch.take(ids_b), o_nscan = scratch.take(256), o_keys = scratch.take((size_t)chunk_q * stride * 8);
+    int rc = kdb_ensure_scratch(idx, scratch.total());
     if (rc) return rc;
-    FsBump scratch{reinterpret_cast<unsigned char *>(idx->d_scratch)};
-    uint32_t *d_ids = scratch.take<uint32_t>(ids_b);
-    uint32_t *d_nscan = scratch.take<uint32_t>(256);
-    unsigned long long *d_keys = scratch.take<unsigned long long>((size_t)chunk_q * stride * 8);
+    uint32_t *d_ids = fs_at<uint32_t>(idx, o_ids);
+    uint32_t *d_nscan = fs_at<uint32_t>(idx, o_nscan);
+    unsigned long long *d_keys = fs_at<unsigned long long>(idx, o_keys);
     if (ids_needed) {
         KDB_HIP(hipMemsetAsync(d_nscan, 0, 8, s));
         hipLaunchKernelGGL(compact_ids_kernel, dim3(((v.count >> 5) + 256) / 256), dim3(256), 0, s, v.deleted, d_allow, d_first_allowed, v.count, d_ids,
@@ -1999,138 +1922,6 @@ static int flat_scan_anyk(kdb_index *idx, const KdbView &v, const void *d_q, con
     return KDB_OK;
 }
 
-// Geometry of one scan of <= FS_MAX_B queries with k <= 128: which kernels, how many stripes, how much scratch.
-struct FsPlan {
-    uint32_t kl, n_qtiles, n_q16;
-    size_t lds_s;         // the small kernel's LDS with the queries in the index's own precision
-    KdbView vr;           // the view of the ranking copy (fs_rank_view)
-    bool copy_padded;     // ... which has another row stride than v
-    bool need_ids;        // scan list: the compacted ids of the rows that are live and allowed (else identity)
-    bool rank16, small, big, few_tier;
-    uint32_t want, min_tiles, cap;                   // small / 128 x 128 tile kernel
-    uint32_t want_big, cap_big;                      // big-tile kernel ...
-    uint32_t fb_nqt, fb_nqg, fb_nqx, fb_spx;         // ... its blockIdx -> (query tile, stripe) map (FsParams)
-    uint32_t fb_slack, fb_period;
-    uint32_t fb_seeded, fb_seed_nstr;                // a seed launch goes first; the stripe count that decision assumed
-    uint32_t want_few;                               // first tier of the exact pass
-    size_t n_part, n_part_big, n_part_few, n_qpad;   // (stripe, query) lists; query rows the ranking kernels may touch
-    size_t ids_bytes, fbq_bytes, fbl_bytes, rsl_bytes, part_bytes, qp_bytes;
-};
-
-static FsPlan fs_plan(const kdb_index *idx, const KdbView &v, uint32_t B, uint32_t k, bool need_ids, bool queries_normalised) {
-    FsPlan g{};
-    g.n_qtiles = (B + FS_TQ - 1) / FS_TQ;
-    g.kl = fs_kl(k);
-    // small batches take the HBM-bound streaming kernel (16 queries per workgroup, whole queries in LDS)
-    g.n_q16 = (B + FSS_TQ - 1) / FSS_TQ;
-    g.lds_s = fs_small_lds(v, g.kl);
-    // which kernel (measured at 1M x 768, scripts/flat_probe.py): the streaming kernel re-reads the rows once per 16 queries
-    // and wins up to 32 queries (0.47 ms at 32); the big-tile kernel (flat_scan_big.cuh: 256 queries x 256 rows per
-    // workgroup; rows must be whole 128-byte slabs -- any number: 64-d halfs are ONE slab, 8192 queries 11.4 -> 2.9 ms against the
-    // 128 x 128 tile kernel -- in a 1- or 2-byte encoding: int8 rows, float16 rows, or the
-    // half-precision ranking copy of float32 rows) wins from 65 queries on (128 queries 0.92 vs 1.20 ms for the 128 x 128
-    // tile kernel, 256 queries 1.10 vs 1.81 ms; k=100: 1.30 vs 3.66 ms) and between 33 and 64 queries when the lists are
-    // short (k=10, 48 queries: 0.69 vs 1.04 ms; k=100, 64 queries: 1.12 vs 0.94 ms)
-    g.vr = fs_rank_view(idx, v);
-    g.copy_padded = g.vr.ld != v.ld;
-    const uint32_t rowb = v.precision == KDB_PREC_I8 ? v.ld : g.vr.ld * 2u;
-    const bool rank16_ok = fs_rank16_ok(idx, v, queries_normalised);
-    const bool big_ok = B >= FS_BIG_MIN && rowb % (uint32_t)FB_SLAB == 0u &&
-                        (v.precision == KDB_PREC_I8 || v.precision == KDB_PREC_F16 || (rank16_ok && idx->d_rows16 != nullptr));
-    g.small = B <= FS_SMALL_MAX && g.lds_s <= FS_LDS_MAX && !(big_ok && B > 32u && g.kl <= 48u);
-    // float32, large batches: rank on the f16 MFMA inside a rigorous error band, settle the rest exactly
-    // (small batches rank on the half-precision copy of the rows, when the index keeps one: half the HBM bytes)
-    g.rank16 = (!g.small || idx->d_rows16) && rank16_ok;
-    g.big = !g.small && big_ok;
-
-    g.ids_bytes = ((size_t)v.count * 4 + 255) / 256 * 256;
-    g.need_ids = need_ids;
-    uint32_t stripes_max = FS_MAX_MERGE / g.kl;
-    if (stripes_max < 1) stripes_max = 1;
-    // stripes: ONE round of resident workgroups (two fit a CU: 512 in all).  Every stripe pays a start-up phase
-    // (threshold still open, everything is a survivor), so more, shorter stripes only cost: measured at 1M x 768,
-    // 512 workgroups beat 1024 and 2048 for every batch from 1 to 8192 queries.
-    g.want = 512 / (g.small ? g.n_q16 : g.n_qtiles);
-    if (g.want < 1) g.want = 1;
-    if (g.want > stripes_max) g.want = stripes_max;
-    g.min_tiles = g.small ? 4u : 8u;
-    {   // never more stripes than the index could fill
-        const uint32_t max_tiles = (v.count + FS_TR - 1) / FS_TR;
-        const uint32_t lim = (max_tiles + g.min_tiles - 1) / g.min_tiles;
-        if (g.want > lim) g.want = lim;
-        if (g.want < 1) g.want = 1;
-    }
-    g.n_part = (size_t)g.want * g.n_qtiles * FS_TQ;
-    // buffered mode: kl entries + room for max(kl, 64) appends between two compactions (<= 320 in all)
-    g.cap = (g.small || g.kl <= (uint32_t)FS_LDS_KL) ? g.kl : g.kl + (g.kl > 64u ? g.kl : 64u);
-    g.fb_nqg = g.fb_nqx = g.fb_spx = g.want_big = 1;
-    if (g.big) {
-        g.fb_nqt = (B + FB_T - 1) / FB_T;                 // <= 32 (batches above 8192 queries are split)
-        const uint32_t per_xcd = 8u;
-        while (g.fb_nqg * per_xcd < g.fb_nqt && g.fb_nqg < 8u) g.fb_nqg *= 2u; // groups of <= 8 query tiles; 1, 2 or 4 groups
-        g.fb_nqx = (g.fb_nqt + g.fb_nqg - 1u) / g.fb_nqg; // query tiles an XCD serves
-        g.fb_spx = 32u / g.fb_nqx;                        // stripes an XCD walks (32 CUs, one workgroup each)
-        g.want_big = (8u / g.fb_nqg) * g.fb_spx;
-        if (g.want_big > stripes_max) g.want_big = stripes_max;
-        const uint32_t max_tiles = (v.count + FB_T - 1) / FB_T;
-        const uint32_t lim = (max_tiles + 3u) / 4u;
-        if (g.want_big > lim) g.want_big = lim;
-        if (g.want_big < 1) g.want_big = 1;
-    }
-    g.fb_slack = 64u;
-    g.fb_period = 4u; // measured at 8192 queries over 1M x 768: period 1 / 2 / 4 = 14.8 / 14.0 / 13.9 ms
-    while (g.fb_period > 1u && fb_cap(g.kl, g.fb_slack, g.fb_period) > 64u * (uint32_t)FB_CSLOTS) g.fb_period--;
-    if (fb_cap(g.kl, g.fb_slack, g.fb_period) > 64u * (uint32_t)FB_CSLOTS) g.fb_slack = 64u * (uint32_t)FB_CSLOTS - g.kl - g.fb_period * (uint32_t)FB_T;
-    g.cap_big = fb_cap(g.kl, g.fb_slack, g.fb_period);
-    g.n_part_big = g.big ? (size_t)g.want_big * g.fb_nqt * FB_T : 0;
-    // Seed launch: only when the stripe geometry is known here (no filter, no deleted rows: the row count never leaves the
-    // device otherwise), every stripe holds a whole first tile, and a stripe's share of the kl best is at most the 16 rows
-    // a tile's block maxima vouch for.  Same integer arithmetic as fs_resolve_n.
-    if (g.big && !need_ids) {
-        const uint32_t n_tiles = (v.count + FB_T - 1) / FB_T;
-        uint32_t ns = g.want_big;
-        const uint32_t lim4 = (n_tiles + 3u) / 4u;
-        if (ns > lim4) ns = lim4;
-        if (ns < 1u) ns = 1u;
-        const uint32_t tiles_per = (n_tiles + ns - 1u) / ns;
-        const uint32_t n_str = (n_tiles + tiles_per - 1u) / tiles_per;
-        const uint64_t last_rows = (uint64_t)v.count - (uint64_t)(n_str - 1u) * tiles_per * FB_T;
-        const uint32_t share = (g.kl + n_str - 1u) / n_str;
-        // (a stripe of fewer than 32 tiles pays more for the extra tile than the open thresholds cost it: 128 queries over
-        //  1M x 768 = 256 stripes of 15 tiles 0.92 vs 0.89 ms; 8192 queries = 8 stripes of 488 tiles 11.80 vs 11.94 ms)
-        uint32_t seed_min_tiles = 32u;
-        if (const char *e = getenv("KDB_FB_SEED_MIN_TILES")) seed_min_tiles = (uint32_t)atoi(e); // (tests: the seed path on small cases)
-        if (n_str >= 2u && last_rows >= (uint64_t)FB_T && share <= 16u && tiles_per >= seed_min_tiles) g.fb_seeded = 1u;
-        g.fb_seed_nstr = n_str;
-    }
-
-    g.part_bytes = g.n_part * g.cap * 8 + g.n_part * 4 + 1024;
-    // big-tile kernel: lists + counts + the thresholds the stripes publish / end with (two floats per (stripe, query))
-    if (g.big && g.n_part_big * g.cap_big * 8 + g.n_part_big * 12 + 1024 > g.part_bytes) g.part_bytes = g.n_part_big * g.cap_big * 8 + g.n_part_big * 12 + 1024;
-    g.fbq_bytes = g.rank16 ? (((size_t)g.n_qtiles * FS_TQ * v.ld * 4 + 255) & ~(size_t)255) : 0; // vectors of the unsettled queries
-    if (g.big && v.precision == KDB_PREC_F16) g.fbq_bytes = ((size_t)g.fb_nqt * FB_T * v.ld * 2 + 255) & ~(size_t)255; // the queries as halfs
-    g.n_qpad = (size_t)(g.big ? g.fb_nqt * FB_T : g.n_qtiles * FS_TQ); // query rows the ranking kernels may touch (d_q holds >= as many)
-    if (g.rank16 && g.copy_padded) { // ... the ranking scan's query halfs live there first, with the copy's stride
-        const size_t h = ((g.n_qpad * g.vr.ld * 2 + 255) & ~(size_t)255);
-        if (h > g.fbq_bytes) g.fbq_bytes = h;
-    }
-    g.qp_bytes = (g.rank16 && g.copy_padded) ? ((g.n_qpad * g.vr.ld * 4 + 255) & ~(size_t)255) : 0;
-    g.few_tier = g.rank16 && !g.small && g.lds_s <= FS_LDS_MAX;
-    g.want_few = 512u / (FS_FEW / (uint32_t)FSS_TQ);
-    if (g.want_few > stripes_max) g.want_few = stripes_max;
-    {
-        const uint32_t max_tiles = (v.count + FS_TR - 1) / FS_TR;
-        const uint32_t lim = (max_tiles + 3u) / 4u;
-        if (g.want_few > lim) g.want_few = lim;
-        if (g.want_few < 1u) g.want_few = 1u;
-    }
-    g.n_part_few = (size_t)g.want_few * FS_TQ; // one 128-query block of lists per stripe
-    if (g.few_tier && g.n_part_few * g.kl * 8 + g.n_part_few * 4 + 1024 > g.part_bytes) g.part_bytes = g.n_part_few * g.kl * 8 + g.n_part_few * 4 + 1024;
-    g.fbl_bytes = g.rank16 ? (((size_t)g.n_qtiles * FS_TQ * 4 + 255) & ~(size_t)255) : 0; // their indices
-    g.rsl_bytes = ((size_t)g.n_qtiles * FS_TQ * 4 + 255) & ~(size_t)255;                  // queries handed to the rescue pass
-    return g;
-}
-
 // per-stripe lists in `part`: keys, ids, counts of n_part (stripe, query) pairs with cap entries each
 static void fs_set_lists(FsParams &p, unsigned char *part, size_t n_part, uint32_t cap) {
     p.cap = cap;
@@ -2143,28 +1934,28 @@ static int flat_scan_one(kdb_index *idx, const KdbView &v, const void *d_q, cons
                          const uint32_t *d_allow, const uint32_t *d_first_allowed, uint32_t *d_out_ids, float *d_out_dist,
                          uint32_t *d_out_count, int queries_normalised, hipStream_t s) {
     const bool dist64 = (queries_normalised & 2) != 0; // int8: d_out_dist is a double array (KDB_SEARCH_DIST_F64)
-    const FsPlan g = fs_plan(idx, v, B, k, d_allow != nullptr || idx->n_deleted > 0, (queries_normalised & 1) != 0);
+    const FsPlanIn in = fs_plan_in(idx, v, B, k, d_allow != nullptr || idx->n_deleted > 0, (queries_normalised & 1) != 0);
+    const FsPlan g = fs_plan(in);
+    const KdbView vr = fs_rank_view(v, g.ld_rank);
     const FsCall c{idx, v, d_q, d_qnorm, B, k, g.kl, d_out_ids, d_out_dist, d_out_count, s};
 
     // ---- scan list: identity, or the compacted ids of the rows that are live and allowed.  Nothing on this path
     //      waits for the device: the number of rows to scan stays in HBM and every kernel derives the stripe
     //      geometry from it (fs_resolve).
-    // scratch layout: [scan_ids: count u32][n_scan word (256 B)][unsettled queries][their list][rescue list][partials][padded queries]
-    int rc = kdb_ensure_scratch(idx, g.ids_bytes + 256 + g.fbq_bytes + g.fbl_bytes + g.rsl_bytes + g.part_bytes + g.qp_bytes + 4096);
+    int rc = kdb_ensure_scratch(idx, g.total);
     if (rc) return rc;
-    FsBump scratch{reinterpret_cast<unsigned char *>(idx->d_scratch)};
-    uint32_t *d_ids = scratch.take<uint32_t>(g.ids_bytes);
-    uint32_t *d_nscan = scratch.take<uint32_t>(256);
+    uint32_t *d_ids = fs_at<uint32_t>(idx, g.o_ids);
+    uint32_t *d_nscan = fs_at<uint32_t>(idx, g.o_hdr);
     uint32_t *d_fbcount = d_nscan + 4; // inside the 256-byte header
     uint32_t *d_rscount = d_nscan + 8;
-    float *d_fbq = scratch.take<float>(g.fbq_bytes);
-    uint32_t *d_fblist = scratch.take<uint32_t>(g.fbl_bytes);
-    uint32_t *d_rslist = scratch.take<uint32_t>(g.rsl_bytes);
-    unsigned char *part = scratch.take<unsigned char>(g.part_bytes);
+    float *d_fbq = fs_at<float>(idx, g.o_fbq);
+    uint32_t *d_fblist = fs_at<uint32_t>(idx, g.o_fblist);
+    uint32_t *d_rslist = fs_at<uint32_t>(idx, g.o_rslist);
+    unsigned char *part = fs_at<unsigned char>(idx, g.o_part);
     const void *q_rank = d_q; // what the ranking kernels read as queries
     if (g.qp_bytes) {
-        float *d_qp = scratch.take<float>(g.qp_bytes);
-        rc = fs_pad_queries(v, g.vr, d_q, g.n_qpad, d_qp, s);
+        float *d_qp = fs_at<float>(idx, g.o_qpad);
+        rc = fs_pad_queries(v, vr, d_q, g.n_qpad, d_qp, s);
         if (rc) return rc;
         q_rank = d_qp;
     }
@@ -2193,7 +1984,7 @@ static int flat_scan_one(kdb_index *idx, const KdbView &v, const void *d_q, cons
     if (g.rank16 && g.small) p.rows16 = idx->d_rows16;
     if ((g.rank16 && !g.small) || (g.big && v.precision == KDB_PREC_F16)) { // the query halfs live in the buffer the exact pass fills later (it is idle during the ranking scan)
         const bool rk = g.rank16 && g.copy_padded; // (float16 indexes: their own rows, their own stride)
-        const size_t nq_elems = g.n_qpad * (rk ? g.vr.ld : v.ld);
+        const size_t nq_elems = g.n_qpad * (rk ? g.ld_rank : v.ld);
         hipLaunchKernelGGL(queries_to_f16_kernel, dim3((unsigned)((nq_elems / 4 + 255) / 256)), dim3(256), 0, s,
                            reinterpret_cast<const float *>(rk ? q_rank : d_q), nq_elems, reinterpret_cast<uint16_t *>(d_fbq));
         KDB_HIP(hipGetLastError());
@@ -2218,8 +2009,6 @@ static int flat_scan_one(kdb_index *idx, const KdbView &v, const void *d_q, cons
         p.tile_rows = FB_T;
         p.fb_nqt = g.fb_nqt, p.fb_nqg = g.fb_nqg, p.fb_nqx = g.fb_nqx, p.fb_spx = g.fb_spx;
         p.fb_slack = g.fb_slack, p.fb_period = g.fb_period;
-        // the switches of closed experiments, here and nowhere else: no shipped build can set them otherwise
-        p.fb_alt = 1u, p.fb_grow = 1u, p.fb_pref = 0u;
         p.fb_dbg = fs_dbg_switches("KDB_FB_DBG");
         p.fb_seeded = g.fb_seeded, p.fb_seed_nstr = g.fb_seed_nstr;
     }
@@ -2233,8 +2022,8 @@ static int flat_scan_one(kdb_index *idx, const KdbView &v, const void *d_q, cons
             const void *rows_b = pr == FS_PREC_F32R ? (const void *)idx->d_rows16 : v.rows;
             const void *q_b = pr == KDB_PREC_I8 ? d_q : (const void *)d_fbq;
             auto launch_big_one = [&](auto kern) -> int {
-                KDB_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)FB_LDS));
-                hipLaunchKernelGGL(kern, dim3(256), dim3(512), FB_LDS, s, pr == FS_PREC_F32R ? g.vr : v, reinterpret_cast<const unsigned char *>(rows_b),
+                KDB_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)FB_LDS_BASE));
+                hipLaunchKernelGGL(kern, dim3(256), dim3(512), FB_LDS_BASE, s, pr == FS_PREC_F32R ? vr : v, reinterpret_cast<const unsigned char *>(rows_b),
                                    reinterpret_cast<const unsigned char *>(q_b), p);
                 KDB_HIP(hipGetLastError());
                 return KDB_OK;
@@ -2247,10 +2036,10 @@ static int flat_scan_one(kdb_index *idx, const KdbView &v, const void *d_q, cons
         });
     } else {
         // f16-ranked: the ranking copy's view and the queries laid out for it (queries as halfs: half the LDS, more workgroups per CU)
-        const KdbView &v_rank = g.rank16 ? g.vr : v;
+        const KdbView &v_rank = g.rank16 ? vr : v;
         auto rank = [&](auto M, auto P) -> int {
             constexpr int m = decltype(M)::value, pr = decltype(P)::value;
-            if (g.small) return fs_launch_small(c, fss_kernel_for<m, pr>(v_rank.ld), v_rank, q_rank, p, g.n_q16, fs_small_lds_as<pr>(v_rank.ld, g.kl));
+            if (g.small) return fs_launch_small(c, fss_kernel_for<m, pr>(v_rank.ld), v_rank, q_rank, p, g.n_q16, fs_small_lds(pr, v_rank.ld, g.kl));
             return fs_launch_tile(c, flat_scan_kernel<m, pr>, v_rank, q_rank, p);
         };
         rc = g.rank16 ? fs_dispatch<FS_PREC_F32R>(v.precision, v.metric, rank) : fs_dispatch(v.precision, v.metric, rank);
@@ -2262,7 +2051,7 @@ static int flat_scan_one(kdb_index *idx, const KdbView &v, const void *d_q, cons
     uint32_t rtq = FSR_TQ; // queries per rescue work item: as many as fit LDS
     while (rtq > 1 && fsr_lds_bytes(v.ld, rtq) > FS_LDS_MAX) rtq--;
     if (g.rank16) {
-        p.band = fs_band(idx, v);
+        p.band = fs_band(v.metric, idx->max_norm2, v.dim);
         p.fb_count = d_fbcount;
         p.fb_list = d_fblist;
         KDB_HIP(hipMemsetAsync(d_fbcount, 0, 4, s));
@@ -2355,30 +2144,6 @@ static int fs_group_tables(uint32_t B, uint32_t G, const uint32_t *group_offsets
     return KDB_OK;
 }
 
-// Stripes per group.  Workgroup b runs on XCD b % 8 (the dispatcher deals workgroups round-robin) and serves stripe
-// (b/8/T)*8 + b%8, so that the tiles of one stripe share an L2: XCD x owns the stripes s = x (mod 8) and therefore
-// T * ceil-ish(want/8) workgroups for its n_cu/8 CUs.  Round 2 sized `want` as if the chip were one pool of slots: with
-// 105 tiles it picked 9 stripes, which gave XCD 0 twice the work of the others (config 5 ran at 2.85 TB/s).  Now the
-// estimated time -- rounds of the BUSIEST XCD x (rows of a stripe + a start-up allowance for the open threshold of a
-// stripe's first tiles) -- is minimised over the stripe counts the merge can take.
-static uint32_t fs_group_stripes(const kdb_index *idx, uint32_t T, uint32_t G, uint64_t total, uint32_t stripes_max, size_t lds_s) {
-    const uint32_t per_cu = (uint32_t)(160u * 1024u / lds_s) > 0 ? (uint32_t)(160u * 1024u / lds_s) : 1u;
-    const uint32_t slots_x = ((uint32_t)idx->n_cu / 8u > 0 ? (uint32_t)idx->n_cu / 8u : 1u) * (per_cu > 2 ? 2u : per_cu);
-    uint32_t want = 1;
-    const double rows_g = (double)total / (double)G; // rows per group (the caller's bound, or counted)
-    const double startup = 3.0 * FS_TR;
-    double best = 1e300;
-    const uint32_t lim = stripes_max < 64u ? stripes_max : 64u;
-    for (uint32_t w = 1; w <= lim; w++) {
-        if ((double)w * 4.0 * FS_TR > rows_g && w > 1) break; // a stripe is at least min_tiles tiles
-        const uint64_t on_x = (uint64_t)T * ((w + 7u) / 8u);  // workgroups of the busiest XCD
-        const uint64_t rounds = (on_x + slots_x - 1) / slots_x;
-        const double t = (double)rounds * (rows_g / (double)w + startup);
-        if (t < best * 0.98) { best = t; want = w; } // the fewest stripes within 2 % of the best
-    }
-    return want;
-}
-
 int kdb_launch_flat_scan_groups(kdb_index *idx, const KdbView &v, const void *d_q, const float *d_qnorm, uint32_t B,
                                 uint32_t k, uint32_t G, const uint32_t *group_offsets, const uint32_t *d_lists,
                                 uint32_t words32, uint64_t max_total_allowed, uint32_t *d_out_ids, float *d_out_dist,
@@ -2388,8 +2153,9 @@ int kdb_launch_flat_scan_groups(kdb_index *idx, const KdbView &v, const void *d_
         return KDB_ERR_INVALID;
     }
     if (B == 0 || G == 0) return KDB_OK;
+    const FsPlanIn in = fs_plan_in(idx, v, B, k, true, queries_normalised != 0);
     const uint32_t kl = fs_kl(k); // finalists are re-scored in the order of the graph search
-    const size_t lds_s = fs_small_lds(v, kl);
+    const size_t lds_s = fs_small_lds((int)v.precision, v.ld, kl);
     if (lds_s > FS_LDS_MAX) {
         kdb_set_error("grouped flat scan: %u-d rows need %zu bytes of LDS per workgroup", v.dim, lds_s);
         return KDB_ERR_UNSUPPORTED;
@@ -2403,11 +2169,10 @@ int kdb_launch_flat_scan_groups(kdb_index *idx, const KdbView &v, const void *d_
 
     // group sizes first if the caller gave no bound (one 4*G-byte read-back)
     const size_t chunk_words = (size_t)G * FG_NB;
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    rc = kdb_ensure_scratch(idx, al(chunk_words * 4) * 2 + al((size_t)G * 4) * 2 + 4096);
-    if (rc) return rc;
     uint64_t total = max_total_allowed;
     if (total == 0) {
+        rc = kdb_ensure_scratch(idx, fs_group_count_bytes(G));
+        if (rc) return rc;
         uint32_t *d_gn0 = reinterpret_cast<uint32_t *>(idx->d_scratch);
         hipLaunchKernelGGL(group_count_kernel, ggrid, dim3(256), 0, s, v.deleted, d_lists, words32, v.count, d_gn0);
         KDB_HIP(hipGetLastError());
@@ -2418,35 +2183,30 @@ int kdb_launch_flat_scan_groups(kdb_index *idx, const KdbView &v, const void *d_
         if (total == 0) total = 1;
     }
     if (total > (uint64_t)G * v.count) total = (uint64_t)G * v.count;
-    const uint32_t want = fs_group_stripes(idx, T, G, total, FS_MAX_MERGE / kl, lds_s);
-    const uint32_t n_qtiles = (B + FS_TQ - 1) / FS_TQ;
-    const size_t n_part = (size_t)want * n_qtiles * FS_TQ;
-
-    const size_t ids_bytes = (size_t)total * 4 + 1024;
-    const size_t part_bytes = n_part * kl * 8 + n_part * 4 + 1024;
-    const KdbView vr = fs_rank_view(idx, v);
-    const size_t qp_bytes = vr.ld != v.ld ? al((size_t)B * vr.ld * 4) : 0;
-    rc = kdb_ensure_scratch(idx, al(ids_bytes) + al((size_t)G * 4) * 2 + al(chunk_words * 4) * 2 + al(tiles.size() * 4) * 2 + al((size_t)B * 4) * 4 + 256 +
-                                     al(part_bytes) + qp_bytes + 4096);
+    // stripes, the ranking copy and the scratch layout: fs_group_plan (kl and lds_s above are the same functions' values)
+    const FsGroupPlan g = fs_group_plan(in, (uint32_t)idx->n_cu, T, G, total);
+    const uint32_t want = g.want, n_qtiles = g.n_qtiles;
+    const size_t n_part = g.n_part;
+    const KdbView vr = fs_rank_view(v, g.ld_rank);
+    rc = kdb_ensure_scratch(idx, g.total);
     if (rc) return rc;
-    FsBump scratch{reinterpret_cast<unsigned char *>(idx->d_scratch)};
-    uint32_t *d_ids = scratch.take<uint32_t>(ids_bytes);
-    uint32_t *d_gn = scratch.take<uint32_t>((size_t)G * 4);
-    uint32_t *d_gbase = scratch.take<uint32_t>((size_t)G * 4);
-    uint32_t *d_ccnt = scratch.take<uint32_t>(chunk_words * 4);  // [G][FG_NB] rows per chunk
-    uint32_t *d_cbase = scratch.take<uint32_t>(chunk_words * 4); // where each chunk writes
-    uint32_t *d_tiles = scratch.take<uint32_t>(tiles.size() * 4);
-    uint32_t *d_qgrp = scratch.take<uint32_t>((size_t)B * 4);
-    uint32_t *d_qtile = scratch.take<uint32_t>((size_t)B * 4);
-    uint32_t *d_qflag = scratch.take<uint32_t>((size_t)B * 4);
-    uint32_t *d_tflag = scratch.take<uint32_t>(tiles.size() * 4);
-    uint32_t *d_fbc = scratch.take<uint32_t>(256);
+    uint32_t *d_ids = fs_at<uint32_t>(idx, g.o_ids);
+    uint32_t *d_gn = fs_at<uint32_t>(idx, g.o_gn);
+    uint32_t *d_gbase = fs_at<uint32_t>(idx, g.o_gbase);
+    uint32_t *d_ccnt = fs_at<uint32_t>(idx, g.o_ccnt);   // [G][FG_NB] rows per chunk
+    uint32_t *d_cbase = fs_at<uint32_t>(idx, g.o_cbase); // where each chunk writes
+    uint32_t *d_tiles = fs_at<uint32_t>(idx, g.o_tiles);
+    uint32_t *d_qgrp = fs_at<uint32_t>(idx, g.o_qgrp);
+    uint32_t *d_qtile = fs_at<uint32_t>(idx, g.o_qtile);
+    uint32_t *d_qflag = fs_at<uint32_t>(idx, g.o_qflag);
+    uint32_t *d_tflag = fs_at<uint32_t>(idx, g.o_tflag);
+    uint32_t *d_fbc = fs_at<uint32_t>(idx, g.o_hdr);
     uint32_t *d_rsc = d_fbc + 4; // queries handed to the rescue pass: count (inside the 256-byte block), list
-    uint32_t *d_rsl = scratch.take<uint32_t>((size_t)B * 4);
-    unsigned char *part = scratch.take<unsigned char>(part_bytes);
+    uint32_t *d_rsl = fs_at<uint32_t>(idx, g.o_rsl);
+    unsigned char *part = fs_at<unsigned char>(idx, g.o_part);
     // float32 indexes with a half-precision row copy rank on it inside the error band (see fs_plan); the
     // exact pass re-runs only the tiles that hold an unsettled query, with their group's id list
-    const bool rank16 = idx->d_rows16 && fs_rank16_ok(idx, v, queries_normalised != 0);
+    const bool rank16 = g.rank16;
 
     FsParams p{};
     p.ctr = kdb_stats_begin(idx, 2, B, 0);
@@ -2455,7 +2215,7 @@ int kdb_launch_flat_scan_groups(kdb_index *idx, const KdbView &v, const void *d_
     KDB_HIP(hipMemcpyAsync(d_tiles, tiles.data(), tiles.size() * 4, hipMemcpyHostToDevice, s));
     KDB_HIP(hipMemcpyAsync(d_qgrp, qgrp.data(), (size_t)B * 4, hipMemcpyHostToDevice, s));
     KDB_HIP(hipMemcpyAsync(d_qtile, qtile.data(), (size_t)B * 4, hipMemcpyHostToDevice, s));
-    KDB_HIP(hipMemsetAsync(d_qflag, 0, al((size_t)B * 4) + al(tiles.size() * 4) + 256, s)); // q_flag, tile_flag, count
+    KDB_HIP(hipMemsetAsync(d_qflag, 0, g.o_rsl - g.o_qflag, s)); // q_flag, tile_flag, count
     hipLaunchKernelGGL(group_count_kernel, ggrid, dim3(256), 0, s, v.deleted, d_lists, words32, v.count, d_ccnt);
     hipLaunchKernelGGL(group_prefix_kernel, dim3(1), dim3(256), 0, s, d_ccnt, G, d_cbase, d_gn, d_gbase, p.ctr);
     hipLaunchKernelGGL(group_fill_kernel, ggrid, dim3(256), 0, s, v.deleted, d_lists, words32, v.count, d_cbase, d_ids);
@@ -2487,8 +2247,8 @@ int kdb_launch_flat_scan_groups(kdb_index *idx, const KdbView &v, const void *d_
     const void *q_rank = d_q;
     if (rank16) {
         p.rows16 = idx->d_rows16;
-        if (qp_bytes) {
-            float *d_qp = scratch.take<float>(qp_bytes);
+        if (vr.ld != v.ld) {
+            float *d_qp = fs_at<float>(idx, g.o_qpad);
             rc = fs_pad_queries(v, vr, d_q, B, d_qp, s);
             if (rc) return rc;
             q_rank = d_qp;
@@ -2497,7 +2257,7 @@ int kdb_launch_flat_scan_groups(kdb_index *idx, const KdbView &v, const void *d_
     const KdbView &v_rank = rank16 ? vr : v;
     auto rank = [&](auto M, auto P) -> int {
         constexpr int m = decltype(M)::value, pr = decltype(P)::value;
-        return fs_launch_small(c, fss_kernel_for<m, pr>(v_rank.ld), v_rank, q_rank, p, T, fs_small_lds_as<pr>(v_rank.ld, kl));
+        return fs_launch_small(c, fss_kernel_for<m, pr>(v_rank.ld), v_rank, q_rank, p, T, fs_small_lds(pr, v_rank.ld, kl));
     };
     rc = rank16 ? fs_dispatch<FS_PREC_F32R>(v.precision, v.metric, rank) : fs_dispatch(v.precision, v.metric, rank);
     if (rc) return rc;
@@ -2505,7 +2265,7 @@ int kdb_launch_flat_scan_groups(kdb_index *idx, const KdbView &v, const void *d_
 
     // ---- settle (grouped scan: one query per rescue work item)
     if (rank16) {
-        p.band = fs_band(idx, v);
+        p.band = fs_band(v.metric, idx->max_norm2, v.dim);
         p.fb_count = d_fbc;
         p.q_flag = d_qflag;
         p.tile_flag = d_tflag;

@@ -46,17 +46,10 @@
 #define FB_DBG 0u
 #endif
 #define FB_SB() __builtin_amdgcn_sched_barrier(0)
-constexpr int FB_T = 256;        // rows per tile = queries per tile
-constexpr int FB_SLAB = 128;     // bytes of every row per K slab
-constexpr int FB_CSLOTS = 20;     // fs_compact_wave register slots: a list never holds more than 64 * 20 entries
+// (FB_T = 256 rows per tile = queries per tile, FB_SLAB = 128 bytes of every row per K slab, FB_CSLOTS and fb_cap: kdb_flat_plan.h)
 constexpr uint32_t FB_DUMPS = 96; // 16-score blocks a wave can park in its scratch between two phase-B passes
 constexpr uint32_t FB_STAGE = 2u * FB_T * FB_SLAB; // one slab buffer: rows + queries = 64 KB
 constexpr size_t FB_LDS_BASE = 2u * FB_STAGE + FB_T * 12u + 2u * FB_T * 8u + FB_T * 4u + 64u;
-constexpr size_t FB_LDS = FB_LDS_BASE + 4u * 256u; // + the landing words of the row prefetch (four waves x 64 lanes x 4 B)
-
-// entries allocated per (stripe, query): lists are compacted every `period` tiles when they hold more than kl + slack
-// entries, and a tile appends at most FB_T entries to a list
-__host__ __device__ inline uint32_t fb_cap(uint32_t kl, uint32_t slack, uint32_t period) { return kl + slack + period * (uint32_t)FB_T; }
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef int i32x16 __attribute__((ext_vector_type(16)));
@@ -87,21 +80,6 @@ __device__ __forceinline__ void fb_glds4(const unsigned char *g0, const unsigned
                  : "v"(g0), "v"(g1), "v"(g2), "v"(g3), "s"(lds_dst)
                  : "memory", "scc");
 }
-// One dword per lane from each lane's own address to LDS lds_dst + lane*4: used as a PREFETCH -- the line of a row slab that the
-// slab DMA will ask for three steps later is pulled into the XCD's L2 now (the landing words are never read).  LDS-DMA rather than
-// a register load: nothing to keep alive, nothing the compiler could reuse too early.
-__device__ __forceinline__ void fb_glds1(const unsigned char *g0, uint32_t lds_dst /* wave-uniform */) {
-    uint32_t keep;
-    asm volatile("s_mov_b32 %0, m0\n\t"
-                 "s_mov_b32 m0, %2\n\t"
-                 "s_nop 0\n\t"
-                 "global_load_lds_dword %1, off\n\t"
-                 "s_mov_b32 m0, %0"
-                 : "=&s"(keep)
-                 : "v"(g0), "s"(lds_dst)
-                 : "memory");
-}
-__device__ __forceinline__ void fb_dma_wait1() { asm volatile("s_waitcnt vmcnt(1)" ::: "memory"); } // all but the youngest request
 __device__ __forceinline__ float fb_max3(float a, float b, float c) { return fmaxf(fmaxf(a, b), c); }
 __device__ __forceinline__ void fb_dma_wait() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 
@@ -143,12 +121,8 @@ flat_scan_big_kernel(KdbView v, const unsigned char *__restrict__ rows8 /* rowb 
     uint32_t row_begin = stripe * geo.rows_per_stripe;
     uint32_t row_end = row_begin + geo.rows_per_stripe < geo.n_scan ? row_begin + geo.rows_per_stripe : geo.n_scan;
     uint32_t q0 = qtile * FB_T;
-    // The host decides on the seed launch from ITS copy of the stripe geometry ("same integer arithmetic as fs_resolve_n",
-    // flat_scan.hip).  Both launches re-check on the device, with the same expression: every stripe holds a whole tile, a stripe's
-    // share of the kl best fits the sixteen block maxima, and the host's stripe count is fs_resolve's.  Should the two ever drift,
-    // the seed publishes nothing and the scan reads nothing -- open thresholds, slower, still exact.
-    const bool seed_ok = p.fb_seeded && p.fb_seed_nstr == geo.n_stripes && geo.n_stripes >= 2u &&
-                         (geo.n_stripes - 1u) * geo.rows_per_stripe + FB_T <= geo.n_scan && (p.kl + geo.n_stripes - 1u) / geo.n_stripes <= 16u;
+    // The host decided on the seed launch with this predicate on this geometry (fs_plan); both launches check it on the device.
+    const bool seed_ok = fs_seed_ok(geo, p.kl, p.fb_seeded, p.fb_seed_nstr);
     if (SEED) {
         if (!seed_ok) return;
         row_end = row_begin + FB_T;
@@ -292,11 +266,6 @@ flat_scan_big_kernel(KdbView v, const unsigned char *__restrict__ rows8 /* rowb 
     unsigned long long tm_sel = 0, tm_cmp = 0;
     unsigned long long n_app = 0, n_dmp = 0, n_cmp = 0; // debug counts (FB_DBG & 256 / 512)
     uint32_t t = 0;
-    // row prefetch (p.fb_pref, rows of >= 4 slabs, not the seed launch): thread r < 256 touches row r's line of the slab that is
-    // computed three steps from now -- this tile's, or the next tile's first slabs
-    const bool pf_on = !SEED && p.fb_pref != 0u && nslab >= 4u && tid < FB_T;
-    const uint32_t pf_lds = __builtin_amdgcn_readfirstlane(lds0 + (uint32_t)FB_LDS_BASE + ((uint32_t)wave & 3u) * 256u);
-    uint32_t cur_id = tid < FB_T ? sel_id[tid] : 0u; // the row this thread prefetches: row tid of the current tile
     for (uint32_t tile = row_begin; tile < row_end; tile += FB_T, t++) {
         const uint32_t tp = t & 1u;
         const bool has_next = tile + FB_T < row_end;
@@ -336,8 +305,8 @@ flat_scan_big_kernel(KdbView v, const unsigned char *__restrict__ rows8 /* rowb 
             const bool dma = (dma_same || dma_next) && !(FB_DBG & 2u);
             // odd tiles walk their slabs backwards: the query slabs the previous tile used last are requested first, while
             // they are still in the XCD's L2 (a tile period streams more bytes through an XCD than its L2 holds)
-            const uint32_t odd = t & p.fb_alt;
-            const uint32_t nslab_i = dma_same ? (odd ? nslab - 2u - s : s + 1u) : ((odd || !p.fb_alt) ? 0u : nslab - 1u);
+            const uint32_t odd = t & 1u;
+            const uint32_t nslab_i = dma_same ? (odd ? nslab - 2u - s : s + 1u) : (odd ? 0u : nslab - 1u);
             if (dma_next) {
 #pragma unroll
                 for (int j = 0; j < 4; j++)
@@ -354,19 +323,6 @@ flat_scan_big_kernel(KdbView v, const unsigned char *__restrict__ rows8 /* rowb 
             FB_SB();
             read_frags(0, buf, 2);
             if (dma) issue_queries(buf ^ 1u, nslab_i);
-            bool pf = false; // (wave-uniform: waves 0..3 hold the threads r < 256)
-            if (pf_on) { // the slab computed at step s + 3: of this tile (walked backwards when the tile is odd), or of the next one
-                if (s + 3u < nslab) {
-                    const uint32_t sl = odd ? nslab - 1u - (s + 3u) : s + 3u;
-                    fb_glds1(rows8 + (size_t)cur_id * rowb + sl * FB_SLAB, pf_lds);
-                    pf = true;
-                } else if (has_next) {
-                    const uint32_t s2 = s + 3u - nslab, odd2 = p.fb_alt ? (odd ^ 1u) : 0u;
-                    const uint32_t sl = odd2 ? nslab - 1u - s2 : s2;
-                    fb_glds1(rows8 + (size_t)n_id * rowb + sl * FB_SLAB, pf_lds);
-                    pf = true;
-                }
-            }
             FB_SB();
             mfma_step(1);
             FB_SB();
@@ -374,8 +330,7 @@ flat_scan_big_kernel(KdbView v, const unsigned char *__restrict__ rows8 /* rowb 
             FB_SB();
             mfma_step(0);
             FB_SB();
-            if (pf) fb_dma_wait1(); // (the prefetch is the youngest request: it may stay in flight)
-            else fb_dma_wait();
+            fb_dma_wait();
             // ids / norms of the next tile: stored BEFORE the first slab's barrier.  The last slab step reads them (aptr, above)
             // and with two-slab rows that step is the next one: stored behind this barrier they raced with it (waves 4-7 read
             // what waves 0-3 had not written yet: stale or never-written ids -> wrong rows ranked, or a fault).  The other
@@ -549,8 +504,8 @@ flat_scan_big_kernel(KdbView v, const unsigned char *__restrict__ rows8 /* rowb 
         __syncthreads(); // appends (LDS counts, list entries in HBM scratch) are complete; the dump scratch is free again
         // (a lighter barrier here -- s_waitcnt lgkmcnt(0) + s_barrier, the store acknowledgements returning behind the next
         //  tile's first MFMA steps -- measured no different: 12.25 vs 12.26 ms)
-        uint32_t per = p.fb_period;
-        if (p.fb_grow) per = t < 64u ? per : t < 128u ? 2u * per : t < 256u ? 4u * per : 8u * per; // (powers of two: rounds stay aligned)
+        // (the rounds thin out once the thresholds have settled; powers of two: rounds stay aligned)
+        const uint32_t per = t < 64u ? p.fb_period : t < 128u ? 2u * p.fb_period : t < 256u ? 4u * p.fb_period : 8u * p.fb_period;
         const bool compact_now = ((t == 0u && !seed_ok) || (t + 1u) % per == 0u || flags[2] != 0u) && has_next;
         if (tm_on && (FB_DBG & 2048u)) tm_cmp += __builtin_readcyclecounter() - tm1; // 2048: the wait at this barrier alone
         if (compact_now) { // (the first tile keeps everything: thresholds start open)
@@ -581,7 +536,6 @@ flat_scan_big_kernel(KdbView v, const unsigned char *__restrict__ rows8 /* rowb 
             if (p.g_pub) read_published();
         }
         if (tm_on && !(FB_DBG & 2048u)) tm_cmp += __builtin_readcyclecounter() - tm1;
-        cur_id = n_id;
     }
     if ((FB_DBG & 32u) && p.ctr && lane == 0) { // per-wave cycle totals: selection phases, compaction rounds (with their barriers)
         atomicAdd(p.ctr + 2, tm_sel);
