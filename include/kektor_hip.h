@@ -54,9 +54,11 @@
  *     request).  The host-pointer entry points (kdb_search_batch, kdb_flat_scan_batch, kdb_distance_batch) hold the handle's
  *     lock only to pick one of KDB_SLOTS (4, at most 16) slots -- a stream and a pair of staging buffers -- and to enqueue;
  *     they wait for their answers outside it.  One-query callers that find every slot busy are combined: calls of up to
- *     KDB_COMBINE_MAX_B (16) queries with the same (k, ef, flags) and no allow list leave as ONE launch as soon as a slot is
+ *     KDB_COMBINE_MAX_B (16) queries with the same flags and no allow list -- whatever their k and ef: the launch reads them
+ *     per query, kdb_search_batch_mixed below; KDB_COMBINE_MIXED=0 at kdb_index_create: the same (k, ef) only -- leave as ONE
+ *     launch as soon as a slot is
  *     free (no window, no timer: a lone caller never waits), and that launch stays open for KDB_SESSION_US (300) microseconds:
- *     a matching call that arrives while its kernel runs is written into its page-locked buffer and walked by a workgroup that
+ *     a call it can hold that arrives while its kernel runs is written into its page-locked buffer and walked by a workgroup that
  *     waited for it -- no launch of its own (with KDB_SEARCH_HEAP_ORDER a query that meets equal distances is answered once its
  *     launch has closed: up to that window later); kdb_index_caller_stats counts launches and the calls they carried.
  *     Writers -- uploads, kdb_index_mark_deleted, kdb_index_set_entry, build / add_batch, reserve, destroy -- wait until no
@@ -277,6 +279,32 @@ KDB_API int kdb_search_batch_multi_dev(kdb_index *idx, const float *d_queries, u
                                const uint64_t *d_allow_lists, uint32_t G, uint64_t words_per_list,
                                const uint32_t *d_allow_of_query, uint32_t flags, uint32_t *d_out_ids,
                                float *d_out_dist, uint32_t *d_out_count, void *stream);
+
+/* SearchWithScores for B requests that differ in k and efSearch: query b is answered exactly as kdb_search_batch answers it alone
+ * with (k[b], ef[b]) -- ids, distances, order, counters.  out_ids / out_dist are [B][k_stride], out_count [B]; positions
+ * [count, k_stride) of a row hold id 0 and +inf.  ONE launch walks them all: its beam is sized for the largest effective ef of the
+ * batch (the KDB_SEARCH_NEEDS_REFINE boost first, then max(ef, k)), rounded up to the top of its beam class -- 64, 128, 256, or the
+ * value itself above 256 (kdb_mixed_plan.h holds the rules).  A small-ef query walked in a larger class returns the same answer.
+ * Host pointers: any k[b] == 0 or k[b] > k_stride is KDB_ERR_INVALID and nothing is launched; allow_bits as for kdb_search_batch
+ * (one optional list for the whole batch).  Flags as for kdb_search_batch; kdb_search_set_trace applies.  The call goes out alone,
+ * through a slot or (traced, KDB_SEARCH_FAIL_ON_DROP, too large for a slot) on a turn of the index's staging buffer; it is not cut
+ * into chunks.
+ * Device pointers: the host cannot read d_k / d_ef, so the caller states ef_max, the largest effective ef it will send; a query with
+ * k == 0, k > k_stride or an effective ef above the launch's capacity comes back as count 0 | KDB_MIXED_BAD_QUERY (bit 30 of
+ * out_count) and is never walked.  Per-query allow lists as for kdb_search_batch_multi_dev; G == 0: d_allow_lists is one optional
+ * list shared by the batch, as kdb_search_batch_dev has it.
+ * kdb_index_mixed_stats, out[4]: [0] launches that carried at least two distinct (k, effective ef), [1] the calls they carried,
+ * [2] callers that could not join an open launch because of their k or ef, [3] reserved (0).  ([0] and [1] count host-pointer
+ * calls: the library never reads the device arrays of the _dev form.) */
+#define KDB_MIXED_BAD_QUERY 0x40000000u
+KDB_API int kdb_search_batch_mixed(kdb_index *idx, const float *queries, uint32_t B, const uint32_t *k, const uint32_t *ef,
+                                   uint32_t k_stride, const uint64_t *allow_bits, uint32_t flags,
+                                   uint32_t *out_ids, float *out_dist, uint32_t *out_count);
+KDB_API int kdb_search_batch_mixed_dev(kdb_index *idx, const float *d_queries, uint32_t B, const uint32_t *d_k, const uint32_t *d_ef,
+                                       uint32_t k_stride, uint32_t ef_max,
+                                       const uint64_t *d_allow_lists, uint32_t G, uint64_t words_per_list, const uint32_t *d_allow_of_query,
+                                       uint32_t flags, uint32_t *d_out_ids, float *d_out_dist, uint32_t *d_out_count, void *stream);
+KDB_API int kdb_index_mixed_stats(kdb_index *idx, uint64_t *out /* [4] */);
 
 /* SearchWithScores for B queries.  queries: [B][dim] f32, un-normalised (the library performs the
  * reference's query prep, hnsw_index.go:404-434).  allow_bits: NULL (nil allow-list) or

@@ -22,6 +22,7 @@
 #include <stdexcept>
 #include <string>
 #include <tuple>
+#include <utility>
 #include <vector>
 
 #include <linux/futex.h> // (the batcher's followers sleep on a futex word: Linux, like the library itself)
@@ -294,6 +295,29 @@ class Index {
             for (uint32_t i = 0; i < cnt[b]; i++) out[b].push_back({ids[(size_t)b * k + i], score(dist, (size_t)b * k + i)});
         return out;
     }
+    // B requests that differ in k and efSearch, ONE launch (kdb_search_batch_mixed): results[b] is what SearchWithScores(query b, ks[b],
+    // allowList, efs[b]) returns; a k <= 0 anywhere, or any error, gives empty lists, like SearchBatch
+    std::vector<std::vector<SearchResult>> SearchMixed(const float *queries, uint32_t B, const std::vector<int> &ks, const std::vector<int> &efs,
+                                                       const AllowList *allowList) const {
+        std::vector<std::vector<SearchResult>> out(B);
+        if (!h_ || B == 0 || ks.size() != B || efs.size() != B) return out;
+        std::vector<uint32_t> k(B), ef(B);
+        uint32_t stride = 0;
+        for (uint32_t b = 0; b < B; b++) {
+            if (ks[b] <= 0) return out;
+            k[b] = (uint32_t)ks[b];
+            ef[b] = (uint32_t)(efs[b] > 0 ? efs[b] : 0);
+            if (k[b] > stride) stride = k[b];
+        }
+        std::vector<uint32_t> ids((size_t)B * stride), cnt(B);
+        DistBuf dist((size_t)B * stride, wide());
+        int rc = kdb_search_batch_mixed(h_, queries, B, k.data(), ef.data(), stride, allowList ? allowList->words.data() : nullptr, flags(), ids.data(),
+                                        dist.ptr(), cnt.data());
+        if (rc) return out;
+        for (uint32_t b = 0; b < B; b++)
+            for (uint32_t i = 0; i < cnt[b]; i++) out[b].push_back({ids[(size_t)b * stride + i], score(dist, (size_t)b * stride + i)});
+        return out;
+    }
     // exact scan over live (and allowed) rows: BruteForceIndex.SearchWithScores semantics (vector_index.go:104-140)
     std::vector<std::vector<SearchResult>> FlatScanBatch(const float *queries, uint32_t B, int k, const AllowList *allowList) const {
         std::vector<std::vector<SearchResult>> out(B);
@@ -423,7 +447,10 @@ class Index {
 // the Go shim's hipBatcher, integration/go/hnsw_hip.go).  SearchWithScores keeps the contract of
 // hnsw.Index.SearchWithScores (hnsw_index.go:343-366): it blocks until the caller's answer is ready and returns an
 // empty slice on any error, on a stopped batcher and for a non-nil empty allow list.
-//   * callers that share (k, efSearch, allow-list object) share a group; the first caller of a group is its leader;
+//   * callers that share (k, efSearch, allow-list object) share a group; the first caller of a group is its leader.  Over an index
+//     that offers SearchMixed (kektor::hnsw::Index does: kdb_search_batch_mixed walks requests of different k and efSearch in one
+//     launch) the callers of one allow list share a group WHATEVER their k and efSearch -- unless the list is so selective that the
+//     group takes the exact scan (below), which has one k per call: those keep the full key;
 //   * PIPELINED: up to `maxInFlight` (2) groups are on the device at once (the library serves concurrent calls from separate
 //     slots: include/kektor_hip.h, "Conventions").  A leader that finds a turn free goes AT ONCE -- a lone caller never sleeps;
 //     while every turn is taken its group stays open and grows for free, so batch size follows the load: everything that
@@ -454,6 +481,7 @@ class BasicMicroBatcher {
     struct Stats {
         uint64_t calls = 0, batches = 0, flatBatches = 0, largest = 0;
         uint64_t passedThrough = 0; // unfiltered calls handed to an index that combines concurrent calls itself
+        uint64_t mixedBatches = 0;  // batches that went out through SearchMixed (callers of one allow list, any k and efSearch)
     };
     static constexpr int kMaxFlatK = 1024; // kdb_flat_scan_batch: k <= 1024
     explicit BasicMicroBatcher(IndexT &idx) : idx_(idx) {}
@@ -488,10 +516,13 @@ class BasicMicroBatcher {
             auto out = idx_.SearchBatch(query.data(), 1, k, nullptr, efSearch);
             return out.empty() ? std::vector<SearchResult>() : std::move(out[0]);
         }
+        // one group per allow list whatever k and efSearch are, where the index can walk such a group in one launch and the list does
+        // not send it to the exact scan (counted outside the lock: the list belongs to the caller)
+        const bool mix = allowList && mixes(idx_, 0) && !takes_flat_scan(k, allowList);
         std::unique_lock<std::mutex> lk(mu_);
         if (closed_) return {};
         stats_.calls++;
-        const Key key{k, efSearch, allowList};
+        const Key key = mix ? Key{-1, -1, allowList} : Key{k, efSearch, allowList};
         std::shared_ptr<Group> g;
         auto it = groups_.find(key);
         const bool leader = it == groups_.end();
@@ -503,6 +534,8 @@ class BasicMicroBatcher {
         }
         const size_t me = g->queries.size();
         g->queries.push_back(query.data());
+        g->ks.push_back(k);
+        g->efs.push_back(efSearch);
         if (g->queries.size() >= opt_.maxBatch) { // full: later callers start the next group
             groups_.erase(key);
             g->sealed = true;
@@ -534,16 +567,11 @@ class BasicMicroBatcher {
             const uint32_t dim = idx_.Dim();
             std::vector<float> Q((size_t)B * dim);
             for (uint32_t b = 0; b < B; b++) std::memcpy(Q.data() + (size_t)b * dim, g->queries[b], (size_t)dim * 4);
-            if (allowList) {
-                uint64_t allowed = 0;
-                for (uint64_t w : allowList->words) allowed += (uint64_t)__builtin_popcountll(w);
-                const uint32_t count = idx_.Count();
-                // the exact scan answers k <= kMaxFlatK (kdb_flat_scan_batch); larger k keeps the graph walk, which still
-                // answers -- routing must never turn a query the reference would answer into []
-                flat = allowed > 0 && count > 0 && k <= kMaxFlatK && (double)allowed < opt_.flatScanSelectivity * (double)count;
-            }
+            if (allowList && !mix) flat = takes_flat_scan(k, allowList);
             try {
-                out = flat ? idx_.FlatScanBatch(Q.data(), B, k, allowList) : idx_.SearchBatch(Q.data(), B, k, allowList, efSearch);
+                out = flat  ? idx_.FlatScanBatch(Q.data(), B, k, allowList)
+                      : mix ? search_mixed(idx_, 0, Q.data(), B, g->ks, g->efs, allowList)
+                            : idx_.SearchBatch(Q.data(), B, k, allowList, efSearch);
             } catch (const std::exception &) {
                 out.clear();
                 if (flat) { // the scan refused (an argument it does not take): the walk is the reference's own path
@@ -560,6 +588,7 @@ class BasicMicroBatcher {
         if (!stopped) inflight_--;
         stats_.batches++;
         if (flat) stats_.flatBatches++;
+        if (mix && !stopped) stats_.mixedBatches++;
         if (B > stats_.largest) stats_.largest = B;
         lk.unlock();
         turn_cv_.notify_all(); // (leaders only: one per open group)
@@ -574,9 +603,36 @@ class BasicMicroBatcher {
     // IndexT::CombinesConcurrentCalls() if it exists, else false (a test double, an index behind another transport)
     template <class T> static auto combines(const T &i, int) -> decltype(i.CombinesConcurrentCalls()) { return i.CombinesConcurrentCalls(); }
     template <class T> static bool combines(const T &, long) { return false; }
+    // ... and IndexT::SearchMixed the same way: an index without it (today's test doubles) keeps the (k, efSearch, list) keying
+    template <class T>
+    static auto mixes(T &i, int) -> decltype(i.SearchMixed((const float *)nullptr, 0u, std::declval<const std::vector<int> &>(),
+                                                                 std::declval<const std::vector<int> &>(), (const AllowList *)nullptr), true) {
+        return true;
+    }
+    template <class T> static bool mixes(T &, long) { return false; }
+    template <class T>
+    static auto search_mixed(T &i, int, const float *q, uint32_t B, const std::vector<int> &ks, const std::vector<int> &efs, const AllowList *a)
+        -> decltype(i.SearchMixed(q, B, ks, efs, a)) {
+        return i.SearchMixed(q, B, ks, efs, a);
+    }
+    template <class T>
+    static std::vector<std::vector<SearchResult>> search_mixed(T &, long, const float *, uint32_t, const std::vector<int> &, const std::vector<int> &,
+                                                               const AllowList *) {
+        return {};
+    }
+    // a filter that allows less than flatScanSelectivity of the ids takes the exact scan, which answers k <= kMaxFlatK
+    // (kdb_flat_scan_batch); larger k keeps the graph walk, which still answers -- routing must never turn a query the reference
+    // would answer into []
+    bool takes_flat_scan(int k, const AllowList *allowList) const {
+        uint64_t allowed = 0;
+        for (uint64_t w : allowList->words) allowed += (uint64_t)__builtin_popcountll(w);
+        const uint32_t count = idx_.Count();
+        return allowed > 0 && count > 0 && k <= kMaxFlatK && (double)allowed < opt_.flatScanSelectivity * (double)count;
+    }
     using Key = std::tuple<int, int, const AllowList *>;
     struct Group {
         std::vector<const float *> queries; // callers' buffers: they are blocked in SearchWithScores until done
+        std::vector<int> ks, efs;           // ... and what each of them asked for (a group over SearchMixed holds several)
         std::vector<std::vector<SearchResult>> results;
         bool sealed = false;               // (under mu_)
         std::atomic<uint32_t> done{0};     // futex word

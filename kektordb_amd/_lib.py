@@ -29,6 +29,7 @@ ABI_SYMBOLS = [
     "kdb_index_vacuum", "kdb_index_dead_link_scan", "kdb_index_drop_walk_planes", "kdb_index_add",
     "kdb_index_decode_rows", "kdb_index_decode_rows_dev", "kdb_search_by_id", "kdb_search_by_id_dev", "kdb_flat_scan_by_id", "kdb_flat_scan_by_id_dev",
     "kdb_consensus_batch", "kdb_consensus_batch_dev", "kdb_belief_batch", "kdb_belief_batch_dev",
+    "kdb_search_batch_mixed", "kdb_search_batch_mixed_dev", "kdb_index_mixed_stats",
 ]
 
 
@@ -140,6 +141,9 @@ def load():
     L.kdb_search_batch.argtypes = [vp, vp, u32, u32, u32, vp, u32, vp, vp, vp]
     L.kdb_search_batch_dev.argtypes = [vp, vp, u32, u32, u32, vp, u32, vp, vp, vp, vp]
     L.kdb_search_batch_multi_dev.argtypes = [vp, vp, u32, u32, u32, vp, u32, C.c_uint64, vp, u32, vp, vp, vp, vp]
+    L.kdb_search_batch_mixed.argtypes = [vp, vp, u32, vp, vp, u32, vp, u32, vp, vp, vp]
+    L.kdb_search_batch_mixed_dev.argtypes = [vp, vp, u32, vp, vp, u32, u32, vp, u32, C.c_uint64, vp, u32, vp, vp, vp, vp]
+    L.kdb_index_mixed_stats.argtypes = [vp, vp]
     L.kdb_flat_scan_groups_dev.argtypes = [vp, vp, u32, u32, u32, vp, vp, C.c_uint64, C.c_uint64, u32, vp, vp, vp, vp]
     L.kdb_index_append_nodes.argtypes = [vp, u32, u32, vp]
     L.kdb_index_patch_adjacency.argtypes = [vp, u32, u32, vp, vp, vp]

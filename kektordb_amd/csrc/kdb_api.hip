@@ -349,6 +349,8 @@ extern "C" int kdb_index_create(const kdb_index_desc *desc, kdb_index **out) {
         const char *e = getenv("KDB_SLOTS");
         int ns = e ? atoi(e) : 4; // (four: the hardware queues a process has unless GPU_MAX_HW_QUEUES says otherwise; measured 4 vs 8: DESIGN 5.7)
         idx->n_slots = ns < 1 ? 1 : ns > KDB_MAX_SLOTS ? KDB_MAX_SLOTS : ns;
+        const char *cm = getenv("KDB_COMBINE_MIXED"); // 0: callers combine with callers of their own (k, ef) only
+        idx->combine_mixed = !(cm && atoi(cm) == 0);
         int prio_lo = 0, prio_hi = 0;
         (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
         for (int i = 0; i < idx->n_slots; i++) KDB_TRY(hipStreamCreateWithPriority(&idx->slots[i].stream, hipStreamNonBlocking, prio_hi));
@@ -1009,15 +1011,18 @@ static int prepare_queries(kdb_index *idx, const KdbView &v, const float *d_quer
     return kdb_launch_prep_queries(v, d_queries, B, *d_q, *d_qnorm, (flags & KDB_SEARCH_PREPARED) ? 0 : 1, s);
 }
 
-static uint32_t effective_ef(uint32_t ef, uint32_t flags) {
-    if (flags & KDB_SEARCH_NEEDS_REFINE) { // hnsw_index.go:387-399
-        uint32_t boosted = 2 * ef;
-        if (boosted < 80) boosted = 80;
-        if (boosted > 200) boosted = 200;
-        if (boosted > ef) ef = boosted;
-    }
-    return ef;
+static uint32_t effective_ef(uint32_t ef, uint32_t flags) { // (max(ef, k) is the launchers': they know k)
+    return kdb_mixed_effective_ef(ef, 0u, (flags & KDB_SEARCH_NEEDS_REFINE) != 0u); // hnsw_index.go:387-399
 }
+
+struct MixedKeys { // a mixed launch (kdb_search_batch_mixed[_dev]): k and ef of every query on the device, the launch's capacity
+    const uint32_t *d_k = nullptr, *d_ef = nullptr;
+    uint32_t ef_cap = 0;
+};
+
+struct HostKeys { // a mixed host-pointer call: the caller's k [B] and ef [B], staged beside the queries
+    const uint32_t *k, *ef;
+};
 
 struct KdbDone { // completion words of a combined launch (KdbMultiAllow::done_flags) and, for an open launch, its session word
     uint32_t *flags;
@@ -1034,7 +1039,8 @@ struct MultiLists { // heterogeneous batch (kdb_search_batch_multi_dev): G lists
 
 static int search_dev_locked(kdb_index *idx, const float *d_queries, uint32_t B, uint32_t k, uint32_t ef,
                              const uint64_t *d_allow_bits, uint32_t flags, uint32_t *d_out_ids, float *d_out_dist,
-                             uint32_t *d_out_count, hipStream_t s, const MultiLists *ml = nullptr, const KdbDone *done = nullptr) {
+                             uint32_t *d_out_count, hipStream_t s, const MultiLists *ml = nullptr, const KdbDone *done = nullptr,
+                             const MixedKeys *mx = nullptr /* set: k is the stride of the output rows, ef is not read */) {
     KdbView v = kdb_make_view(idx);
     if (B == 0) return KDB_OK;
     if (k == 0) {
@@ -1105,6 +1111,13 @@ static int search_dev_locked(kdb_index *idx, const float *d_queries, uint32_t B,
     }
     if (flags & KDB_SEARCH_TIE_FLAG) raw |= 8u;    // bit 31 of out_count: the walk met equal distances
     if (flags & KDB_SEARCH_HEAP_ORDER) raw |= 16u; // ... and such queries are re-walked in the reference's heap order
+    uint32_t ef_launch = effective_ef(ef, flags);
+    if (mx) { // every query's own k and ef: the kernels apply the boost and max(ef, k) per query (bit 6 of raw: the boost)
+        ma.k_of_query = mx->d_k;
+        ma.ef_of_query = mx->d_ef;
+        ef_launch = mx->ef_cap;
+        if (flags & KDB_SEARCH_NEEDS_REFINE) raw |= 64u;
+    }
     uint32_t *tr_nd = nullptr, *tr_nh = nullptr;
     if (idx->trace_ndist && idx->trace_on_device) {
         tr_nd = idx->trace_ndist;
@@ -1115,7 +1128,7 @@ static int search_dev_locked(kdb_index *idx, const float *d_queries, uint32_t B,
         tr_nd = reinterpret_cast<uint32_t *>(idx->d_scratch);
         tr_nh = tr_nd + B;
     }
-    rc = kdb_launch_search(idx, v, d_q, d_qnorm, raw, B, k, effective_ef(ef, flags), d_allow, ma, entry, d_out_ids, d_out_dist,
+    rc = kdb_launch_search(idx, v, d_q, d_qnorm, raw, B, k, ef_launch, d_allow, ma, entry, d_out_ids, d_out_dist,
                            d_out_count, tr_nd, tr_nh, s);
     if (rc) return rc;
     if (idx->trace_ndist && !idx->trace_on_device) {
@@ -1165,7 +1178,8 @@ extern "C" int kdb_search_batch_dev(kdb_index *idx, const float *d_queries, uint
 // slot and to enqueue; staging copies, the wait for the answers and the copy back happen outside it.
 //   * a call that finds a free slot goes out at once, alone (a lone caller never waits for company);
 //   * a search of up to KDB_COMBINE_MAX_B queries without an allow list that finds every slot busy joins -- or founds -- the group
-//     that waits for the next free slot: same (k, ef, flags) = ONE launch.  The thread that frees a slot launches the group
+//     that waits for the next free slot: same flags = ONE launch, whatever k and ef are (the launch reads them per query:
+//     kdb_mixed_plan.h; KDB_COMBINE_MIXED=0: same (k, ef) only).  The thread that frees a slot launches the group
 //     (nobody is woken for it); the kernel reads the queries from the slot's page-locked buffer, writes the answers there and
 //     publishes a completion word per query; every member watches its own words and leaves when ITS walk is done;
 //   * writers wait until no such call is in flight and hold new ones back meanwhile (KdbWriteLock);
@@ -1173,15 +1187,21 @@ extern "C" int kdb_search_batch_dev(kdb_index *idx, const float *d_queries, uint
 //     decode, consensus, belief -- takes a turn on the index's own staging buffer: HostTurn, below, is that protocol.
 // ---------------------------------------------------------------------------------------------
 struct StagedLayout { // one call's (or group's) buffers inside a slot: the same offsets on the device and in page-locked memory
-    size_t qbytes, aw, o_allow, o_ids, o_dist, o_cnt, out_span, total;
+    size_t qbytes, kbytes, aw, o_keys, o_allow, o_ids, o_dist, o_cnt, out_span, total;
+    size_t in_span() const { return aw ? o_allow + aw : kbytes ? o_keys + kbytes : qbytes; } // queries | keys | allow list: one copy
 };
-static StagedLayout staged_layout(const kdb_index *idx, uint32_t B, uint32_t k, bool allow, size_t dist_bytes) {
+// (KdbCarver's order: queries | k [B], ef [B] of a mixed call | allow list | ids | distances | counts; an absent region takes nothing)
+static StagedLayout staged_layout(const kdb_index *idx, uint32_t B, uint32_t k, bool allow, size_t dist_bytes, bool mixed = false) {
     auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
     StagedLayout L;
     L.qbytes = (size_t)B * idx->desc.dim * 4;
+    L.kbytes = mixed ? (size_t)B * 8 : 0;
     L.aw = allow ? kdb_bits_bytes(idx->count) : 0;
-    L.o_allow = al(L.qbytes);
-    L.o_ids = L.o_allow + al(L.aw);
+    KdbCarver cv;
+    (void)cv.take(L.qbytes);
+    L.o_keys = cv.take(L.kbytes);
+    L.o_allow = cv.take(L.aw);
+    L.o_ids = cv.take(0);
     L.o_dist = L.o_ids + (((size_t)B * k * 4 + 7) & ~(size_t)7); // 8-byte aligned: may hold doubles
     L.o_cnt = L.o_dist + (size_t)B * k * dist_bytes;
     L.out_span = L.o_cnt + (size_t)B * 4 - L.o_ids;
@@ -1222,8 +1242,8 @@ static size_t host_pin_max() { // calls whose buffers exceed this go through the
 }
 
 // an upper bound of what a call needs in a slot (the allow list is sized by the count the caller saw: at most the capacity's)
-static bool fits_a_slot(const kdb_index *idx, uint32_t B, uint32_t k, bool allow, size_t dist_bytes) {
-    return (size_t)B * idx->desc.dim * 4 + (allow ? kdb_bits_bytes(idx->cap) : 0) + (size_t)B * k * (4 + dist_bytes) + (size_t)B * 4 + 4096 <= host_pin_max();
+static bool fits_a_slot(const kdb_index *idx, uint32_t B, uint32_t k, bool allow, size_t dist_bytes, bool mixed = false) {
+    return (size_t)B * idx->desc.dim * 4 + (mixed ? (size_t)B * 8 + 256 : 0) + (allow ? kdb_bits_bytes(idx->cap) : 0) + (size_t)B * k * (4 + dist_bytes) + (size_t)B * 4 + 4096 <= host_pin_max();
 }
 
 static uint64_t now_ns() {
@@ -1248,6 +1268,8 @@ static kdb_group *group_get(kdb_index *idx) { // under mu
             g.members.clear();
             g.open = false;
             g.cap_q = 0;
+            g.mixed = false;
+            g.h_kq = g.h_efq = nullptr;
             return &g;
         }
     return nullptr;
@@ -1298,20 +1320,43 @@ static void launch_search_group(kdb_index *idx, std::unique_lock<std::mutex> &lk
     idx->n_group_members += g->members.size();
     if (nq > idx->largest_group) idx->largest_group = nq;
     // an open launch has room for KDB_GROUP_CAP queries (int8 indexes quantise their queries in a kernel of its own: closed launches)
-    const bool session = session_us() != 0u && idx->desc.precision != KDB_PREC_I8 && !idx->writers_waiting && nq < KDB_GROUP_CAP;
+    bool session = session_us() != 0u && idx->desc.precision != KDB_PREC_I8 && !idx->writers_waiting && nq < KDB_GROUP_CAP;
+    MixedKeys mx;
+    if (g->mixed) { // the launch's bounds are fixed HERE (kdb_mixed_plan.h): capacity from the largest effective ef, stride from the largest k
+        mx.ef_cap = kdb_mixed_ef_cap(g->eff_max);
+        uint32_t stride = session ? kdb_mixed_open_stride(g->k_max, mx.ef_cap, idx->desc.dim, (uint32_t)g->dist_bytes, host_pin_max()) : 0u;
+        if (stride == 0u) { // (no room for KDB_GROUP_CAP rows of the founders' own k: a closed launch of exactly them)
+            session = false;
+            stride = g->k_max;
+        }
+        g->k = stride;
+        g->ef = mx.ef_cap;
+        idx->n_mixed_launches++;
+        idx->n_mixed_calls += g->members.size();
+    }
     g->cap_q = session ? KDB_GROUP_CAP : nq;
-    const StagedLayout L = staged_layout(idx, g->cap_q, g->k, false, g->dist_bytes);
+    const StagedLayout L = staged_layout(idx, g->cap_q, g->k, false, g->dist_bytes, g->mixed);
     int rc = slot_ensure(idx, sl, L.total);
     if (rc == KDB_OK) {
         unsigned char *const h = reinterpret_cast<unsigned char *>(sl.h_pin);
         const size_t dim = idx->desc.dim;
         lk.unlock(); // (inflight > 0 keeps writers out; the group is sealed: its member list is final)
         size_t o = 0;
+        uint32_t *const kq = reinterpret_cast<uint32_t *>(h + L.o_keys), *const efq = kq + g->cap_q;
+        uint32_t b = 0;
         for (const kdb_group::Member &m : g->members) {
             memcpy(h + o, m.q, (size_t)m.B * dim * 4);
             o += (size_t)m.B * dim * 4;
+            if (g->mixed)
+                for (uint32_t i = 0; i < m.B; i++, b++) kq[b] = m.k, efq[b] = m.ef;
         }
         lk.lock();
+        if (g->mixed) {
+            g->h_kq = kq;
+            g->h_efq = efq;
+            mx.d_k = kq;
+            mx.d_ef = efq;
+        }
         g->h_ids = h + L.o_ids;
         g->h_dist = h + L.o_dist;
         g->h_cnt = h + L.o_cnt;
@@ -1336,7 +1381,7 @@ static void launch_search_group(kdb_index *idx, std::unique_lock<std::mutex> &lk
         if (rc == KDB_OK)
             rc = search_dev_locked(idx, reinterpret_cast<float *>(h), done.sess_ctl ? g->cap_q : nq, g->k, g->ef, nullptr, g->flags,
                                    reinterpret_cast<uint32_t *>(h + L.o_ids), reinterpret_cast<float *>(h + L.o_dist), reinterpret_cast<uint32_t *>(h + L.o_cnt),
-                                   sl.stream, nullptr, &done);
+                                   sl.stream, nullptr, &done, g->mixed ? &mx : nullptr);
         if (rc && idx->open_session == g) kdb_close_session(idx);
     }
     if (rc) group_fail(g, rc);
@@ -1445,6 +1490,11 @@ static int watch_done_words(kdb_index *idx, kdb_group *g, uint32_t off, uint32_t
 static int combined_search_call(kdb_index *idx, const float *queries, uint32_t B, uint32_t k, uint32_t ef, uint32_t flags, uint32_t *out_ids,
                                 void *out_dist, uint32_t *out_count) {
     const size_t dist_bytes = (flags & KDB_SEARCH_DIST_F64) ? 8 : 4;
+    // callers combine across (k, ef) by the rules of kdb_mixed_plan.h: the forming group takes any key with equal flags and bytes per
+    // distance, a running open launch whatever its stride and capacity admit.  (KDB_COMBINE_MIXED=0, or an ef beyond
+    // KDB_MIXED_COMBINE_EF_MAX: with callers of the same key only.)
+    const uint32_t eff = kdb_mixed_effective_ef(ef, k, (flags & KDB_SEARCH_NEEDS_REFINE) != 0u);
+    const bool may_mix = idx->combine_mixed && eff <= KDB_MIXED_COMBINE_EF_MAX;
     std::unique_lock<std::mutex> lk(idx->mu);
     if (idx->writers_waiting) idx->slot_cv.wait(lk, [&] { return idx->writers_waiting == 0; });
     kdb_group *g = nullptr;
@@ -1452,10 +1502,18 @@ static int combined_search_call(kdb_index *idx, const float *queries, uint32_t B
     if (kdb_group *os = idx->open_session) { // a launch that still accepts queries: write mine into its buffer, publish the count
         if (now_ns() - os->t_launch_ns.load(std::memory_order_relaxed) > (uint64_t)session_us() * 1000ull || idx->writers_waiting) {
             kdb_close_session(idx);
-        } else if (os->k == k && os->ef == ef && os->flags == flags && os->nq + B <= os->cap_q && !os->failed.load(std::memory_order_relaxed)) {
+        } else if (os->flags == flags && os->dist_bytes == dist_bytes && os->nq + B <= os->cap_q && !os->failed.load(std::memory_order_relaxed) &&
+                   !(os->mixed ? may_mix && kdb_mixed_admit(k, eff, flags, (uint32_t)dist_bytes, os->k, os->ef, os->flags, (uint32_t)os->dist_bytes)
+                               : os->k == k && os->eff == eff)) {
+            idx->n_mixed_refused++; // (its k or ef alone keeps this caller out of the running launch)
+        } else if (os->flags == flags && os->dist_bytes == dist_bytes && os->nq + B <= os->cap_q && !os->failed.load(std::memory_order_relaxed)) {
             g = os;
             off = g->nq;
             memcpy(reinterpret_cast<unsigned char *>(idx->slots[g->slot].h_pin) + (size_t)off * idx->desc.dim * 4, queries, (size_t)B * idx->desc.dim * 4);
+            if (g->mixed) { // my entries of the per-query arrays, BEFORE the new count is published below
+                for (uint32_t i = 0; i < B; i++) g->h_kq[off + i] = k, g->h_efq[off + i] = ef;
+                idx->n_mixed_calls++;
+            }
             g->nq += B;
             g->refs++;
             idx->n_group_members++;
@@ -1465,20 +1523,25 @@ static int combined_search_call(kdb_index *idx, const float *queries, uint32_t B
     }
     if (g) {
         // (joined an open launch)
-    } else if ((g = idx->forming) && g->k == k && g->ef == ef && g->flags == flags && g->nq + B <= KDB_GROUP_CAP) { // join the group that waits for a slot
+    } else if ((g = idx->forming) && g->flags == flags && g->dist_bytes == dist_bytes && g->nq + B <= KDB_GROUP_CAP &&
+               ((g->k == k && g->eff == eff && !g->mixed) || (may_mix && g->eff_max <= KDB_MIXED_COMBINE_EF_MAX))) { // join the group that waits for a slot
         off = g->nq;
         g->nq += B;
         g->refs++;
-        g->members.push_back({queries, B});
+        g->members.push_back({queries, B, k, ef});
+        if (g->k != k || g->eff != eff) g->mixed = true; // (its stride and capacity are fixed when it is launched)
+        if (k > g->k_max) g->k_max = k;
+        if (eff > g->eff_max) g->eff_max = eff;
     } else {
         while (!(g = group_get(idx))) idx->slot_cv.wait(lk); // (more founders than group objects: wait for one to come back)
-        g->k = k;
+        g->k = g->k_max = k;
         g->ef = ef;
+        g->eff = g->eff_max = eff;
         g->flags = flags;
         g->dist_bytes = dist_bytes;
         g->nq = B;
         g->refs = 1;
-        g->members.push_back({queries, B});
+        g->members.push_back({queries, B, k, ef});
         int si = idx->writers_waiting ? -1 : slot_find_free(idx);
         if (si >= 0) {
             launch_search_group(idx, lk, g, si); // a free slot: out at once, alone
@@ -1495,8 +1558,16 @@ static int combined_search_call(kdb_index *idx, const float *queries, uint32_t B
     int rc = watch_done_words(idx, g, off, B);
     if (rc == KDB_OK) {
         while (!g->launched.load(std::memory_order_acquire)) sched_yield(); // (set before the launch: orders the reads below behind the launcher's writes)
-        memcpy(out_ids, g->h_ids + (size_t)off * k * 4, (size_t)B * k * 4);
-        memcpy(out_dist, g->h_dist + (size_t)off * k * dist_bytes, (size_t)B * k * dist_bytes);
+        const size_t stride = g->k; // (the caller's own k unless the launch is mixed: then row by row, the first k of every row)
+        if (stride == k) {
+            memcpy(out_ids, g->h_ids + (size_t)off * k * 4, (size_t)B * k * 4);
+            memcpy(out_dist, g->h_dist + (size_t)off * k * dist_bytes, (size_t)B * k * dist_bytes);
+        } else {
+            for (uint32_t i = 0; i < B; i++) {
+                memcpy(out_ids + (size_t)i * k, g->h_ids + ((size_t)off + i) * stride * 4, (size_t)k * 4);
+                memcpy(reinterpret_cast<unsigned char *>(out_dist) + (size_t)i * k * dist_bytes, g->h_dist + ((size_t)off + i) * stride * dist_bytes, (size_t)k * dist_bytes);
+            }
+        }
         memcpy(out_count, g->h_cnt + (size_t)off * 4, (size_t)B * 4);
     }
     lk.lock();
@@ -1527,7 +1598,7 @@ static int combined_search_call(kdb_index *idx, const float *queries, uint32_t B
 // the kernel makes them visible).
 template <typename F>
 static int staged_slot_call(kdb_index *idx, const float *queries, uint32_t B, uint32_t k, const uint64_t *allow_bits, uint32_t *out_ids, void *out_dist,
-                            uint32_t *out_count, size_t dist_bytes, bool direct_out, F run) {
+                            uint32_t *out_count, size_t dist_bytes, bool direct_out, F run, const HostKeys *hk = nullptr) {
     constexpr size_t direct_max = (size_t)64 << 10;
     std::unique_lock<std::mutex> lk(idx->mu);
     close_expired_session(idx);
@@ -1540,13 +1611,17 @@ static int staged_slot_call(kdb_index *idx, const float *queries, uint32_t B, ui
     idx->inflight++;
     idx->n_groups++;
     idx->n_group_members++;
-    const StagedLayout L = staged_layout(idx, B, k, allow_bits != nullptr, dist_bytes);
+    const StagedLayout L = staged_layout(idx, B, k, allow_bits != nullptr, dist_bytes, hk != nullptr);
     int rc = slot_ensure(idx, sl, L.total);
     unsigned char *const h = reinterpret_cast<unsigned char *>(sl.h_pin), *const d = reinterpret_cast<unsigned char *>(sl.d_io);
     bool queued = false;
     if (rc == KDB_OK) {
         lk.unlock(); // stage in outside the lock (inflight > 0 keeps writers out: count and capacity cannot move)
         memcpy(h, queries, L.qbytes);
+        if (hk) {
+            memcpy(h + L.o_keys, hk->k, (size_t)B * 4);
+            memcpy(h + L.o_keys + (size_t)B * 4, hk->ef, (size_t)B * 4);
+        }
         if (allow_bits) memcpy(h + L.o_allow, allow_bits, L.aw);
         lk.lock();
         const bool direct = direct_out && L.out_span <= direct_max;
@@ -1555,7 +1630,7 @@ static int staged_slot_call(kdb_index *idx, const float *queries, uint32_t B, ui
             KdbLaneGuard lane(idx, sl.stream);
             rc = lane.rc;
             // queries and allow list sit side by side on both sides: one copy
-            if (rc == KDB_OK && hipMemcpyAsync(d, h, allow_bits ? L.o_allow + L.aw : L.qbytes, hipMemcpyHostToDevice, sl.stream) != hipSuccess) {
+            if (rc == KDB_OK && hipMemcpyAsync(d, h, L.in_span(), hipMemcpyHostToDevice, sl.stream) != hipSuccess) {
                 kdb_set_error("staging copy to the device failed");
                 rc = KDB_ERR_HIP;
             }
@@ -1651,14 +1726,18 @@ struct DropWatch {
 // A search or an exact scan of queries on a turn: run(d_q, d_allow, d_ids, d_dist, d_cnt, stream, B) as for staged_slot_call.
 template <typename F>
 static int staged_big_call(kdb_index *idx, const float *queries, uint32_t B, uint32_t k, const uint64_t *allow_bits, uint32_t *out_ids, void *out_dist,
-                           uint32_t *out_count, size_t dist_bytes, bool fail_on_drop, F run) {
+                           uint32_t *out_count, size_t dist_bytes, bool fail_on_drop, F run, const HostKeys *hk = nullptr) {
     HostTurn turn(idx);
-    const StagedLayout L = staged_layout(idx, B, k, allow_bits != nullptr, dist_bytes);
+    const StagedLayout L = staged_layout(idx, B, k, allow_bits != nullptr, dist_bytes, hk != nullptr);
     unsigned char *const d = turn.stage(L.total);
     if (!d) return turn.rc;
     hipStream_t s = idx->stream;
     turn.lk.unlock();
     KDB_HIP(hipMemcpyAsync(d, queries, L.qbytes, hipMemcpyHostToDevice, s));
+    if (hk) {
+        KDB_HIP(hipMemcpyAsync(d + L.o_keys, hk->k, (size_t)B * 4, hipMemcpyHostToDevice, s));
+        KDB_HIP(hipMemcpyAsync(d + L.o_keys + (size_t)B * 4, hk->ef, (size_t)B * 4, hipMemcpyHostToDevice, s));
+    }
     if (allow_bits) KDB_HIP(hipMemcpyAsync(d + L.o_allow, allow_bits, L.aw, hipMemcpyHostToDevice, s));
     turn.lk.lock();
     DropWatch drops;
@@ -1803,6 +1882,102 @@ extern "C" int kdb_search_batch(kdb_index *idx, const float *queries, uint32_t B
     static const uint32_t combine_max_b = [] { const char *e = getenv("KDB_COMBINE_MAX_B"); return e ? (uint32_t)atoi(e) : 16u; }();
     if (!allow_bits && B <= combine_max_b && B <= KDB_GROUP_CAP) return combined_search_call(idx, queries, B, k, ef, flags, out_ids, out_dist, out_count);
     return staged_slot_call(idx, queries, B, k, allow_bits, out_ids, out_dist, out_count, dist_bytes, true, run);
+}
+
+// ---- mixed batches: every query its own k and efSearch, one launch (kdb_mixed_plan.h) ---------------------------------------
+// Host pointers.  Validated here, before anything is staged; the launch's capacity comes from the arrays; k and ef travel beside the
+// queries (StagedLayout::o_keys).  Routes: a slot, or a turn on the index's staging buffer when the call is traced, asks for
+// KDB_SEARCH_FAIL_ON_DROP or does not fit a slot -- ONE launch either way: a large batch is not cut into chunks (chunks of a
+// mixed batch would each need the capacity of the whole), and a small one does not join other callers' launches.
+extern "C" int kdb_search_batch_mixed(kdb_index *idx, const float *queries, uint32_t B, const uint32_t *k, const uint32_t *ef, uint32_t k_stride,
+                                      const uint64_t *allow_bits, uint32_t flags, uint32_t *out_ids, float *out_dist, uint32_t *out_count) {
+    KDB_CHECK_IDX(idx);
+    if (B == 0) return KDB_OK;
+    if (!queries || !k || !ef || !out_ids || !out_dist || !out_count || k_stride == 0) {
+        kdb_set_error("search_mixed: null buffer or k_stride == 0");
+        return KDB_ERR_INVALID;
+    }
+    const bool refine = (flags & KDB_SEARCH_NEEDS_REFINE) != 0u;
+    uint32_t eff_max = 0;
+    bool distinct = false;
+    for (uint32_t b = 0; b < B; b++) {
+        if (!kdb_mixed_query_valid(k[b], 0u, k_stride, 0u)) {
+            kdb_set_error("search_mixed: k[%u] = %u is outside 1..k_stride (%u)", b, k[b], k_stride);
+            return KDB_ERR_INVALID;
+        }
+        const uint32_t e = kdb_mixed_effective_ef(ef[b], k[b], refine);
+        if (e > eff_max) eff_max = e;
+        if (k[b] != k[0] || e != kdb_mixed_effective_ef(ef[0], k[0], refine)) distinct = true;
+    }
+    MixedKeys mx;
+    mx.ef_cap = kdb_mixed_ef_cap(eff_max);
+    KDB_HIP(hipSetDevice(idx->device));
+    const size_t dist_bytes = (flags & KDB_SEARCH_DIST_F64) ? 8 : 4;
+    const HostKeys hk{k, ef};
+    auto run = [&](float *d_q, uint64_t *d_allow, uint32_t *d_ids, float *d_dist, uint32_t *d_cnt, hipStream_t s, uint32_t nq) {
+        const StagedLayout L = staged_layout(idx, nq, k_stride, d_allow != nullptr, dist_bytes, true);
+        MixedKeys m = mx;
+        m.d_k = reinterpret_cast<const uint32_t *>(reinterpret_cast<const unsigned char *>(d_q) + L.o_keys);
+        m.d_ef = m.d_k + nq;
+        const int rc = search_dev_locked(idx, d_q, nq, k_stride, 0u, d_allow, flags, d_ids, d_dist, d_cnt, s, nullptr, nullptr, &m);
+        if (rc == KDB_OK && distinct && idx->has_graph && idx->count) { // (under idx->mu, as every enqueue)
+            idx->n_mixed_launches++;
+            idx->n_mixed_calls++;
+        }
+        return rc;
+    };
+    const bool traced = idx->trace_ndist != nullptr; // (set by the caller's own thread before the call: kdb_search_set_trace)
+    if (traced || (flags & KDB_SEARCH_FAIL_ON_DROP) || !fits_a_slot(idx, B, k_stride, allow_bits != nullptr, dist_bytes, true))
+        return staged_big_call(idx, queries, B, k_stride, allow_bits, out_ids, out_dist, out_count, dist_bytes, (flags & KDB_SEARCH_FAIL_ON_DROP) != 0, run, &hk);
+    return staged_slot_call(idx, queries, B, k_stride, allow_bits, out_ids, out_dist, out_count, dist_bytes, true, run, &hk);
+}
+
+// Device pointers: the arrays cannot be read here, so the caller states the largest effective ef it sends; the kernels refuse the
+// queries that break the launch's bounds (KDB_MIXED_BAD_QUERY).  Per-query allow lists as kdb_search_batch_multi_dev has them.
+extern "C" int kdb_search_batch_mixed_dev(kdb_index *idx, const float *d_queries, uint32_t B, const uint32_t *d_k, const uint32_t *d_ef, uint32_t k_stride,
+                                          uint32_t ef_max, const uint64_t *d_allow_lists, uint32_t G, uint64_t words_per_list,
+                                          const uint32_t *d_allow_of_query, uint32_t flags, uint32_t *d_out_ids, float *d_out_dist, uint32_t *d_out_count,
+                                          void *stream) {
+    KDB_CHECK_IDX(idx);
+    if (B == 0) return KDB_OK;
+    if (!d_queries || !d_k || !d_ef || !d_out_ids || !d_out_dist || !d_out_count || k_stride == 0 || ef_max == 0) {
+        kdb_set_error("search_mixed: null buffer, k_stride == 0 or ef_max == 0");
+        return KDB_ERR_INVALID;
+    }
+    if (G != 0 && (!d_allow_lists || !d_allow_of_query)) {
+        kdb_set_error("search_mixed: G = %u lists without d_allow_lists / d_allow_of_query", G);
+        return KDB_ERR_INVALID;
+    }
+    DevCall call(idx, stream);
+    if (call.rc) return call.rc;
+    MixedKeys mx;
+    mx.d_k = d_k;
+    mx.d_ef = d_ef;
+    mx.ef_cap = kdb_mixed_ef_cap(ef_max);
+    if (G == 0) return search_dev_locked(idx, d_queries, B, k_stride, 0u, d_allow_lists, flags, d_out_ids, d_out_dist, d_out_count, call.s, nullptr, nullptr, &mx);
+    if (words_per_list < ((uint64_t)(idx->count >> 6) + 1)) {
+        kdb_set_error("search_mixed: words_per_list %llu < (count>>6)+1 = %llu", (unsigned long long)words_per_list,
+                      (unsigned long long)(idx->count >> 6) + 1);
+        return KDB_ERR_INVALID;
+    }
+    MultiLists ml;
+    ml.G = G;
+    ml.words64 = words_per_list;
+    ml.d_of_query = d_allow_of_query;
+    return search_dev_locked(idx, d_queries, B, k_stride, 0u, d_allow_lists, flags, d_out_ids, d_out_dist, d_out_count, call.s, &ml, nullptr, &mx);
+}
+
+// out[4]: [0] launches that carried at least two distinct (k, effective ef), [1] the calls they carried, [2] callers that could not
+// join an open launch because of their k or ef, [3] reserved
+extern "C" int kdb_index_mixed_stats(kdb_index *idx, uint64_t *out) {
+    KDB_CHECK_IDX(idx);
+    if (!out) return KDB_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(idx->mu);
+    out[0] = idx->n_mixed_launches;
+    out[1] = idx->n_mixed_calls;
+    out[2] = idx->n_mixed_refused;
+    out[3] = 0;
+    return KDB_OK;
 }
 
 // statistics of the concurrent host-pointer calls, out[10]: [0] launches that left through a slot, [1] calls they carried, [2] the largest

@@ -9,6 +9,7 @@
 #include <string>
 #include <vector>
 #include "../../include/kektor_hip.h"
+#include "kdb_mixed_plan.h"
 
 #define KDB_ID_MASK 0x3fffffffu
 #define KDB_F_EXPANDED 0x80000000u  // beam entry already expanded (popped)
@@ -63,6 +64,11 @@ struct KdbMultiAllow {
     const uint32_t *sess_ctl = nullptr;
     uint32_t sess_gen = 0;
     uint32_t sess_grid = 0;
+    // A MIXED launch (kdb_search_batch_mixed[_dev], kdb_mixed_plan.h): query b asks for k_of_query[b] results at efSearch
+    // ef_of_query[b].  The launch's scalar k is then the output STRIDE and its scalar ef the beam's CAPACITY (ef_cap); a query the
+    // two cannot hold is answered with count 0 | KDB_MIXED_BAD_QUERY, never walked.  Both null: every query takes the scalars.
+    const uint32_t *k_of_query = nullptr;
+    const uint32_t *ef_of_query = nullptr;
 };
 
 // Per-call scratch of the asynchronous entry points.  An index keeps KDB_LANES sets; a call takes the set last used on
@@ -82,6 +88,7 @@ struct KdbMultiAllow {
 #define KDB_LANES (2 + KDB_MAX_SLOTS)
 #define KDB_GROUP_POOL (KDB_MAX_SLOTS + 2)
 #define KDB_GROUP_CAP 256u  // queries one combined launch may carry (completion words per group)
+static_assert(KDB_GROUP_CAP == KDB_MIXED_GROUP_CAP, "kdb_mixed_plan.h sizes an open launch's buffer for KDB_GROUP_CAP queries");
 struct kdb_slot {
     hipStream_t stream = nullptr;
     void *d_io = nullptr;   // queries | allow list | ids | distances | counts (device side)
@@ -90,7 +97,13 @@ struct kdb_slot {
     bool busy = false;
 };
 struct kdb_group {
-    uint32_t k = 0, ef = 0, flags = 0;           // the key callers must share to join
+    // Forming (and a launch whose members all share one key): k, ef, flags are that key; eff = max(boosted ef, k).  A MIXED launch --
+    // its members differ in (k, eff), kdb_mixed_plan.h -- has k = the stride of its output rows and ef = its capacity, fixed when it
+    // is launched, and reads every query's own k and ef from h_kq / h_efq in the slot's page-locked buffer.
+    uint32_t k = 0, ef = 0, flags = 0;
+    uint32_t eff = 0, k_max = 0, eff_max = 0;    // (k_max / eff_max: over the members so far)
+    bool mixed = false;
+    uint32_t *h_kq = nullptr, *h_efq = nullptr;  // cap_q entries each (a late joiner writes its own before it publishes the new count)
     uint32_t nq = 0;                             // queries joined so far (final once the group is sealed)
     uint32_t refs = 0;                           // callers that have not taken their answers yet
     int slot = -1;
@@ -107,7 +120,7 @@ struct kdb_group {
     std::atomic<uint64_t> t_launch_ns{0};        // (written by the launcher under idx->mu; watchers read it outside the lock)
     struct Member {
         const float *q;
-        uint32_t B;
+        uint32_t B, k, ef;
     };
     std::vector<Member> members;                 // callers' query buffers (every member is blocked in its call until its words are set)
     const unsigned char *h_ids = nullptr, *h_dist = nullptr, *h_cnt = nullptr; // the answers, page-locked
@@ -228,6 +241,8 @@ struct kdb_index {
     std::atomic<uint32_t> walk_ns{150000};    // running estimate of join -> own answer, nanoseconds (first sleep of a watcher)
     std::mutex big_mu;             // calls too large for a slot share d_iobuf / stream / stream2: one at a time
     uint64_t n_groups = 0, n_group_members = 0, largest_group = 0; // statistics of the combiner (kdb_index_caller_stats)
+    uint64_t n_mixed_launches = 0, n_mixed_calls = 0, n_mixed_refused = 0; // kdb_index_mixed_stats
+    bool combine_mixed = true;     // KDB_COMBINE_MIXED (read at creation): concurrent callers combine across (k, ef); 0: exact-key joining
     std::atomic<uint64_t> ns_to_launch{0}, ns_launch_to_done{0}, ns_in_launch{0}, n_naps{0}, n_combined_calls{0}; // where a combined call's time goes
     // scratch lanes: the fields d_visited / d_scratch / d_qbuf / d_gentry / d_work above always name the CURRENT lane's
     // buffers (kdb_lane_acquire copies them in, kdb_lane_release copies them back: calls are serialised by `mu`)

@@ -1902,5 +1902,8 @@ __host__ __device__ constexpr int kdb_beam_slots(uint32_t ef) { // (constexpr: k
     return 0; // (six register slots, ef 257..384, lost to the LDS beam's one merge per hop: 1M x 768, k=100, 1024 queries, ef 384: 3.63 ms
               //  against 2.89 ms at ef 400 -- scripts/ef_probe.py, round 4; the slot count 6 is gone)
 }
+static_assert(kdb_beam_slots(64) == kdb_mixed_beam_class(64) && kdb_beam_slots(65) == kdb_mixed_beam_class(65) && kdb_beam_slots(128) == kdb_mixed_beam_class(128) &&
+                  kdb_beam_slots(129) == kdb_mixed_beam_class(129) && kdb_beam_slots(256) == kdb_mixed_beam_class(256) && kdb_beam_slots(257) == kdb_mixed_beam_class(257),
+              "kdb_mixed_plan.h sizes a mixed launch by kdb_beam_slots' classes");
 
 } // namespace kdbcore

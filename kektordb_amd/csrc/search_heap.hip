@@ -633,6 +633,13 @@ heap_walk_kernel(KdbView v, HeapArgs a) {
         }
         QCtr ctr{};
         bool failed = ep - 1u >= v.count, over = false; // (ep == 0: an empty list / no valid entry)
+        // a mixed launch: the tied query is walked with ITS k and effective ef (a.k: the stride of the output rows, a.ef: the capacity
+        // the heaps were sized for; the search kernel queues valid queries only)
+        uint32_t kq = a.k, efq = a.ef;
+        if (a.ma.k_of_query) {
+            kq = uni(a.ma.k_of_query[qi]);
+            efq = kdb_mixed_effective_ef(uni(a.ma.ef_of_query[qi]), kq, (a.raw & 64u) != 0u);
+        }
         for (int l = v.max_level; l > 0 && !failed && !over; l--) { // greedy descent, ef = 1 (:450-459)
             const uint32_t n = heap_layer<PREC, METRIC, NCH>(v, s, vis, cands, results, res_id, res_key, res_lo, q_allow, ep, l, 1u, qnorm, ctr);
             if (n == 0xffffffffu) over = true;
@@ -641,9 +648,9 @@ heap_walk_kernel(KdbView v, HeapArgs a) {
         }
         uint32_t nout = 0;
         if (!failed && !over) {
-            const uint32_t n = heap_layer<PREC, METRIC, NCH>(v, s, vis, cands, results, res_id, res_key, res_lo, q_allow, ep, 0, a.ef, qnorm, ctr);
+            const uint32_t n = heap_layer<PREC, METRIC, NCH>(v, s, vis, cands, results, res_id, res_key, res_lo, q_allow, ep, 0, efq, qnorm, ctr);
             if (n == 0xffffffffu) over = true;
-            else nout = n < a.k ? n : a.k;
+            else nout = n < kq ? n : kq;
         }
         if (over) { // the candidate heap outgrew its scratch: the fast walk's answer stays, the tie stays reported
             unresolved++;
@@ -737,7 +744,7 @@ int heap_dispatch(const KdbView &v, bool hash, bool reg, bool ov, F f) {
 // walk at once; the rest of the candidate heap (up to cap_c entries: 16 ef, at least 2048) in HBM scratch, per workgroup.  (Round 4
 // gave every wave 60 KB and 64 ef entries of tail whatever ef was: two waves per CU, 480 MB of tails per scratch lane.)
 int kdb_heap_walk_plan(kdb_index *idx, const KdbView &v, uint32_t ef, uint32_t k, uint32_t B, KdbHeapPlan *out) {
-    const uint32_t eff = ef < k ? k : ef;
+    const uint32_t eff = kdb_mixed_effective_ef(ef, k, false); // (a mixed launch: its capacity and its stride -- LDS and heaps hold every query of it)
     const bool wk = v.precision == KDB_PREC_I8;
     const size_t ew = wk ? 12 : 8;
     KdbHeapPlan p{};
@@ -779,7 +786,7 @@ int kdb_launch_heap_walk(kdb_index *idx, const KdbView &v, const void *d_q, cons
                          const uint32_t *d_allow, KdbMultiAllow ma, uint32_t entry, uint32_t *d_tie_list, unsigned char *d_tails, const KdbHeapPlan &plan,
                          unsigned long long *d_ctr, uint32_t *d_out_ids, float *d_out_dist, uint32_t *d_out_count,
                          uint32_t *d_tr_ndist, uint32_t *d_tr_nhops, hipStream_t s, uint32_t vis_first, unsigned char *d_stash, uint32_t mode) {
-    const uint32_t eff = ef < k ? k : ef;
+    const uint32_t eff = kdb_mixed_effective_ef(ef, k, false);
     HeapArgs a{};
     a.queries = d_q;
     a.qnorms = d_qnorm;

@@ -28,6 +28,19 @@ template <bool WK> struct BeamSel<0, WK> { using type = LdsBeamT<WK>; };
 template <int VIS> struct VisSel { using type = VisBitset; };
 template <> struct VisSel<1> { using type = VisHash; };
 
+// k and effective ef of query qi of a mixed launch, wave-uniform and scalar; valid: inside the launch's stride and capacity
+struct MixedKey {
+    uint32_t k, ef;
+    bool valid;
+};
+__device__ __forceinline__ MixedKey mixed_key(const KdbMultiAllow &ma, uint32_t qi, uint32_t raw, uint32_t stride, uint32_t ef_cap) {
+    MixedKey m;
+    m.k = uni(ma.k_of_query[qi]);
+    m.ef = kdb_mixed_effective_ef(uni(ma.ef_of_query[qi]), m.k, (raw & 64u) != 0u);
+    m.valid = kdb_mixed_query_valid(m.k, m.ef, stride, ef_cap);
+    return m;
+}
+
 template <int PREC>
 __device__ __forceinline__ size_t q_lds_bytes(uint32_t ld) {
     return PREC == KDB_PREC_I8 ? ((size_t)ld + 15) / 16 * 16 : (size_t)ld * 4;
@@ -193,6 +206,16 @@ hnsw_search_kernel(KdbView v, const void *__restrict__ queries, const float *__r
             }
         }
         bool failed = dead || ep - 1u >= v.count; // (ep == 0: an empty list / no valid entry)
+        // a mixed launch (kdb_mixed_plan.h): the query has its own k and effective ef; k is then the stride of the output rows and ef
+        // the launch's capacity.  A query the launch cannot hold is not walked.  (The two words are read again where they are used --
+        // two scalar loads per query -- rather than kept across the walk: registers held over the hop loop are what its kernels lack.)
+        uint32_t kq = k, efq = ef; // (kq == 0: a query outside the launch's bounds)
+        if (ma.k_of_query) {
+            const MixedKey mk = mixed_key(ma, uni(qi), raw, k, ef);
+            kq = mk.valid ? mk.k : 0u;
+            efq = mk.ef;
+            failed = failed || kq == 0u;
+        }
         EpKnown epk; // the next layer's entry point is this layer's nearest result: its distance is known
         if constexpr (WIDE > 1) { // what the helper waves need to know about this query
             if (lane == 0) {
@@ -221,12 +244,13 @@ hnsw_search_kernel(KdbView v, const void *__restrict__ queries, const float *__r
             }
         }
         uint32_t nout = 0;
-        if (!failed) layer(ep, 0, ef);
+        if (!failed) layer(ep, 0, uni(efq));
         // Equal distances met on the way (RegBeam::tied): raw & 8 -> reported in bit 31 of out_count; raw & 16 -> the query is
         // queued for the heap-order walk (heap_walk_kernel), which replaces its answer and supplies ITS counters.
         // raw & 32: that pass runs BESIDE this kernel (other stream, workgroups on other XCDs, each XCD with an L2 of its own): a
         // queued query's answer must not be written to the caller's arrays by BOTH kernels -- whichever L2 writes its lines back
         // last would win -- so this kernel puts it aside (the pass copies it back should its heaps outgrow their scratch)
+        const bool bad = kq == 0u;
         const bool requeue = b.tied && (raw & 16u) && tie_list != nullptr;
         const bool aside = requeue && (raw & 32u);
         const KdbTieStash st{tie_stash, B, k};
@@ -236,7 +260,7 @@ hnsw_search_kernel(KdbView v, const void *__restrict__ queries, const float *__r
         if (!failed) {
             // results, ascending (:2596-2610), first k
             // raw & 4 (int8 indexes): out_dist is a double array -- the reference's float64 distances, not their float rounding
-            nout = b.write_results(k, o_ids, o_dist, PREC == KDB_PREC_F32 && METRIC == KDB_METRIC_COSINE,
+            nout = b.write_results(kq, o_ids, o_dist, PREC == KDB_PREC_F32 && METRIC == KDB_METRIC_COSINE,
                                    (PREC == KDB_PREC_I8 && (raw & 4u)) ? o_dist64 : nullptr);
         }
         for (uint32_t p = nout + (uint32_t)lane; p < k; p += 64) {
@@ -251,7 +275,7 @@ hnsw_search_kernel(KdbView v, const void *__restrict__ queries, const float *__r
                 m[1] = ctr.n_dist;
                 m[2] = ctr.n_hops;
             } else {
-                out_count[qi] = nout | ((b.tied && (raw & 8u)) ? 0x80000000u : 0u);
+                out_count[qi] = nout | ((b.tied && (raw & 8u)) ? 0x80000000u : 0u) | (bad ? KDB_MIXED_BAD_QUERY : 0u);
                 if (tr_ndist) tr_ndist[qi] = ctr.n_dist;
                 if (tr_nhops) tr_nhops[qi] = ctr.n_hops;
                 if (requeue) tie_list[4u + atomicAdd(tie_list, 1u)] = qi;
@@ -333,7 +357,8 @@ static int launch_search_bs(kdb_index *idx, const KdbView &v, const void *d_q, c
                             uint32_t k, uint32_t ef, const uint32_t *d_allow, KdbMultiAllow ma, uint32_t entry, uint32_t *d_out_ids,
                             float *d_out_dist, uint32_t *d_out_count, uint32_t *d_tr_ndist, uint32_t *d_tr_nhops,
                             hipStream_t s) {
-    const uint32_t eff = ef < k ? k : ef; // ef = max(efSearch, k) (:2377-2380)
+    // ef = max(efSearch, k) (:2377-2380); a mixed launch: k is the stride and ef the capacity the caller worked out (ef_cap)
+    const uint32_t eff = ma.k_of_query ? ef : kdb_mixed_effective_ef(ef, k, false);
     const uint32_t beam_cap = ((eff + 2) + 63) / 64 * 64; // LDS beam (BS == 0)
     const uint32_t nr_cap = kdb_nr_cap(idx->n_deleted); // traversal-only candidates (NrList): the rule is kdb_walk_lds.h's, shared with the construction walks
     const size_t qb = PREC == KDB_PREC_I8 ? ((size_t)v.ld + 15) / 16 * 16 : (size_t)v.ld * 4;
@@ -585,7 +610,7 @@ static int launch_search_t(kdb_index *idx, const KdbView &v, const void *d_q, co
                            uint32_t k, uint32_t ef, const uint32_t *d_allow, KdbMultiAllow ma, uint32_t entry, uint32_t *d_out_ids,
                            float *d_out_dist, uint32_t *d_out_count, uint32_t *d_tr_ndist, uint32_t *d_tr_nhops,
                            hipStream_t s) {
-    const uint32_t eff = ef < k ? k : ef;
+    const uint32_t eff = ma.k_of_query ? ef : kdb_mixed_effective_ef(ef, k, false);
 #define KDB_A idx, v, d_q, d_qnorm, raw, B, k, ef, d_allow, ma, entry, d_out_ids, d_out_dist, d_out_count, d_tr_ndist, d_tr_nhops, s
     switch (kdb_beam_slots(eff)) { // beam in registers (1/2/4 slots of 64 entries) or in LDS
     case 1: return launch_search_bs<PREC, METRIC, NCH, 1>(KDB_A);

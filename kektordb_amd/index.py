@@ -29,6 +29,7 @@ BY_ID_DROP_SELF = 256    # KDB_BY_ID_DROP_SELF: a by-id answer without the sourc
 VACUUM_ELECT_TOP_LEVEL = 1  # KDB_VACUUM_ELECT_TOP_LEVEL
 COUNT_TIED = 0x80000000
 COUNT_MASK = 0x7fffffff
+MIXED_BAD_QUERY = 0x40000000  # KDB_MIXED_BAD_QUERY: a query of a mixed _dev batch outside the launch's bounds (count 0, never walked)
 CONSENSUS_MAX_K = 64  # KDB_CONSENSUS_MAX_K
 # kdb_consensus: CalculateConsensus's score, variance and maxVar, len(nodes), len(activeNodes)
 CONSENSUS_DTYPE = np.dtype([("score", "<f8"), ("variance", "<f8"), ("max_pair", "<f8"), ("n_found", "<u4"), ("n_active", "<u4")])
@@ -374,6 +375,66 @@ class HipIndex:
                                           | (SEARCH_TIE_FLAG if tie_flag else 0) | (SEARCH_HEAP_ORDER if heap_order else 0),
                                           _tptr(d_out_ids), _tptr(d_out_dist), _tptr(d_out_count),
                                           C.c_void_p(stream) if stream else None), "kdb_search_batch_dev")
+
+    def search_batch_mixed(self, queries, ks, efs, allow_bits=None, trace: bool = False, prepared=False, fail_on_drop: bool = False,
+                           dist64: bool = False, tie_flag: bool = False, heap_order: bool = False, k_stride: Optional[int] = None):
+        """B requests that differ in k and efSearch, one launch (kdb_search_batch_mixed): query b is answered as search_batch answers
+        it alone with (ks[b], efs[b]).  -> (ids [B,stride] u32, raw dist [B,stride], count [B] u32[, (n_dist[B], n_hops[B])]) with
+        stride = max(ks) unless k_stride says otherwise; positions [count, stride) of a row hold id 0 and +inf.  Keyword flags as for
+        search_batch."""
+        self._live()
+        q = np.ascontiguousarray(queries, dtype=np.float32)
+        assert q.ndim == 2 and q.shape[1] == self.dim
+        B = q.shape[0]
+        kk = np.ascontiguousarray(ks, dtype=np.uint32)
+        ee = np.ascontiguousarray(efs, dtype=np.uint32)
+        assert kk.shape == (B,) and ee.shape == (B,)
+        stride = int(k_stride) if k_stride is not None else (int(kk.max()) if B else 1)
+        ids = np.zeros((B, stride), dtype=np.uint32)
+        dist = np.full((B, stride), np.inf, dtype=np.float64 if dist64 else np.float32)
+        cnt = np.zeros(B, dtype=np.uint32)
+        ab = None if allow_bits is None else np.ascontiguousarray(allow_bits, dtype=np.uint64)
+        nd = nh = None
+        if trace:
+            nd = np.zeros(B, dtype=np.uint32)
+            nh = np.zeros(B, dtype=np.uint32)
+            check(self.L.kdb_search_set_trace(self.h, _ptr(nd), _ptr(nh), 0), "set_trace")
+        try:
+            check(self.L.kdb_search_batch_mixed(self.h, _ptr(q), B, _ptr(kk), _ptr(ee), stride, _ptr(ab),
+                                                self._flags(prepared) | (4 if fail_on_drop else 0) | (SEARCH_DIST_F64 if dist64 else 0)
+                                                | (SEARCH_TIE_FLAG if tie_flag else 0) | (SEARCH_HEAP_ORDER if heap_order else 0),
+                                                _ptr(ids), _ptr(dist), _ptr(cnt)), "kdb_search_batch_mixed")
+        finally:
+            if trace:
+                self.L.kdb_search_set_trace(self.h, None, None, 0)
+        if trace:
+            return ids, dist, cnt, (nd, nh)
+        return ids, dist, cnt
+
+    def search_batch_mixed_dev(self, d_queries, d_ks, d_efs, k_stride: int, ef_max: int, d_out_ids, d_out_dist, d_out_count, d_allow_lists=None,
+                               d_allow_of_query=None, stream=None, prepared=False, dist64=False, tie_flag=False, heap_order=False):
+        """torch device tensors in, asynchronous on `stream`: d_ks / d_efs [B] int32 (read as uint32), outputs [B, k_stride]; ef_max is
+        the largest effective ef the batch holds.  d_allow_of_query given: d_allow_lists is [G, words] and query b uses list
+        d_allow_of_query[b] (-1 = none), as search_batch_multi_dev; else d_allow_lists is one optional list for the whole batch.  A
+        query outside the launch's bounds comes back as count 0 | MIXED_BAD_QUERY."""
+        self._live()
+        _ready(stream)
+        B = int(d_queries.shape[0])
+        G = words = 0
+        if d_allow_of_query is not None:
+            G, words = int(d_allow_lists.shape[0]), int(d_allow_lists.shape[1])
+        check(self.L.kdb_search_batch_mixed_dev(self.h, _tptr(d_queries), B, _tptr(d_ks), _tptr(d_efs), k_stride, ef_max, _tptr(d_allow_lists), G, words,
+                                                _tptr(d_allow_of_query), self._flags(prepared) | (SEARCH_DIST_F64 if dist64 else 0)
+                                                | (SEARCH_TIE_FLAG if tie_flag else 0) | (SEARCH_HEAP_ORDER if heap_order else 0),
+                                                _tptr(d_out_ids), _tptr(d_out_dist), _tptr(d_out_count), C.c_void_p(stream) if stream else None),
+              "kdb_search_batch_mixed_dev")
+
+    def mixed_stats(self):
+        """kdb_index_mixed_stats: [launches that carried at least two distinct (k, effective ef), the calls they carried, callers that
+        could not join an open launch because of their k or ef, 0]"""
+        out = np.zeros(4, dtype=np.uint64)
+        check(self.L.kdb_index_mixed_stats(self.h, _ptr(out)), "kdb_index_mixed_stats")
+        return [int(x) for x in out]
 
     def flat_scan_batch(self, queries, k: int, allow_bits=None, dist64: bool = False):
         self._live()
