@@ -39,6 +39,15 @@
  *                           per-node similarity of Engine.VBeliefState (pkg/engine/epistemic.go:22-182, :81): centroid, distances to
  *                           it, pair distances and the score in ONE kernel, about 40 bytes per list back
  *   kdb_belief_batch        the search of VBeliefState (:45) and that consensus as one call: the k result rows never leave the device
+ *   kdb_index_set_column    the metadata indexes AddMetadataUnlocked fills (pkg/core/core.go:1640-1758: strings and bools in the inverted
+ *                           index, float64 in the B-tree) as per-id columns in HBM
+ *   kdb_filter_parse        the filter grammar of DB.FindIDsByFilter / evaluateBooleanFilter / findFilterOperator (core.go:44-48,
+ *                           :1766-1839, :1866-1897, :1900-2034), host only
+ *   kdb_filter_eval         FindIDsByFilter itself for P filters at once: predicate programs over the columns -> P dense allow lists
+ *                           and their cardinalities in one streaming kernel (`!=`: live minus matched, :1998-2029, without the walk over
+ *                           every node of GetAllValidNodeIDs, hnsw_index.go:2884-2900)
+ *   kdb_search_filtered     Engine.VSearch(index, query, k, filter, ...) from programs to answers (pkg/engine/ops.go:928-1007): lists,
+ *                           routing between walk and exact scan, answers, as one call
  *   kdb_merge_topk          the merge step of the id-range shard (no reference
  *                           counterpart -- the reference is single process)
  *   kdb_sharded_search_batch  the same path over every GPU of a node from ONE process: fan-out,
@@ -449,6 +458,117 @@ KDB_API int kdb_belief_batch(kdb_index *idx, const float *queries, uint32_t B, u
 KDB_API int kdb_belief_batch_dev(kdb_index *idx, const float *d_queries, uint32_t B, uint32_t k, uint32_t ef,
                                  const uint64_t *d_allow_bits, const uint64_t *d_active_bits, uint32_t flags, uint32_t *d_out_ids,
                                  float *d_out_dist, uint32_t *d_out_count, kdb_consensus *d_out, double *d_out_similarity, void *stream);
+
+/* ---- metadata filters on the device (filter.hip; geometry and validation in kdb_filter_plan.h) ---------------------------------
+ * The reference turns a filter string into a roaring bitmap on the host: DB.FindIDsByFilter (pkg/core/core.go:1766-1839) splits on
+ * OR, then AND, and evaluateBooleanFilter (:1900-2034) answers each comparison from the inverted index (strings, bools) or the
+ * B-tree (float64), both filled by AddMetadataUnlocked (:1640-1758); Engine.VSearch hands the bitmap to SearchWithScores as the
+ * allow list.  Here the metadata lives in HBM as COLUMNS indexed by internal id, a filter is a small PREDICATE PROGRAM, and one
+ * streaming kernel writes the allow lists -- in the layout every filtered entry point above takes -- and their cardinalities.
+ *
+ * COLUMNS.  A node has at most one value per key: a string / bool (inverted index) or a float64 (B-tree).  Up to KDB_MAX_COLUMNS
+ * slots per index, each capacity+1 entries:
+ *   KDB_COL_F64   8 bytes per id, the B-tree value; NaN = the node has no numeric value for the key.  JSON carries neither NaN nor
+ *                 +-inf: kdb_index_set_column refuses +-inf (KDB_ERR_INVALID, nothing written); kdb_index_set_column_dev cannot
+ *                 look: the caller keeps +-inf out (an infinity would compare like any other double);
+ *   KDB_COL_CODE  4 bytes per id, the caller's dictionary code of the string value (bools are "true" / "false"); 0 = no value.
+ * kdb_index_set_column writes values[0..n) to ids first_id .. first_id+n-1 (1 <= first_id, first_id+n-1 <= capacity; ids above
+ * count may be filled ahead of their rows).  The first upload of a slot allocates it filled with "absent"; later calls overwrite
+ * their range and must name the same kind; n = 1 is VSetMetadata.  A writer in the sense of "Conventions".  kdb_index_reserve moves
+ * live columns with the other arrays (absent tail; KDB_ERR_OOM leaves the index as it was), kdb_index_compress copies them device to
+ * device to the new index, kdb_index_destroy frees them.  An index that never uploads a column allocates nothing.
+ * kdb_index_column_info: *kind = 0 and *bytes = 0 for an empty slot.
+ *
+ * PROGRAMS.  A term compares one column with one constant:
+ *   KDB_FOP_F64_EQ / LT / LE / GT / GE   column value <op> term.value, IEEE double compare: an absent value (NaN) never matches,
+ *                                        -0.0 == 0.0 (Go's == and <, :1924, :1965-1989); a NaN term.value is refused;
+ *   KDB_FOP_CODE_EQ                      column code == term.code (term.code != 0);
+ *   KDB_FOP_NEVER                        false (a key nobody has a column for: `indexInv[key]` / `indexBTree[key]` missing).
+ * A CLAUSE is a maximal run of terms chained by KDB_FT_OR_NEXT (set on every term but the clause's last); its value is the OR of
+ * its terms, inverted when its FIRST term carries KDB_FT_NOT.  A BLOCK is a run of clauses ended by KDB_FT_END_BLOCK on its last
+ * term (a term with END_BLOCK must not carry OR_NEXT): the AND of its clauses.  A PROGRAM is the OR of its blocks, ANDed with LIVE:
+ * 1 <= id <= count and not deleted.  The last term of a program must carry END_BLOCK; 1..KDB_FILTER_MAX_TERMS terms per program,
+ * 1..KDB_FILTER_MAX_PROGRAMS programs per call; a term's column must be a live slot of the kind its op reads.
+ * The reference maps onto this as: `k = v` one clause of up to two alternatives -- F64_EQ if v parses as a number and k has a
+ * numeric column, CODE_EQ if k has a code column and the dictionary knows v (the "lenient union" of :1933-1944), NEVER if
+ * neither; `k != v` the same clause with NOT (live minus matched, :1998-2029); `<`, `<=`, `>`, `>=` one F64 term; AND within a block,
+ * OR between blocks (:1785-1836).  The AND with live is exact: VDelete removes a node's metadata (pkg/engine/ops.go:428), so no index
+ * of the reference names a deleted node, and `!=` starts from the non-deleted nodes (GetAllValidNodeIDs, hnsw_index.go:2884-2900).
+ *
+ * kdb_filter_eval_dev: `terms` and `prog_offsets` (P+1 entries, program p = terms[prog_offsets[p] .. prog_offsets[p+1])) are HOST
+ * arrays, staged by the library like group_offsets of kdb_flat_scan_groups_dev.  d_lists receives P lists back to back,
+ * words_per_list >= (count>>6)+1 uint64 words each; EVERY word is written: bit 0 clear, bits above count clear, padding words zero.
+ * d_card: NULL or P uint32, the cardinality of each list (zeroed by the call, then one vector atomic add per (tile, program)).
+ * Asynchronous on `stream`, per-stream scratch as for the other _dev calls: a search queued behind it on the same stream needs no
+ * host synchronisation.  kdb_filter_eval is the host-output form (out_lists may be NULL when only out_card is wanted; not both).
+ * One lane per id; a wave's ballot is a list word; a wave covers KDB_FILTER_TILE_WORDS (16) consecutive words so each list receives
+ * contiguous runs of 128 bytes; the programs are taken KDB_FILTER_CHUNK (32) at a time and a column element is read once per (tile,
+ * chunk); a program's terms are fetched once per pass of up to 16 words, not once per word (kdb_filter_plan.h). */
+#define KDB_MAX_COLUMNS 16u
+enum { KDB_COL_F64 = 1, KDB_COL_CODE = 2 };
+enum { KDB_FOP_NEVER = 0, KDB_FOP_F64_EQ = 1, KDB_FOP_F64_LT = 2, KDB_FOP_F64_LE = 3, KDB_FOP_F64_GT = 4, KDB_FOP_F64_GE = 5, KDB_FOP_CODE_EQ = 6 };
+enum { KDB_FT_OR_NEXT = 1, KDB_FT_NOT = 2, KDB_FT_END_BLOCK = 4 };
+#define KDB_FILTER_MAX_TERMS 64u
+#define KDB_FILTER_MAX_PROGRAMS 4096u
+typedef struct { uint8_t op; uint8_t flags; uint16_t col; uint32_t code; double value; } kdb_filter_term; /* 16 bytes */
+KDB_API int kdb_index_set_column(kdb_index *idx, uint32_t col, uint32_t kind, uint32_t first_id, uint32_t n, const void *values);
+KDB_API int kdb_index_set_column_dev(kdb_index *idx, uint32_t col, uint32_t kind, uint32_t first_id, uint32_t n, const void *d_values);
+KDB_API int kdb_index_drop_column(kdb_index *idx, uint32_t col);
+KDB_API int kdb_index_column_info(kdb_index *idx, uint32_t col, uint32_t *kind, uint64_t *bytes);
+KDB_API int kdb_filter_eval_dev(kdb_index *idx, const kdb_filter_term *terms, const uint32_t *prog_offsets, uint32_t P,
+                                uint64_t *d_lists, uint64_t words_per_list, uint32_t *d_card, void *stream);
+KDB_API int kdb_filter_eval(kdb_index *idx, const kdb_filter_term *terms, const uint32_t *prog_offsets, uint32_t P,
+                            uint64_t *out_lists, uint64_t words_per_list, uint32_t *out_card);
+
+/* The filter STRING, host only (works without a GPU): the grammar of FindIDsByFilter restated, not improved.
+ *   - the filter is trimmed; empty: KDB_ERR_INVALID "empty filter" (:1777-1780);
+ *   - split on (?i)\s+OR\s+, each piece on (?i)\s+AND\s+ (core.go:44,48; leftmost matches, not quote-aware, as there); pieces are
+ *     trimmed, empty ones skipped, a block left without clauses is skipped (:1828-1833);
+ *   - the operator is the first of != <= >= = < > outside '...' / "..." (findFilterOperator, :1866-1897; compound ones first);
+ *     none: KDB_ERR_INVALID "invalid filter format";
+ *   - key = trimmed text before it; value = trimmed text after it, then stripped of every leading and trailing ' and " (:1908-1910);
+ *   - is_numeric / number: strtod over the WHOLE value in the C locale.  Known differences from Go's strconv.ParseFloat: Go accepts
+ *     underscores in hexadecimal mantissas and requires a p-exponent on them; both are refused / required here too by a syntax
+ *     check, so what remains is strtod's "nan(chars)" form (refused) -- report others as bugs.  A value out of double range is not
+ *     numeric, as ParseFloat's error makes it.  A range operator with a value that is not numeric: KDB_ERR_INVALID "value must be
+ *     numeric"; a NaN operand with ANY operator: KDB_ERR_INVALID (the reference's B-tree walk returns every item for `< NaN`; not
+ *     reproduced).  Whitespace is ASCII: \t \n \f \r and space split, those and \v trim.
+ * CONTAINS(...) never reaches this function: the engine strips it first (parseHybridFilter).
+ * Output: atoms in order; spans are byte offsets into `filter` as passed.  *n_atoms = the number of atoms the filter has; at most
+ * `cap` are written (atoms may be NULL when cap is 0: count first, then fill).  The mirrors turn atoms into terms with their own
+ * schema (key -> slots) and dictionary (kektordb_amd.index.compile_filter, kektor::hnsw::Index::CompileFilter). */
+enum { KDB_FA_EQ = 0, KDB_FA_NE = 1, KDB_FA_LT = 2, KDB_FA_LE = 3, KDB_FA_GT = 4, KDB_FA_GE = 5 };
+typedef struct {
+    uint32_t key_off, key_len;   /* span of the key inside `filter` */
+    uint32_t val_off, val_len;   /* span of the value, quotes stripped */
+    uint8_t op;                  /* KDB_FA_* */
+    uint8_t flags;               /* KDB_FT_END_BLOCK on the last atom of a block */
+    uint8_t is_numeric;          /* the value parses as a float64: `number` holds it */
+    uint8_t reserved[5];
+    double number;
+} kdb_filter_atom; /* 32 bytes */
+KDB_API int kdb_filter_parse(const char *filter, kdb_filter_atom *atoms, uint32_t cap, uint32_t *n_atoms);
+
+/* A filtered request as ONE call (host pointers; a composition like kdb_search_by_id): Engine.VSearch(index, query, k, filter)
+ * from programs to answers.  B queries; P programs as for kdb_filter_eval; prog_of_query[b] = the program of query b or
+ * KDB_NO_FILTER.  The call evaluates the programs, reads the P cardinalities back and routes PER PROGRAM by the rule of the
+ * micro-batcher's takes_flat_scan (include/kektor_hip.hpp), unchanged:
+ *   card == 0                                          route 2: out_count = 0, never scanned and never walked -- an empty list means
+ *                                                      "no filter" to the exact scan (vector_index.go:130) but "no results" to the
+ *                                                      engine (pkg/engine/ops.go:937-939);
+ *   k <= 1024 and card < flat_selectivity * count      route 1: the exact scan (kdb_flat_scan_groups_dev for float32 / float16 at
+ *                                                      k <= 128; one kdb_flat_scan_batch_dev per list for int8 and for k above 128,
+ *                                                      which the grouped scan does not serve);
+ *   otherwise, and KDB_NO_FILTER queries               route 0: kdb_search_batch_multi_dev.
+ * Per query the answer -- ids, distance bits, count -- is bit for bit what kdb_search_batch (route 0) or kdb_flat_scan_batch
+ * (route 1) returns for that query alone with that list; rows beyond the count hold what those calls leave there.
+ * out_route: NULL or [B]; out_card: NULL or [P].  flags: KDB_SEARCH_NEEDS_REFINE, KDB_SEARCH_TIE_FLAG, KDB_SEARCH_HEAP_ORDER
+ * (walk only).  flat_selectivity: 0 <= f <= 1 (0: nothing takes the scan).  Takes turns on the index's staging buffer like
+ * kdb_search_by_id and is never combined with other callers' queries. */
+KDB_API int kdb_search_filtered(kdb_index *idx, const float *queries, uint32_t B, uint32_t k, uint32_t ef,
+                                const kdb_filter_term *terms, const uint32_t *prog_offsets, uint32_t P, const uint32_t *prog_of_query,
+                                double flat_selectivity, uint32_t flags, uint32_t *out_ids, float *out_dist, uint32_t *out_count,
+                                uint8_t *out_route, uint32_t *out_card);
 
 /* B queries x C candidate ids each (ids[B][C], id 0 = skip -> +inf): raw accumulates out[B][C].   */
 KDB_API int kdb_distance_batch(kdb_index *idx, const float *queries, uint32_t B, const uint32_t *ids, uint32_t C,

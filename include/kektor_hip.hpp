@@ -398,6 +398,107 @@ class Index {
         r.ok = r.consensus.n_active > 0;
         return r;
     }
+    // ---- metadata filters on the device (kektor_hip.h, "metadata filters"; the reference: DB.FindIDsByFilter, core.go:1766-1839) ----
+    // One key of the mirror's schema: its numeric column (the reference's B-tree) and / or its code column with the dictionary of
+    // the strings seen so far (its inverted index; bools are "true" / "false"); -1 = the key has no such column
+    struct FilterKey {
+        int f64Slot = -1, codeSlot = -1;
+        std::map<std::string, uint32_t> dict; // string value -> code >= 1
+    };
+    using FilterSchema = std::map<std::string, FilterKey>;
+    using FilterProgram = std::vector<kdb_filter_term>;
+    // values[i] belongs to id firstID + i: doubles (NaN = no value) for KDB_COL_F64, uint32 codes (0 = no value) for KDB_COL_CODE
+    void SetColumn(uint32_t slot, uint32_t kind, uint32_t firstID, uint32_t n, const void *values) {
+        check(kdb_index_set_column(h_, slot, kind, firstID, n, values), "set_column");
+    }
+    void DropColumn(uint32_t slot) { check(kdb_index_drop_column(h_, slot), "drop_column"); }
+    // A filter string -> one predicate program.  `k = v`: F64_EQ if v is numeric and k has a numeric column, CODE_EQ if k has a code
+    // column and the dictionary knows v (the lenient union, core.go:1933-1944), NEVER if neither; `k != v`: the same clause with NOT;
+    // a range operator: one F64 term, NEVER without a numeric column.  Throws kektor::Error where the reference returns an error.
+    static FilterProgram CompileFilter(const std::string &filter, const FilterSchema &schema) {
+        uint32_t n = 0;
+        check(kdb_filter_parse(filter.c_str(), nullptr, 0, &n), "filter_parse");
+        std::vector<kdb_filter_atom> atoms(n ? n : 1);
+        check(kdb_filter_parse(filter.c_str(), atoms.data(), n, &n), "filter_parse");
+        FilterProgram prog;
+        auto term = [](uint8_t op, uint16_t col, uint32_t code, double value) {
+            kdb_filter_term t;
+            std::memset(&t, 0, sizeof t);
+            t.op = op, t.col = col, t.code = code, t.value = value;
+            return t;
+        };
+        for (uint32_t i = 0; i < n; i++) {
+            const kdb_filter_atom &a = atoms[i];
+            const auto it = schema.find(filter.substr(a.key_off, a.key_len));
+            const FilterKey *key = it == schema.end() ? nullptr : &it->second;
+            const size_t first = prog.size();
+            if (a.op == KDB_FA_EQ || a.op == KDB_FA_NE) {
+                if (key && a.is_numeric && key->f64Slot >= 0) prog.push_back(term(KDB_FOP_F64_EQ, (uint16_t)key->f64Slot, 0, a.number));
+                if (key && key->codeSlot >= 0) {
+                    const auto d = key->dict.find(filter.substr(a.val_off, a.val_len));
+                    if (d != key->dict.end() && d->second) prog.push_back(term(KDB_FOP_CODE_EQ, (uint16_t)key->codeSlot, d->second, 0.0));
+                }
+            } else if (key && key->f64Slot >= 0) {
+                const uint8_t op = a.op == KDB_FA_LT ? KDB_FOP_F64_LT : a.op == KDB_FA_LE ? KDB_FOP_F64_LE : a.op == KDB_FA_GT ? KDB_FOP_F64_GT : KDB_FOP_F64_GE;
+                prog.push_back(term(op, (uint16_t)key->f64Slot, 0, a.number));
+            }
+            if (prog.size() == first) prog.push_back(term(KDB_FOP_NEVER, 0, 0, 0.0));
+            for (size_t j = first; j + 1 < prog.size(); j++) prog[j].flags |= KDB_FT_OR_NEXT;
+            if (a.op == KDB_FA_NE) prog[first].flags |= KDB_FT_NOT;
+            if (a.flags & KDB_FT_END_BLOCK) prog.back().flags |= KDB_FT_END_BLOCK;
+        }
+        if (prog.empty()) { // every block was empty: the reference's empty bitmap
+            prog.push_back(term(KDB_FOP_NEVER, 0, 0, 0.0));
+            prog.back().flags = KDB_FT_END_BLOCK;
+        }
+        if (prog.size() > KDB_FILTER_MAX_TERMS) throw std::invalid_argument("CompileFilter: more than KDB_FILTER_MAX_TERMS terms");
+        return prog;
+    }
+    // FindIDsByFilter for several programs in one pass over the columns: lists[p] as an AllowList, cards[p] its cardinality
+    std::vector<AllowList> EvalFilters(const std::vector<FilterProgram> &programs, std::vector<uint32_t> *cards = nullptr) const {
+        std::vector<kdb_filter_term> terms;
+        std::vector<uint32_t> off;
+        pack(programs, terms, off);
+        const uint32_t P = (uint32_t)programs.size(), count = Count();
+        const uint64_t words = ((uint64_t)count >> 6) + 1;
+        std::vector<uint64_t> flat((size_t)P * words);
+        std::vector<uint32_t> card(P);
+        check(kdb_filter_eval(h_, terms.data(), off.data(), P, flat.data(), words, card.data()), "filter_eval");
+        std::vector<AllowList> out;
+        for (uint32_t p = 0; p < P; p++) {
+            out.emplace_back(count);
+            std::memcpy(out.back().words.data(), flat.data() + (size_t)p * words, (size_t)words * 8);
+        }
+        if (cards) *cards = card;
+        return out;
+    }
+    // Engine.VSearch with a filter per request, as ONE call (kdb_search_filtered): query b uses programs[progOfQuery[b]]
+    // (KDB_NO_FILTER: none).  results[b] is what SearchWithScores (the walk) or FlatScanBatch (a program that allows less than
+    // flatSelectivity of the ids, k <= 1024) returns for it; a program that matches nothing gives [].  Empty lists on any error.
+    std::vector<std::vector<SearchResult>> SearchFiltered(const float *queries, uint32_t B, int k, int efSearch, const std::vector<FilterProgram> &programs,
+                                                          const std::vector<uint32_t> &progOfQuery, double flatSelectivity = 0.1,
+                                                          std::vector<uint8_t> *routes = nullptr, std::vector<uint32_t> *cards = nullptr) const {
+        std::vector<std::vector<SearchResult>> out(B);
+        if (!h_ || k <= 0 || B == 0 || progOfQuery.size() != B || programs.empty()) return out;
+        std::vector<kdb_filter_term> terms;
+        std::vector<uint32_t> off;
+        pack(programs, terms, off);
+        std::vector<uint32_t> ids((size_t)B * k), cnt(B), card(programs.size());
+        std::vector<float> dist((size_t)B * k);
+        std::vector<uint8_t> route(B);
+        int rc = kdb_search_filtered(h_, queries, B, (uint32_t)k, (uint32_t)(efSearch > 0 ? efSearch : 0), terms.data(), off.data(), (uint32_t)programs.size(),
+                                     progOfQuery.data(), flatSelectivity, flags() & ~(uint32_t)KDB_SEARCH_DIST_F64, ids.data(), dist.data(), cnt.data(),
+                                     route.data(), card.data());
+        if (rc) return out;
+        for (uint32_t b = 0; b < B; b++)
+            for (uint32_t i = 0; i < (cnt[b] & KDB_COUNT_MASK); i++) {
+                const float d = dist[(size_t)b * k + i]; // (int8: the float64 distance rounded to float on the way out)
+                out[b].push_back({ids[(size_t)b * k + i], (metric_ == KDB_METRIC_COSINE && precision_ == KDB_PREC_F32) ? 1.0 - (double)d : (double)d});
+            }
+        if (routes) *routes = route;
+        if (cards) *cards = card;
+        return out;
+    }
     kdb_index *handle() const { return h_; }
     // concurrent kdb_search_batch calls of a few queries share launches inside the library (kektor_hip.h, "Conventions"): a
     // batcher in front of this index passes unfiltered one-query calls through
@@ -436,6 +537,14 @@ class Index {
     }
     static void check(int rc, const char *what) {
         if (rc) throw Error(rc, what);
+    }
+    static void pack(const std::vector<FilterProgram> &programs, std::vector<kdb_filter_term> &terms, std::vector<uint32_t> &off) {
+        off.assign(1, 0u);
+        for (const FilterProgram &p : programs) {
+            terms.insert(terms.end(), p.begin(), p.end());
+            off.push_back((uint32_t)terms.size());
+        }
+        if (terms.empty()) terms.resize(1); // (a pointer the library refuses by its own rules, not a null one)
     }
     kdb_index *h_ = nullptr;
     uint32_t dim_, metric_, precision_;

@@ -8,4 +8,5 @@ streams, torch.distributed), never the compute path.
 """
 from ._lib import KdbError, build_library, load, LIB_PATH, ABI_SYMBOLS  # noqa: F401
 from .index import HipIndex, SearchResult, L2, COSINE, F32, F16, I8  # noqa: F401
+from .index import compile_filter, parse_filter, pack_programs  # noqa: F401
 from .cluster import Cluster  # noqa: F401

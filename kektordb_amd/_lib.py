@@ -30,6 +30,8 @@ ABI_SYMBOLS = [
     "kdb_index_decode_rows", "kdb_index_decode_rows_dev", "kdb_search_by_id", "kdb_search_by_id_dev", "kdb_flat_scan_by_id", "kdb_flat_scan_by_id_dev",
     "kdb_consensus_batch", "kdb_consensus_batch_dev", "kdb_belief_batch", "kdb_belief_batch_dev",
     "kdb_search_batch_mixed", "kdb_search_batch_mixed_dev", "kdb_index_mixed_stats",
+    "kdb_index_set_column", "kdb_index_set_column_dev", "kdb_index_drop_column", "kdb_index_column_info",
+    "kdb_filter_eval", "kdb_filter_eval_dev", "kdb_filter_parse", "kdb_search_filtered",
 ]
 
 
@@ -57,6 +59,16 @@ class Counters(C.Structure):
 class Consensus(C.Structure):  # kdb_consensus, 32 bytes
     _fields_ = [("score", C.c_double), ("variance", C.c_double), ("max_pair", C.c_double), ("n_found", C.c_uint32),
                 ("n_active", C.c_uint32)]
+
+
+class FilterTerm(C.Structure):  # kdb_filter_term, 16 bytes
+    _fields_ = [("op", C.c_uint8), ("flags", C.c_uint8), ("col", C.c_uint16), ("code", C.c_uint32), ("value", C.c_double)]
+
+
+class FilterAtom(C.Structure):  # kdb_filter_atom, 32 bytes
+    _fields_ = [("key_off", C.c_uint32), ("key_len", C.c_uint32), ("val_off", C.c_uint32), ("val_len", C.c_uint32),
+                ("op", C.c_uint8), ("flags", C.c_uint8), ("is_numeric", C.c_uint8), ("reserved", C.c_uint8 * 5),
+                ("number", C.c_double)]
 
 
 class BuildParams(C.Structure):
@@ -197,6 +209,14 @@ def load():
     L.kdb_index_drop_walk_planes.argtypes = [vp, C.c_int]
     L.kdb_cluster_comm_info.argtypes = [vp, C.POINTER(u32), C.POINTER(u32)]
     L.kdb_cluster_debug_fail_next.argtypes = [vp, u32]
+    L.kdb_index_set_column.argtypes = [vp, u32, u32, u32, u32, vp]
+    L.kdb_index_set_column_dev.argtypes = [vp, u32, u32, u32, u32, vp]
+    L.kdb_index_drop_column.argtypes = [vp, u32]
+    L.kdb_index_column_info.argtypes = [vp, u32, C.POINTER(u32), C.POINTER(C.c_uint64)]
+    L.kdb_filter_eval.argtypes = [vp, vp, vp, u32, vp, C.c_uint64, vp]
+    L.kdb_filter_eval_dev.argtypes = [vp, vp, vp, u32, vp, C.c_uint64, vp, vp]
+    L.kdb_filter_parse.argtypes = [C.c_char_p, vp, u32, C.POINTER(u32)]
+    L.kdb_search_filtered.argtypes = [vp, vp, u32, u32, u32, vp, vp, u32, vp, C.c_double, u32, vp, vp, vp, vp, vp]
     _lib = L
     return L
 

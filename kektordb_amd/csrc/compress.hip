@@ -253,6 +253,15 @@ extern "C" int kdb_index_compress(kdb_index *src, uint32_t precision, uint32_t f
         KDB_TRYC(hipStreamSynchronize(s));
         dst->n_deleted = src->n_deleted;
     }
+    // ---- the metadata columns (filter.hip): the new index keeps ids and capacity, so every live slot is one device-to-device copy
+    for (uint32_t c = 0; c < KDB_MAX_COLUMNS; c++) {
+        if (!src->d_col[c]) continue;
+        const size_t cb = ((size_t)src->cap + 1) * (src->col_kind[c] == KDB_COL_F64 ? 8 : 4);
+        KDB_TRYC(hipMalloc(&dst->d_col[c], cb));
+        dst->col_kind[c] = src->col_kind[c];
+        KDB_TRYC(hipMemcpyAsync(dst->d_col[c], src->d_col[c], cb, hipMemcpyDeviceToDevice, s));
+    }
+    KDB_TRYC(hipStreamSynchronize(s));
 #undef KDB_TRYC
     *out = dst;
     return KDB_OK;

@@ -187,6 +187,9 @@ struct kdb_index {
     bool norms_valid = false;   // L2 row norms for the flat scan
     uint32_t n_deleted = 0;
     float absmax = 0.f;
+    // metadata columns (filter.hip): slot c holds (cap + 1) entries of col_kind[c] (0: the slot is empty, nothing allocated)
+    void *d_col[KDB_MAX_COLUMNS] = {};
+    uint32_t col_kind[KDB_MAX_COLUMNS] = {};
     // scratch
     uint32_t *d_visited = nullptr;  // slots * vis_words
     uint32_t vis_slots = 0;
@@ -405,6 +408,11 @@ int kdb_launch_by_id_finish(const uint32_t *d_src_ids, const uint8_t *d_found, u
 // consensus.hip: CalculateConsensus for B id lists, one workgroup per list (everything optional may be null)
 int kdb_launch_consensus(const KdbView &v, const uint32_t *d_ids, const uint32_t *d_counts, uint32_t B, uint32_t stride, const float *d_queries,
                          const uint32_t *d_active, kdb_consensus *d_out, double *d_sim, float *d_centroid, double *d_gram, hipStream_t s);
+// filter.hip: entries [first, first + n) of a column filled with "absent" (NaN / code 0); the predicate programs of kdb_filter_eval
+// (terms / prog_offsets: host arrays, already validated by kdb_filter_validate; staged through the lane's scratch)
+int kdb_launch_col_fill(void *d_col, uint32_t kind, size_t first, size_t n, hipStream_t s);
+int kdb_launch_filter_eval(kdb_index *idx, const kdb_filter_term *terms, const uint32_t *prog_offsets, uint32_t P, uint64_t *d_lists,
+                           uint64_t words_per_list, uint32_t *d_card, hipStream_t s);
 // graph construction (what the three files share: kdb_graph_build.cuh, kdb_walk_lds.h)
 // add.hip: the sequential Add
 int kdb_add_graph(kdb_index *idx, uint32_t first_id, uint32_t n, const uint8_t *levels, uint32_t ef_construction, kdb_add_stats *out);

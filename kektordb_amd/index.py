@@ -31,6 +31,17 @@ COUNT_TIED = 0x80000000
 COUNT_MASK = 0x7fffffff
 MIXED_BAD_QUERY = 0x40000000  # KDB_MIXED_BAD_QUERY: a query of a mixed _dev batch outside the launch's bounds (count 0, never walked)
 CONSENSUS_MAX_K = 64  # KDB_CONSENSUS_MAX_K
+NO_FILTER = 0xFFFFFFFF  # KDB_NO_FILTER
+# metadata filters on the device (kektor_hip.h, "metadata filters"): column kinds, term ops and flags, atom ops, limits
+MAX_COLUMNS = 16
+COL_F64, COL_CODE = 1, 2
+FOP_NEVER, FOP_F64_EQ, FOP_F64_LT, FOP_F64_LE, FOP_F64_GT, FOP_F64_GE, FOP_CODE_EQ = 0, 1, 2, 3, 4, 5, 6
+FT_OR_NEXT, FT_NOT, FT_END_BLOCK = 1, 2, 4
+FA_EQ, FA_NE, FA_LT, FA_LE, FA_GT, FA_GE = 0, 1, 2, 3, 4, 5
+FILTER_MAX_TERMS, FILTER_MAX_PROGRAMS = 64, 4096
+FILTER_TILE_IDS, FILTER_CHUNK = 1024, 32  # kdb_filter_plan.h: ids one wave covers per list, programs that share a column fetch
+TERM_DTYPE = np.dtype([("op", "u1"), ("flags", "u1"), ("col", "<u2"), ("code", "<u4"), ("value", "<f8")])  # kdb_filter_term
+ROUTE_WALK, ROUTE_SCAN, ROUTE_EMPTY = 0, 1, 2  # out_route of kdb_search_filtered
 # kdb_consensus: CalculateConsensus's score, variance and maxVar, len(nodes), len(activeNodes)
 CONSENSUS_DTYPE = np.dtype([("score", "<f8"), ("variance", "<f8"), ("max_pair", "<f8"), ("n_found", "<u4"), ("n_active", "<u4")])
 
@@ -720,6 +731,71 @@ class HipIndex:
                                                    _tptr(d_out_ids), _tptr(d_out_dist), _tptr(d_out_count),
                                                    C.c_void_p(stream) if stream else None), "kdb_merge_topk_packed_f64_dev")
 
+    # ---- metadata filters on the device (filter.hip) ------------------------------------------------
+    def set_column(self, col: int, kind: int, values, first_id: int = 1):
+        """Metadata column `col` (COL_F64: float64, NaN = no value; COL_CODE: uint32 dictionary codes, 0 = no value) for ids
+        first_id .. first_id + len(values) - 1; a torch device tensor goes through kdb_index_set_column_dev."""
+        self._live()
+        if hasattr(values, "data_ptr"):
+            _ready(None)
+            check(self.L.kdb_index_set_column_dev(self.h, col, kind, first_id, int(values.shape[0]), _tptr(values)), "kdb_index_set_column_dev")
+            return
+        v = np.ascontiguousarray(values, dtype=np.float64 if kind == COL_F64 else np.uint32)
+        check(self.L.kdb_index_set_column(self.h, col, kind, first_id, int(v.shape[0]), _ptr(v)), "kdb_index_set_column")
+
+    def drop_column(self, col: int):
+        self._live()
+        check(self.L.kdb_index_drop_column(self.h, col), "kdb_index_drop_column")
+
+    def column_info(self, col: int):
+        """(kind, bytes) of a slot; (0, 0) when it is empty"""
+        self._live()
+        kind, nbytes = C.c_uint32(), C.c_uint64()
+        check(self.L.kdb_index_column_info(self.h, col, C.byref(kind), C.byref(nbytes)), "kdb_index_column_info")
+        return int(kind.value), int(nbytes.value)
+
+    def filter_eval(self, programs, words_per_list: int = 0, want_lists: bool = True):
+        """programs: a list of TERM_DTYPE arrays (compile_filter makes them).  Returns (lists [P, words] uint64 or None, card [P])."""
+        self._live()
+        terms, offs = pack_programs(programs)
+        P = offs.size - 1
+        words = int(words_per_list) if words_per_list else (self.graph_info()[0] >> 6) + 1
+        lists = np.zeros((P, words), dtype=np.uint64) if want_lists else None
+        card = np.zeros(P, dtype=np.uint32)
+        check(self.L.kdb_filter_eval(self.h, _ptr(terms), _ptr(offs), P, _ptr(lists), words, _ptr(card)), "kdb_filter_eval")
+        return lists, card
+
+    def filter_eval_dev(self, programs, d_lists, d_card=None, stream=None):
+        """the same into device tensors: d_lists [P, words] int64 / uint64, d_card [P] int32 or None; asynchronous on `stream`"""
+        self._live()
+        _ready(stream)
+        terms, offs = pack_programs(programs)
+        P = offs.size - 1
+        assert int(d_lists.shape[0]) == P
+        check(self.L.kdb_filter_eval_dev(self.h, _ptr(terms), _ptr(offs), P, _tptr(d_lists), int(d_lists.shape[1]), _tptr(d_card),
+                                         C.c_void_p(stream) if stream else None), "kdb_filter_eval_dev")
+
+    def search_filtered(self, queries, k: int, ef: int, programs, prog_of_query, flat_selectivity: float = 0.1, tie_flag=False,
+                        heap_order=False):
+        """Engine.VSearch with a filter as one call (kdb_search_filtered): query b uses programs[prog_of_query[b]] (NO_FILTER / -1:
+        none).  Returns (ids [B, k], dist [B, k], count [B], route [B], card [P])."""
+        self._live()
+        q = np.ascontiguousarray(queries, dtype=np.float32)
+        B = q.shape[0]
+        terms, offs = pack_programs(programs)
+        P = offs.size - 1
+        poq = np.ascontiguousarray(np.asarray(prog_of_query, dtype=np.int64) & 0xFFFFFFFF, dtype=np.uint32)
+        assert poq.size == B
+        ids = np.zeros((B, k), dtype=np.uint32)
+        dist = np.zeros((B, k), dtype=np.float32)
+        cnt = np.zeros(B, dtype=np.uint32)
+        route = np.zeros(B, dtype=np.uint8)
+        card = np.zeros(P, dtype=np.uint32)
+        flags = (SEARCH_NEEDS_REFINE if self.needs_refine else 0) | (SEARCH_TIE_FLAG if tie_flag else 0) | (SEARCH_HEAP_ORDER if heap_order else 0)
+        check(self.L.kdb_search_filtered(self.h, _ptr(q), B, k, ef, _ptr(terms), _ptr(offs), P, _ptr(poq), float(flat_selectivity), flags,
+                                         _ptr(ids), _ptr(dist), _ptr(cnt), _ptr(route), _ptr(card)), "kdb_search_filtered")
+        return ids, dist, cnt, route, card
+
     # ---- the reference's per-query API --------------------------------------------------------------
     def score(self, raw: float) -> float:
         """The reference's f64 epilogue: float64(sum) (distance_go.go:67) / 1.0-float64(dot) (:127)."""
@@ -824,3 +900,66 @@ def dense_bitset(ids: Sequence[int], count: int) -> np.ndarray:
     if a.size:
         np.bitwise_or.at(w, (a >> np.uint64(6)).astype(np.int64), np.uint64(1) << (a & np.uint64(63)))
     return w
+
+
+def pack_programs(programs):
+    """a list of TERM_DTYPE arrays -> (terms, prog_offsets) as kdb_filter_eval takes them"""
+    progs = [np.ascontiguousarray(p, dtype=TERM_DTYPE).reshape(-1) for p in programs]
+    offs = np.zeros(len(progs) + 1, dtype=np.uint32)
+    if progs:
+        offs[1:] = np.cumsum([p.size for p in progs])
+    terms = np.concatenate(progs) if progs else np.zeros(0, dtype=TERM_DTYPE)
+    if terms.size == 0:
+        terms = np.zeros(1, dtype=TERM_DTYPE)  # (a pointer the library may refuse by its own rules, not a null one)
+    return np.ascontiguousarray(terms), offs
+
+
+def parse_filter(filter: str):
+    """kdb_filter_parse (host only, no GPU needed): the atoms of a filter string, in order, as dicts
+    {key, value, op (FA_*), is_numeric, number, end_block}.  Raises KdbError as the reference returns an error."""
+    L = _lib.load()
+    raw = filter.encode("utf-8")
+    n = C.c_uint32()
+    check(L.kdb_filter_parse(raw, None, 0, C.byref(n)), "kdb_filter_parse")
+    atoms = (_lib.FilterAtom * max(1, n.value))()
+    check(L.kdb_filter_parse(raw, C.cast(atoms, C.c_void_p), n.value, C.byref(n)), "kdb_filter_parse")
+    out = []
+    for a in atoms[:n.value]:
+        out.append({"key": raw[a.key_off:a.key_off + a.key_len].decode("utf-8", "replace"),
+                    "value": raw[a.val_off:a.val_off + a.val_len].decode("utf-8", "replace"), "op": int(a.op),
+                    "is_numeric": bool(a.is_numeric), "number": float(a.number), "end_block": bool(a.flags & FT_END_BLOCK)})
+    return out
+
+
+def compile_filter(filter: str, schema: dict) -> np.ndarray:
+    """A filter string -> one predicate program (TERM_DTYPE array) for this schema:
+        schema[key] = {"f64": slot or None, "code": slot or None, "dict": {string value: code >= 1}}
+    -- the key's numeric column (the reference's B-tree) and / or its code column with the caller's dictionary (its inverted index).
+    `k = v`: F64_EQ if v is numeric and k has a numeric column, CODE_EQ if k has a code column and the dictionary knows v (the lenient
+    union of core.go:1933-1944), NEVER if neither; `k != v` the same with NOT; a range operator is one F64 term, NEVER without a
+    numeric column.  A filter whose blocks are all empty ("AND OR AND" never gets this far: it has no operator) compiles to NEVER."""
+    terms = []
+    for a in parse_filter(filter):
+        sch = schema.get(a["key"]) or {}
+        f64, code = sch.get("f64"), sch.get("code")
+        alts = []
+        if a["op"] in (FA_EQ, FA_NE):
+            if a["is_numeric"] and f64 is not None:
+                alts.append((FOP_F64_EQ, f64, 0, a["number"]))
+            c = (sch.get("dict") or {}).get(a["value"]) if code is not None else None
+            if c:
+                alts.append((FOP_CODE_EQ, code, int(c), 0.0))
+        elif f64 is not None:
+            alts.append(({FA_LT: FOP_F64_LT, FA_LE: FOP_F64_LE, FA_GT: FOP_F64_GT, FA_GE: FOP_F64_GE}[a["op"]], f64, 0, a["number"]))
+        if not alts:
+            alts.append((FOP_NEVER, 0, 0, 0.0))
+        for i, (op, col, c, val) in enumerate(alts):
+            fl = (FT_OR_NEXT if i + 1 < len(alts) else 0) | (FT_NOT if i == 0 and a["op"] == FA_NE else 0)
+            if i + 1 == len(alts) and a["end_block"]:
+                fl |= FT_END_BLOCK
+            terms.append((op, fl, col, c, val))
+    if not terms:
+        terms.append((FOP_NEVER, FT_END_BLOCK, 0, 0, 0.0))
+    if len(terms) > FILTER_MAX_TERMS:
+        raise KdbError(f"compile_filter: {len(terms)} terms, a program holds at most {FILTER_MAX_TERMS}")
+    return np.array(terms, dtype=TERM_DTYPE)
