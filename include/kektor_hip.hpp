@@ -731,7 +731,8 @@ class BasicMicroBatcher {
     }
     // a filter that allows less than flatScanSelectivity of the ids takes the exact scan, which answers k <= kMaxFlatK
     // (kdb_flat_scan_batch); larger k keeps the graph walk, which still answers -- routing must never turn a query the reference
-    // would answer into []
+    // would answer into [].  The library states the same rule once more, per filter program, for kdb_search_filtered:
+    // kdb_filter_route_of (kektordb_amd/csrc/kdb_filter_plan.h, tested by tests/cpp/filter_plan_test.cpp)
     bool takes_flat_scan(int k, const AllowList *allowList) const {
         uint64_t allowed = 0;
         for (uint64_t w : allowList->words) allowed += (uint64_t)__builtin_popcountll(w);

@@ -34,7 +34,8 @@ extern "C" const char *kdb_last_error(void) { return g_err; }
 // GPU_MAX_HW_QUEUES says otherwise (measured: scripts/micro/launch_rate.hip -- 8 threads with a 150 us kernel each reach 25.6 k
 // launches/s on four queues, 42.7 k on eight).  The library does NOT touch the environment (round 5 did, from a constructor: a
 // process-wide side effect, and setenv is not thread-safe under a dlopen from a threaded host): the host that wants eight queues
-// sets the variable before the runtime starts -- INTEGRATION.md, kektordb_amd/__init__.py.
+// sets the variable before the runtime starts -- INTEGRATION.md ("Contract notes").  Nothing in this repository sets it: not the
+// Python package, not bench.py, not the tests.
 extern "C" int kdb_abi_version(void) { return KDB_ABI_VERSION; }
 
 extern "C" int kdb_hip_device_count(void) {
@@ -1613,10 +1614,10 @@ static int combined_search_call(kdb_index *idx, const float *queries, uint32_t B
 }
 
 // One host-pointer call through a slot, alone: exact scans, filtered searches, searches of more than KDB_COMBINE_MAX_B queries.
-// run(d_q, d_allow, d_ids, d_dist, d_cnt, stream, B) enqueues the work (under idx->mu).  Page-locked staging: one memcpy in, one
-// copy of queries | allow list, ONE device-to-host copy of ids | distances | counts, one memcpy out -- or, for a graph search of
-// a few queries, none: the kernel writes its answers straight into the page-locked buffer (posted writes over PCIe; the end of
-// the kernel makes them visible).
+// run(d_q, d_allow, d_ids, d_dist, d_cnt, stream, B, d_k, d_ef) enqueues the work (under idx->mu; d_k, d_ef: the staged arrays of a
+// mixed call, else null).  Page-locked staging: one memcpy in, one copy of queries | allow list, ONE device-to-host copy of
+// ids | distances | counts, one memcpy out -- or, for a graph search of a few queries, none: the kernel writes its answers straight
+// into the page-locked buffer (posted writes over PCIe; the end of the kernel makes them visible).
 template <typename F>
 static int staged_slot_call(kdb_index *idx, const float *queries, uint32_t B, uint32_t k, const uint64_t *allow_bits, uint32_t *out_ids, void *out_dist,
                             uint32_t *out_count, size_t dist_bytes, bool direct_out, F run, const HostKeys *hk = nullptr) {
@@ -1656,10 +1657,12 @@ static int staged_slot_call(kdb_index *idx, const float *queries, uint32_t B, ui
                 rc = KDB_ERR_HIP;
             }
             queued = rc == KDB_OK;
-            if (rc == KDB_OK)
+            if (rc == KDB_OK) {
+                const uint32_t *const d_k = hk ? reinterpret_cast<uint32_t *>(d + L.o_keys) : nullptr;
                 rc = run(reinterpret_cast<float *>(d), allow_bits ? reinterpret_cast<uint64_t *>(d + L.o_allow) : nullptr,
                          reinterpret_cast<uint32_t *>(o_base + L.o_ids), reinterpret_cast<float *>(o_base + L.o_dist),
-                         reinterpret_cast<uint32_t *>(o_base + L.o_cnt), sl.stream, B);
+                         reinterpret_cast<uint32_t *>(o_base + L.o_cnt), sl.stream, B, d_k, hk ? d_k + B : nullptr);
+            }
         }
         if (rc == KDB_OK && !direct && hipMemcpyAsync(h + L.o_ids, d + L.o_ids, L.out_span, hipMemcpyDeviceToHost, sl.stream) != hipSuccess) {
             kdb_set_error("staging copy from the device failed");
@@ -1744,39 +1747,75 @@ struct DropWatch {
     }
 };
 
-// A search or an exact scan of queries on a turn: run(d_q, d_allow, d_ids, d_dist, d_cnt, stream, B) as for staged_slot_call.
+// The frame of a call that takes ONE turn: the turn, the buffer, the copies in outside idx->mu, the enqueue under it on a scratch
+// lane, the copies out outside it, the wait.  declare(st) runs under idx->mu right after the turn is taken (sizes that follow the
+// index's count are read there) and declares every region once; run(d, s) enqueues the work on d = the staged buffer.  The copies
+// go region by region in declaration order on idx->stream.  Two calls differ, and say so:
+struct KdbTurnOpt {
+    bool lane = true;               // false: the kernel needs no scratch -- no lane, and run() is called OUTSIDE idx->mu (consensus)
+    bool launch_first = false;      // nothing to copy in: run() before idx->mu is first dropped (filter_eval); with a lane only
+    size_t slack = 0;               // bytes kept free behind the last region
+    const char *drop_who = nullptr; // set: KDB_SEARCH_FAIL_ON_DROP, reported under this name
+};
+template <typename Declare, typename Run>
+static int kdb_turn_call(kdb_index *idx, const KdbTurnOpt &opt, Declare declare, Run run) {
+    HostTurn turn(idx);
+    KdbStage st;
+    int rc = declare(st);
+    if (rc) return rc;
+    if (st.overflow || (opt.launch_first && !opt.lane)) { // (launch_first launches under idx->mu: it goes with a lane only)
+        kdb_set_error("turn call: %s", st.overflow ? "more staged regions than KdbStage::CAP" : "launch_first without a lane");
+        return KDB_ERR_INVALID;
+    }
+    unsigned char *const d = turn.stage(st.total() + opt.slack);
+    if (!d) return turn.rc;
+    hipStream_t s = idx->stream;
+    if (!opt.launch_first) {
+        turn.lk.unlock();
+        rc = st.copy_in(d, [&](void *dst, const void *src, size_t n) -> int { KDB_HIP(hipMemcpyAsync(dst, src, n, hipMemcpyHostToDevice, s)); return KDB_OK; });
+        if (rc) return rc;
+        if (opt.lane) turn.lk.lock();
+    }
+    DropWatch drops;
+    if (opt.lane) {
+        KdbLaneGuard lane(idx, s);
+        if (lane.rc) return lane.rc;
+        rc = run(d, s);
+        if (opt.drop_who) drops.note(idx);
+    } else {
+        rc = run(d, s);
+    }
+    if (turn.lk.owns_lock()) turn.lk.unlock();
+    if (rc) return rc;
+    rc = st.copy_out(d, [&](void *dst, const void *src, size_t n) -> int { KDB_HIP(hipMemcpyAsync(dst, src, n, hipMemcpyDeviceToHost, s)); return KDB_OK; });
+    if (rc) return rc;
+    KDB_HIP(hipStreamSynchronize(s));
+    return opt.drop_who ? drops.check(idx, opt.drop_who) : KDB_OK;
+}
+
+// A search or an exact scan of queries on a turn: run(d_q, d_allow, d_ids, d_dist, d_cnt, stream, B, d_k, d_ef) as for staged_slot_call.
 template <typename F>
 static int staged_big_call(kdb_index *idx, const float *queries, uint32_t B, uint32_t k, const uint64_t *allow_bits, uint32_t *out_ids, void *out_dist,
                            uint32_t *out_count, size_t dist_bytes, bool fail_on_drop, F run, const HostKeys *hk = nullptr) {
-    HostTurn turn(idx);
-    const StagedLayout L = staged_layout(idx, B, k, allow_bits != nullptr, dist_bytes, hk != nullptr);
-    unsigned char *const d = turn.stage(L.total);
-    if (!d) return turn.rc;
-    hipStream_t s = idx->stream;
-    turn.lk.unlock();
-    KDB_HIP(hipMemcpyAsync(d, queries, L.qbytes, hipMemcpyHostToDevice, s));
-    if (hk) {
-        KDB_HIP(hipMemcpyAsync(d + L.o_keys, hk->k, (size_t)B * 4, hipMemcpyHostToDevice, s));
-        KDB_HIP(hipMemcpyAsync(d + L.o_keys + (size_t)B * 4, hk->ef, (size_t)B * 4, hipMemcpyHostToDevice, s));
-    }
-    if (allow_bits) KDB_HIP(hipMemcpyAsync(d + L.o_allow, allow_bits, L.aw, hipMemcpyHostToDevice, s));
-    turn.lk.lock();
-    DropWatch drops;
-    int rc;
-    {
-        KdbLaneGuard lane(idx, s);
-        if (lane.rc) return lane.rc;
-        rc = run(reinterpret_cast<float *>(d), allow_bits ? reinterpret_cast<uint64_t *>(d + L.o_allow) : nullptr, reinterpret_cast<uint32_t *>(d + L.o_ids),
-                 reinterpret_cast<float *>(d + L.o_dist), reinterpret_cast<uint32_t *>(d + L.o_cnt), s, B);
-        drops.note(idx);
-    }
-    turn.lk.unlock();
-    if (rc) return rc;
-    KDB_HIP(hipMemcpyAsync(out_ids, d + L.o_ids, (size_t)B * k * 4, hipMemcpyDeviceToHost, s));
-    KDB_HIP(hipMemcpyAsync(out_dist, d + L.o_dist, (size_t)B * k * dist_bytes, hipMemcpyDeviceToHost, s));
-    KDB_HIP(hipMemcpyAsync(out_count, d + L.o_cnt, (size_t)B * 4, hipMemcpyDeviceToHost, s));
-    KDB_HIP(hipStreamSynchronize(s));
-    return fail_on_drop ? drops.check(idx, "search") : KDB_OK;
+    KdbRegion q, kq, efq, allow, ids, dist, cnt;
+    KdbTurnOpt opt;
+    opt.slack = 1024;
+    opt.drop_who = fail_on_drop ? "search" : nullptr;
+    return kdb_turn_call(
+        idx, opt,
+        [&](KdbStage &st) {
+            q = st.in(queries, (size_t)B * idx->desc.dim * 4);
+            kq = st.in(hk ? hk->k : nullptr, (size_t)B * 4);
+            efq = st.in(hk ? hk->ef : nullptr, (size_t)B * 4);
+            allow = st.in(allow_bits, kdb_bits_bytes(idx->count));
+            ids = st.out(out_ids, (size_t)B * k * 4);
+            dist = st.out(out_dist, (size_t)B * k * dist_bytes);
+            cnt = st.out(out_count, (size_t)B * 4);
+            return KDB_OK;
+        },
+        [&](unsigned char *d, hipStream_t s) {
+            return run(q.at<float>(d), allow.at<uint64_t>(d), ids.at<uint32_t>(d), dist.at<float>(d), cnt.at<uint32_t>(d), s, B, kq.at<uint32_t>(d), efq.at<uint32_t>(d));
+        });
 }
 
 // Host-pointer search of a large batch in chunks that alternate between two streams (and two scratch lanes): the
@@ -1787,22 +1826,21 @@ static int search_staged_chunks(kdb_index *idx, const float *queries, uint32_t B
     HostTurn turn(idx, true); // (both streams: the destructor waits for stream2 as well)
     const size_t dist_bytes = (flags & KDB_SEARCH_DIST_F64) ? 8 : 4;
     const size_t dim = idx->desc.dim;
-    const size_t aw = allow_bits ? kdb_bits_bytes(idx->count) : 0;
-    KdbCarver cv;
-    const size_t o_q = cv.take((size_t)B * dim * 4), o_allow = cv.take(aw), o_ids = cv.take((size_t)B * k * 4), o_dist = cv.take((size_t)B * k * dist_bytes),
-                 o_cnt = cv.take((size_t)B * 4);
-    unsigned char *const p = turn.stage(cv.total() + 1024);
+    KdbStage st; // (the allow list is the one region copied whole; queries and answers go chunk by chunk, below)
+    const KdbRegion r_q = st.dev((size_t)B * dim * 4), r_allow = st.in(allow_bits, kdb_bits_bytes(idx->count)), r_ids = st.dev((size_t)B * k * 4),
+                    r_dist = st.dev((size_t)B * k * dist_bytes), r_cnt = st.dev((size_t)B * 4);
+    unsigned char *const p = turn.stage(st.total() + 1024);
     if (!p) return turn.rc;
     int rc = KDB_OK;
-    float *d_q = reinterpret_cast<float *>(p + o_q);
-    uint64_t *d_allow = allow_bits ? reinterpret_cast<uint64_t *>(p + o_allow) : nullptr;
-    uint32_t *d_ids = reinterpret_cast<uint32_t *>(p + o_ids);
-    unsigned char *d_dist = p + o_dist;
-    uint32_t *d_cnt = reinterpret_cast<uint32_t *>(p + o_cnt);
+    float *d_q = r_q.at<float>(p);
+    uint64_t *d_allow = r_allow.at<uint64_t>(p);
+    uint32_t *d_ids = r_ids.at<uint32_t>(p);
+    unsigned char *d_dist = r_dist.at<unsigned char>(p);
+    uint32_t *d_cnt = r_cnt.at<uint32_t>(p);
     hipStream_t s1 = idx->stream, s2 = idx->stream2;
     turn.lk.unlock();
     if (allow_bits) {
-        KDB_HIP(hipMemcpyAsync(d_allow, allow_bits, aw, hipMemcpyHostToDevice, s1));
+        KDB_HIP(hipMemcpyAsync(d_allow, allow_bits, r_allow.bytes, hipMemcpyHostToDevice, s1));
         KDB_HIP(hipEventRecord(idx->ev_io, s1));
         KDB_HIP(hipStreamWaitEvent(s2, idx->ev_io, 0));
     }
@@ -1895,7 +1933,7 @@ extern "C" int kdb_search_batch(kdb_index *idx, const float *queries, uint32_t B
         return search_staged_chunks(idx, queries, B, k, ef, allow_bits, flags, out_ids, out_dist, out_count, chunk);
     }
     const size_t dist_bytes = (flags & KDB_SEARCH_DIST_F64) ? 8 : 4;
-    auto run = [&](float *d_q, uint64_t *d_allow, uint32_t *d_ids, float *d_dist, uint32_t *d_cnt, hipStream_t s, uint32_t nq) {
+    auto run = [&](float *d_q, uint64_t *d_allow, uint32_t *d_ids, float *d_dist, uint32_t *d_cnt, hipStream_t s, uint32_t nq, const uint32_t *, const uint32_t *) {
         return search_dev_locked(idx, d_q, nq, k, ef, d_allow, flags, d_ids, d_dist, d_cnt, s);
     };
     if (traced || (flags & KDB_SEARCH_FAIL_ON_DROP) || !fits_a_slot(idx, B, k, allow_bits != nullptr, dist_bytes))
@@ -1935,11 +1973,11 @@ extern "C" int kdb_search_batch_mixed(kdb_index *idx, const float *queries, uint
     KDB_HIP(hipSetDevice(idx->device));
     const size_t dist_bytes = (flags & KDB_SEARCH_DIST_F64) ? 8 : 4;
     const HostKeys hk{k, ef};
-    auto run = [&](float *d_q, uint64_t *d_allow, uint32_t *d_ids, float *d_dist, uint32_t *d_cnt, hipStream_t s, uint32_t nq) {
-        const StagedLayout L = staged_layout(idx, nq, k_stride, d_allow != nullptr, dist_bytes, true);
+    auto run = [&](float *d_q, uint64_t *d_allow, uint32_t *d_ids, float *d_dist, uint32_t *d_cnt, hipStream_t s, uint32_t nq, const uint32_t *d_k,
+                   const uint32_t *d_ef) {
         MixedKeys m = mx;
-        m.d_k = reinterpret_cast<const uint32_t *>(reinterpret_cast<const unsigned char *>(d_q) + L.o_keys);
-        m.d_ef = m.d_k + nq;
+        m.d_k = d_k;
+        m.d_ef = d_ef;
         const int rc = search_dev_locked(idx, d_q, nq, k_stride, 0u, d_allow, flags, d_ids, d_dist, d_cnt, s, nullptr, nullptr, &m);
         if (rc == KDB_OK && distinct && idx->has_graph && idx->count) { // (under idx->mu, as every enqueue)
             idx->n_mixed_launches++;
@@ -2156,7 +2194,7 @@ extern "C" int kdb_flat_scan_batch(kdb_index *idx, const float *queries, uint32_
     }
     KDB_HIP(hipSetDevice(idx->device));
     const size_t dist_bytes = (flags & KDB_SEARCH_DIST_F64) ? 8 : 4;
-    auto run = [&](float *d_q, uint64_t *d_allow, uint32_t *d_ids, float *d_dist, uint32_t *d_cnt, hipStream_t s, uint32_t nq) {
+    auto run = [&](float *d_q, uint64_t *d_allow, uint32_t *d_ids, float *d_dist, uint32_t *d_cnt, hipStream_t s, uint32_t nq, const uint32_t *, const uint32_t *) {
         return flat_dev_locked(idx, d_q, nq, k, d_allow, flags, d_ids, d_dist, d_cnt, s);
     };
     if (!fits_a_slot(idx, B, k, allow_bits != nullptr, dist_bytes)) return staged_big_call(idx, queries, B, k, allow_bits, out_ids, out_dist, out_count, dist_bytes, false, run);
@@ -2200,30 +2238,18 @@ extern "C" int kdb_distance_batch(kdb_index *idx, const float *queries, uint32_t
         return KDB_ERR_INVALID;
     }
     KDB_HIP(hipSetDevice(idx->device));
-    HostTurn turn(idx);
-    KdbCarver cv;
-    const size_t o_q = cv.take((size_t)B * idx->desc.dim * 4), o_ids = cv.take((size_t)B * C * 4), o_out = cv.take((size_t)B * C * 4);
-    unsigned char *const p = turn.stage(cv.total() + 256);
-    if (!p) return turn.rc;
-    float *d_q = reinterpret_cast<float *>(p + o_q);
-    uint32_t *d_ids = reinterpret_cast<uint32_t *>(p + o_ids);
-    float *d_out = reinterpret_cast<float *>(p + o_out);
-    hipStream_t s = idx->stream;
-    turn.lk.unlock();
-    KDB_HIP(hipMemcpyAsync(d_q, queries, (size_t)B * idx->desc.dim * 4, hipMemcpyHostToDevice, s));
-    KDB_HIP(hipMemcpyAsync(d_ids, ids, (size_t)B * C * 4, hipMemcpyHostToDevice, s));
-    turn.lk.lock();
-    int rc;
-    {
-        KdbLaneGuard lane(idx, s);
-        if (lane.rc) return lane.rc;
-        rc = distance_dev_locked(idx, d_q, B, d_ids, C, flags, d_out, s);
-    }
-    turn.lk.unlock();
-    if (rc) return rc;
-    KDB_HIP(hipMemcpyAsync(out, d_out, (size_t)B * C * 4, hipMemcpyDeviceToHost, s));
-    KDB_HIP(hipStreamSynchronize(s));
-    return KDB_OK;
+    KdbRegion q, cand, res;
+    KdbTurnOpt opt;
+    opt.slack = 256;
+    return kdb_turn_call(
+        idx, opt,
+        [&](KdbStage &st) {
+            q = st.in(queries, (size_t)B * idx->desc.dim * 4);
+            cand = st.in(ids, (size_t)B * C * 4);
+            res = st.out(out, (size_t)B * C * 4);
+            return KDB_OK;
+        },
+        [&](unsigned char *d, hipStream_t s) { return distance_dev_locked(idx, q.at<float>(d), B, cand.at<uint32_t>(d), C, flags, res.at<float>(d), s); });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2314,36 +2340,24 @@ static int by_id_host_call(kdb_index *idx, bool flat, const uint32_t *ids, uint3
         return KDB_ERR_INVALID;
     }
     KDB_HIP(hipSetDevice(idx->device));
-    HostTurn turn(idx);
     const size_t db = (flags & KDB_SEARCH_DIST_F64) ? 8 : 4;
-    const size_t aw = allow_bits ? kdb_bits_bytes(idx->count) : 0;
-    KdbCarver cv;
-    const size_t o_src = cv.take((size_t)B * 4), o_allow = cv.take(aw), o_ids = cv.take((size_t)B * k * 4), o_dist = cv.take((size_t)B * k * db),
-                 o_cnt = cv.take((size_t)B * 4);
-    unsigned char *const d = turn.stage(cv.total());
-    if (!d) return turn.rc;
-    hipStream_t s = idx->stream;
-    turn.lk.unlock();
-    KDB_HIP(hipMemcpyAsync(d + o_src, ids, (size_t)B * 4, hipMemcpyHostToDevice, s));
-    if (allow_bits) KDB_HIP(hipMemcpyAsync(d + o_allow, allow_bits, aw, hipMemcpyHostToDevice, s));
-    turn.lk.lock();
-    DropWatch drops;
-    int rc;
-    {
-        KdbLaneGuard lane(idx, s);
-        if (lane.rc) return lane.rc;
-        rc = by_id_dev_locked(idx, flat, reinterpret_cast<uint32_t *>(d + o_src), B, k, ef, allow_bits ? reinterpret_cast<uint64_t *>(d + o_allow) : nullptr,
-                              flags & ~(uint32_t)KDB_SEARCH_FAIL_ON_DROP, reinterpret_cast<uint32_t *>(d + o_ids), reinterpret_cast<float *>(d + o_dist),
-                              reinterpret_cast<uint32_t *>(d + o_cnt), s);
-        drops.note(idx);
-    }
-    turn.lk.unlock();
-    if (rc) return rc;
-    KDB_HIP(hipMemcpyAsync(out_ids, d + o_ids, (size_t)B * k * 4, hipMemcpyDeviceToHost, s));
-    KDB_HIP(hipMemcpyAsync(out_dist, d + o_dist, (size_t)B * k * db, hipMemcpyDeviceToHost, s));
-    KDB_HIP(hipMemcpyAsync(out_count, d + o_cnt, (size_t)B * 4, hipMemcpyDeviceToHost, s));
-    KDB_HIP(hipStreamSynchronize(s));
-    return !flat && (flags & KDB_SEARCH_FAIL_ON_DROP) ? drops.check(idx, "search_by_id") : KDB_OK;
+    KdbRegion src, allow, r_ids, r_dist, r_cnt;
+    KdbTurnOpt opt;
+    opt.drop_who = !flat && (flags & KDB_SEARCH_FAIL_ON_DROP) ? "search_by_id" : nullptr;
+    return kdb_turn_call(
+        idx, opt,
+        [&](KdbStage &st) {
+            src = st.in(ids, (size_t)B * 4);
+            allow = st.in(allow_bits, kdb_bits_bytes(idx->count));
+            r_ids = st.out(out_ids, (size_t)B * k * 4);
+            r_dist = st.out(out_dist, (size_t)B * k * db);
+            r_cnt = st.out(out_count, (size_t)B * 4);
+            return KDB_OK;
+        },
+        [&](unsigned char *d, hipStream_t s) {
+            return by_id_dev_locked(idx, flat, src.at<uint32_t>(d), B, k, ef, allow.at<uint64_t>(d), flags & ~(uint32_t)KDB_SEARCH_FAIL_ON_DROP, r_ids.at<uint32_t>(d),
+                                    r_dist.at<float>(d), r_cnt.at<uint32_t>(d), s);
+        });
 }
 
 extern "C" int kdb_search_by_id(kdb_index *idx, const uint32_t *ids, uint32_t B, uint32_t k, uint32_t ef, const uint64_t *allow_bits, uint32_t flags,
@@ -2383,21 +2397,24 @@ extern "C" int kdb_index_decode_rows(kdb_index *idx, const uint32_t *ids, uint32
     size_t per = ((size_t)64 << 20) / row_b;
     if (per < 1) per = 1;
     if (per > n) per = n;
-    KdbCarver cv;
-    const size_t o_ids = cv.take(per * 4), o_rows = cv.take(per * row_b), o_found = cv.take(per);
-    unsigned char *const d = turn.stage(cv.total());
+    KdbStage st; // (the layout only: every piece is copied in and out by the loop below)
+    const KdbRegion r_ids = st.dev(per * 4), r_rows = st.dev(per * row_b), r_found = st.dev(per);
+    unsigned char *const d = turn.stage(st.total());
     if (!d) return turn.rc;
+    uint32_t *const d_ids = r_ids.at<uint32_t>(d);
+    float *const d_rows = r_rows.at<float>(d);
+    uint8_t *const d_found = r_found.at<uint8_t>(d);
     hipStream_t s = idx->stream;
     const KdbView v = kdb_make_view(idx); // (the call is counted: writers stay out, count, rows and deleted bits cannot move)
     turn.lk.unlock();
     int rc;
     for (size_t i0 = 0; i0 < n; i0 += per) {
         const uint32_t m = (uint32_t)(n - i0 < per ? n - i0 : per);
-        KDB_HIP(hipMemcpyAsync(d + o_ids, ids + i0, (size_t)m * 4, hipMemcpyHostToDevice, s));
-        rc = kdb_launch_decode_rows(v, reinterpret_cast<uint32_t *>(d + o_ids), m, reinterpret_cast<float *>(d + o_rows), d + o_found, 0u, s);
+        KDB_HIP(hipMemcpyAsync(d_ids, ids + i0, (size_t)m * 4, hipMemcpyHostToDevice, s));
+        rc = kdb_launch_decode_rows(v, d_ids, m, d_rows, d_found, 0u, s);
         if (rc) return rc;
-        KDB_HIP(hipMemcpyAsync(out + i0 * idx->desc.dim, d + o_rows, (size_t)m * row_b, hipMemcpyDeviceToHost, s));
-        if (out_found) KDB_HIP(hipMemcpyAsync(out_found + i0, d + o_found, m, hipMemcpyDeviceToHost, s));
+        KDB_HIP(hipMemcpyAsync(out + i0 * idx->desc.dim, d_rows, (size_t)m * row_b, hipMemcpyDeviceToHost, s));
+        if (out_found) KDB_HIP(hipMemcpyAsync(out_found + i0, d_found, m, hipMemcpyDeviceToHost, s));
     }
     KDB_HIP(hipStreamSynchronize(s));
     return KDB_OK;
@@ -2456,33 +2473,29 @@ extern "C" int kdb_consensus_batch(kdb_index *idx, const uint32_t *ids, const ui
             }
     if (B == 0) return KDB_OK;
     KDB_HIP(hipSetDevice(idx->device));
-    HostTurn turn(idx);
     const size_t dim = idx->desc.dim, gw = (size_t)stride + 1;
-    const size_t aw = active_bits ? kdb_bits_bytes(idx->count) : 0;
-    KdbCarver cv;
-    const size_t o_ids = cv.take((size_t)B * stride * 4), o_cnt = cv.take(counts ? (size_t)B * 4 : 0), o_q = cv.take(queries ? (size_t)B * dim * 4 : 0),
-                 o_act = cv.take(aw), o_out = cv.take((size_t)B * sizeof(kdb_consensus)), o_sim = cv.take(out_similarity ? (size_t)B * stride * 8 : 0),
-                 o_cen = cv.take(out_centroid ? (size_t)B * dim * 4 : 0), o_gram = cv.take(out_gram ? (size_t)B * gw * gw * 8 : 0);
-    unsigned char *const d = turn.stage(cv.total());
-    if (!d) return turn.rc;
-    hipStream_t s = idx->stream;
-    const KdbView v = kdb_make_view(idx); // (the call is counted: writers stay out, count, rows and deleted bits cannot move)
-    turn.lk.unlock();
-    if (stride) KDB_HIP(hipMemcpyAsync(d + o_ids, ids, (size_t)B * stride * 4, hipMemcpyHostToDevice, s));
-    if (counts) KDB_HIP(hipMemcpyAsync(d + o_cnt, counts, (size_t)B * 4, hipMemcpyHostToDevice, s));
-    if (queries) KDB_HIP(hipMemcpyAsync(d + o_q, queries, (size_t)B * dim * 4, hipMemcpyHostToDevice, s));
-    if (active_bits) KDB_HIP(hipMemcpyAsync(d + o_act, active_bits, aw, hipMemcpyHostToDevice, s));
-    rc = kdb_launch_consensus(v, reinterpret_cast<uint32_t *>(d + o_ids), counts ? reinterpret_cast<uint32_t *>(d + o_cnt) : nullptr, B, stride,
-                              queries ? reinterpret_cast<float *>(d + o_q) : nullptr, active_bits ? reinterpret_cast<uint32_t *>(d + o_act) : nullptr,
-                              reinterpret_cast<kdb_consensus *>(d + o_out), out_similarity ? reinterpret_cast<double *>(d + o_sim) : nullptr,
-                              out_centroid ? reinterpret_cast<float *>(d + o_cen) : nullptr, out_gram ? reinterpret_cast<double *>(d + o_gram) : nullptr, s);
-    if (rc) return rc;
-    KDB_HIP(hipMemcpyAsync(out, d + o_out, (size_t)B * sizeof(kdb_consensus), hipMemcpyDeviceToHost, s));
-    if (out_similarity && stride) KDB_HIP(hipMemcpyAsync(out_similarity, d + o_sim, (size_t)B * stride * 8, hipMemcpyDeviceToHost, s));
-    if (out_centroid) KDB_HIP(hipMemcpyAsync(out_centroid, d + o_cen, (size_t)B * dim * 4, hipMemcpyDeviceToHost, s));
-    if (out_gram) KDB_HIP(hipMemcpyAsync(out_gram, d + o_gram, (size_t)B * gw * gw * 8, hipMemcpyDeviceToHost, s));
-    KDB_HIP(hipStreamSynchronize(s));
-    return KDB_OK;
+    KdbRegion r_ids, r_cnt, r_q, r_act, r_out, r_sim, r_cen, r_gram;
+    KdbView v;
+    KdbTurnOpt opt;
+    opt.lane = false; // the kernel reads the lists, the rows and the queries where they are: no scratch, launched outside idx->mu
+    return kdb_turn_call(
+        idx, opt,
+        [&](KdbStage &st) { // (stride == 0: the lists and the similarities are empty regions -- null to the kernel, which reads and writes none of them)
+            r_ids = st.in(ids, (size_t)B * stride * 4);
+            r_cnt = st.in(counts, (size_t)B * 4);
+            r_q = st.in(queries, (size_t)B * dim * 4);
+            r_act = st.in(active_bits, kdb_bits_bytes(idx->count));
+            r_out = st.out(out, (size_t)B * sizeof(kdb_consensus));
+            r_sim = st.out(out_similarity, (size_t)B * stride * 8);
+            r_cen = st.out(out_centroid, (size_t)B * dim * 4);
+            r_gram = st.out(out_gram, (size_t)B * gw * gw * 8);
+            v = kdb_make_view(idx); // (once staged the call is counted: writers stay out, count, rows and deleted bits cannot move)
+            return KDB_OK;
+        },
+        [&](unsigned char *d, hipStream_t s) {
+            return kdb_launch_consensus(v, r_ids.at<uint32_t>(d), r_cnt.at<uint32_t>(d), B, stride, r_q.at<float>(d), r_act.at<uint32_t>(d), r_out.at<kdb_consensus>(d),
+                                        r_sim.at<double>(d), r_cen.at<float>(d), r_gram.at<double>(d), s);
+        });
 }
 
 static int belief_check(uint32_t B, uint32_t k, uint32_t flags, const void *queries, const void *out_ids, const void *out_dist, const void *out_count,
@@ -2532,40 +2545,27 @@ extern "C" int kdb_belief_batch(kdb_index *idx, const float *queries, uint32_t B
     if (rc) return rc;
     if (B == 0) return KDB_OK;
     KDB_HIP(hipSetDevice(idx->device));
-    HostTurn turn(idx);
     const size_t db = (flags & KDB_SEARCH_DIST_F64) ? 8 : 4;
-    const size_t bw = kdb_bits_bytes(idx->count);
-    KdbCarver cv;
-    const size_t o_q = cv.take((size_t)B * idx->desc.dim * 4), o_allow = cv.take(allow_bits ? bw : 0), o_act = cv.take(active_bits ? bw : 0),
-                 o_ids = cv.take((size_t)B * k * 4), o_dist = cv.take((size_t)B * k * db), o_cnt = cv.take((size_t)B * 4),
-                 o_out = cv.take((size_t)B * sizeof(kdb_consensus)), o_sim = cv.take(out_similarity ? (size_t)B * k * 8 : 0);
-    unsigned char *const d = turn.stage(cv.total());
-    if (!d) return turn.rc;
-    hipStream_t s = idx->stream;
-    turn.lk.unlock();
-    KDB_HIP(hipMemcpyAsync(d + o_q, queries, (size_t)B * idx->desc.dim * 4, hipMemcpyHostToDevice, s));
-    if (allow_bits) KDB_HIP(hipMemcpyAsync(d + o_allow, allow_bits, bw, hipMemcpyHostToDevice, s));
-    if (active_bits) KDB_HIP(hipMemcpyAsync(d + o_act, active_bits, bw, hipMemcpyHostToDevice, s));
-    turn.lk.lock();
-    DropWatch drops;
-    {
-        KdbLaneGuard lane(idx, s);
-        if (lane.rc) return lane.rc;
-        rc = belief_dev_locked(idx, reinterpret_cast<float *>(d + o_q), B, k, ef, allow_bits ? reinterpret_cast<uint64_t *>(d + o_allow) : nullptr,
-                               active_bits ? reinterpret_cast<uint64_t *>(d + o_act) : nullptr, flags & ~(uint32_t)KDB_SEARCH_FAIL_ON_DROP,
-                               reinterpret_cast<uint32_t *>(d + o_ids), reinterpret_cast<float *>(d + o_dist), reinterpret_cast<uint32_t *>(d + o_cnt),
-                               reinterpret_cast<kdb_consensus *>(d + o_out), out_similarity ? reinterpret_cast<double *>(d + o_sim) : nullptr, s);
-        drops.note(idx);
-    }
-    turn.lk.unlock();
-    if (rc) return rc;
-    KDB_HIP(hipMemcpyAsync(out_ids, d + o_ids, (size_t)B * k * 4, hipMemcpyDeviceToHost, s));
-    KDB_HIP(hipMemcpyAsync(out_dist, d + o_dist, (size_t)B * k * db, hipMemcpyDeviceToHost, s));
-    KDB_HIP(hipMemcpyAsync(out_count, d + o_cnt, (size_t)B * 4, hipMemcpyDeviceToHost, s));
-    KDB_HIP(hipMemcpyAsync(out, d + o_out, (size_t)B * sizeof(kdb_consensus), hipMemcpyDeviceToHost, s));
-    if (out_similarity) KDB_HIP(hipMemcpyAsync(out_similarity, d + o_sim, (size_t)B * k * 8, hipMemcpyDeviceToHost, s));
-    KDB_HIP(hipStreamSynchronize(s));
-    return (flags & KDB_SEARCH_FAIL_ON_DROP) ? drops.check(idx, "belief") : KDB_OK;
+    KdbRegion q, allow, act, r_ids, r_dist, r_cnt, r_out, r_sim;
+    KdbTurnOpt opt;
+    opt.drop_who = (flags & KDB_SEARCH_FAIL_ON_DROP) ? "belief" : nullptr;
+    return kdb_turn_call(
+        idx, opt,
+        [&](KdbStage &st) {
+            q = st.in(queries, (size_t)B * idx->desc.dim * 4);
+            allow = st.in(allow_bits, kdb_bits_bytes(idx->count));
+            act = st.in(active_bits, kdb_bits_bytes(idx->count));
+            r_ids = st.out(out_ids, (size_t)B * k * 4);
+            r_dist = st.out(out_dist, (size_t)B * k * db);
+            r_cnt = st.out(out_count, (size_t)B * 4);
+            r_out = st.out(out, (size_t)B * sizeof(kdb_consensus));
+            r_sim = st.out(out_similarity, (size_t)B * k * 8);
+            return KDB_OK;
+        },
+        [&](unsigned char *d, hipStream_t s) {
+            return belief_dev_locked(idx, q.at<float>(d), B, k, ef, allow.at<uint64_t>(d), act.at<uint64_t>(d), flags & ~(uint32_t)KDB_SEARCH_FAIL_ON_DROP, r_ids.at<uint32_t>(d),
+                                     r_dist.at<float>(d), r_cnt.at<uint32_t>(d), r_out.at<kdb_consensus>(d), r_sim.at<double>(d), s);
+        });
 }
 
 extern "C" int kdb_index_build(kdb_index *idx, uint32_t count, const kdb_build_params *params) {
@@ -3023,27 +3023,21 @@ extern "C" int kdb_filter_eval(kdb_index *idx, const kdb_filter_term *terms, con
         return KDB_ERR_INVALID;
     }
     KDB_HIP(hipSetDevice(idx->device));
-    HostTurn turn(idx);
-    rc = filter_words_check("filter_eval", idx, words_per_list);
-    if (rc) return rc;
-    KdbCarver cv;
-    const size_t lb = (size_t)P * words_per_list * 8;
-    const size_t o_lists = cv.take(lb), o_card = cv.take((size_t)P * 4);
-    unsigned char *const d = turn.stage(cv.total());
-    if (!d) return turn.rc;
-    hipStream_t s = idx->stream;
-    {
-        KdbLaneGuard lane(idx, s);
-        if (lane.rc) return lane.rc;
-        rc = kdb_launch_filter_eval(idx, terms, prog_offsets, P, reinterpret_cast<uint64_t *>(d + o_lists), words_per_list,
-                                    reinterpret_cast<uint32_t *>(d + o_card), s);
-    }
-    turn.lk.unlock();
-    if (rc) return rc;
-    if (out_lists) KDB_HIP(hipMemcpyAsync(out_lists, d + o_lists, lb, hipMemcpyDeviceToHost, s));
-    if (out_card) KDB_HIP(hipMemcpyAsync(out_card, d + o_card, (size_t)P * 4, hipMemcpyDeviceToHost, s));
-    KDB_HIP(hipStreamSynchronize(s));
-    return KDB_OK;
+    KdbRegion lists, card;
+    KdbTurnOpt opt;
+    opt.launch_first = true; // (the programs are staged by the launcher itself, into the lane's scratch: nothing to copy in here)
+    return kdb_turn_call(
+        idx, opt,
+        [&](KdbStage &st) { // the kernel writes both whatever the caller asked for: an output nobody wants stays on the device
+            if (const int wrc = filter_words_check("filter_eval", idx, words_per_list)) return wrc;
+            const size_t lb = (size_t)P * words_per_list * 8, cb = (size_t)P * 4;
+            lists = out_lists ? st.out(out_lists, lb) : st.dev(lb);
+            card = out_card ? st.out(out_card, cb) : st.dev(cb);
+            return (int)KDB_OK;
+        },
+        [&](unsigned char *d, hipStream_t s) {
+            return kdb_launch_filter_eval(idx, terms, prog_offsets, P, lists.at<uint64_t>(d), words_per_list, card.at<uint32_t>(d), s);
+        });
 }
 
 // Engine.VSearch with a filter, from programs to answers: a COMPOSITION like the by-id calls.  The programs are evaluated into the
@@ -3099,33 +3093,12 @@ extern "C" int kdb_search_filtered(kdb_index *idx, const float *queries, uint32_
     KDB_HIP(hipMemcpyAsync(card.data(), d + o_card, (size_t)P * 4, hipMemcpyDeviceToHost, s));
     KDB_HIP(hipStreamSynchronize(s));
     if (out_card) memcpy(out_card, card.data(), (size_t)P * 4);
-    // the rule of the micro-batcher's takes_flat_scan (kektor_hip.hpp), per program
-    std::vector<uint8_t> route_p(P);
-    for (uint32_t p = 0; p < P; p++)
-        route_p[p] = card[p] == 0 ? 2 : (count > 0 && k <= KDB_FLAT_MAX_K && (double)card[p] < flat_selectivity * (double)count) ? 1 : 0;
     // order: walked queries (caller order) | scanned queries, program by program
-    std::vector<uint32_t> order, of_query, scan_progs, group_offsets(1, 0u);
-    order.reserve(B);
-    for (uint32_t b = 0; b < B; b++)
-        if (prog_of_query[b] == KDB_NO_FILTER || route_p[prog_of_query[b]] == 0) {
-            order.push_back(b);
-            of_query.push_back(prog_of_query[b]);
-        }
-    const uint32_t n_walk = (uint32_t)order.size();
-    {
-        std::vector<std::vector<uint32_t>> by_prog(P);
-        for (uint32_t b = 0; b < B; b++)
-            if (prog_of_query[b] != KDB_NO_FILTER && route_p[prog_of_query[b]] == 1) by_prog[prog_of_query[b]].push_back(b);
-        for (uint32_t p = 0; p < P; p++)
-            if (!by_prog[p].empty()) {
-                scan_progs.push_back(p);
-                order.insert(order.end(), by_prog[p].begin(), by_prog[p].end());
-                group_offsets.push_back((uint32_t)order.size() - n_walk);
-            }
-    }
-    const uint32_t n_scan = (uint32_t)order.size() - n_walk, n_run = n_walk + n_scan;
+    const KdbFilterRoute R = kdb_filter_route(card.data(), P, prog_of_query, B, count, k, flat_selectivity, KDB_FLAT_MAX_K);
+    const std::vector<uint32_t> &order = R.order, &of_query = R.of_query, &scan_progs = R.scan_progs, &group_offsets = R.group_offsets;
+    const uint32_t n_walk = R.n_walk, n_scan = R.n_scan, n_run = n_walk + n_scan;
     for (uint32_t b = 0; b < B; b++) { // what no launch writes: programs that match nothing
-        const uint8_t r = prog_of_query[b] == KDB_NO_FILTER ? 0 : route_p[prog_of_query[b]];
+        const uint8_t r = R.route_of_query(prog_of_query[b]);
         if (out_route) out_route[b] = r;
         if (r != 2) continue;
         out_count[b] = 0;

@@ -15,6 +15,7 @@
 #define KDB_FILTER_PLAN_H
 #include <stddef.h>
 #include <stdint.h>
+#include <vector>
 #include "../../include/kektor_hip.h"
 
 #if defined(__HIPCC__)
@@ -217,6 +218,49 @@ KDB_FILTER_HD inline uint32_t kdb_filter_run_words(const kdb_filter_term *terms,
 template <typename Cell>
 KDB_FILTER_HD inline bool kdb_filter_run(const kdb_filter_term *terms, uint32_t n, Cell cell) {
     return kdb_filter_run_words(terms, n, 1u, [&](uint32_t col, uint32_t) { return cell(col); }) != 0u;
+}
+
+// ---- routing of a filtered request (kdb_search_filtered, kdb_api.hip) -- host only ------------------------------------------------
+// The route of one program from its cardinality: 2 = it matches nothing (answered by the host), 1 = the exact scan, 0 = the walk.
+// The rule of the micro-batcher's takes_flat_scan (kektor_hip.hpp), per program; flat_max_k is the exact scan's limit (KDB_FLAT_MAX_K).
+inline uint8_t kdb_filter_route_of(uint32_t card, uint32_t count, uint32_t k, double flat_selectivity, uint32_t flat_max_k) {
+    return card == 0 ? 2 : (count > 0 && k <= flat_max_k && (double)card < flat_selectivity * (double)count) ? 1 : 0;
+}
+// The plan of one request: the order the queries are staged and run in -- the walked ones (no filter, or a program on route 0) in
+// caller order, then the scanned ones program by program, in caller order inside a program -- and what the launches need beside it.
+struct KdbFilterRoute {
+    std::vector<uint8_t> route_p;        // [P] the route of every program
+    std::vector<uint32_t> order;         // [n_walk + n_scan] caller index of the i-th staged query
+    std::vector<uint32_t> of_query;      // [n_walk] the program (or KDB_NO_FILTER) of every walked query
+    std::vector<uint32_t> scan_progs;    // the programs that have scanned queries, ascending
+    std::vector<uint32_t> group_offsets; // [scan_progs.size() + 1] where each one's queries start among the scanned
+    uint32_t n_walk = 0, n_scan = 0;
+    uint8_t route_of_query(uint32_t prog) const { return prog == KDB_NO_FILTER ? 0 : route_p[prog]; }
+};
+inline KdbFilterRoute kdb_filter_route(const uint32_t *card, uint32_t P, const uint32_t *prog_of_query, uint32_t B, uint32_t count, uint32_t k,
+                                       double flat_selectivity, uint32_t flat_max_k) {
+    KdbFilterRoute R;
+    R.route_p.resize(P);
+    for (uint32_t p = 0; p < P; p++) R.route_p[p] = kdb_filter_route_of(card[p], count, k, flat_selectivity, flat_max_k);
+    R.group_offsets.assign(1, 0u);
+    R.order.reserve(B);
+    for (uint32_t b = 0; b < B; b++)
+        if (R.route_of_query(prog_of_query[b]) == 0) {
+            R.order.push_back(b);
+            R.of_query.push_back(prog_of_query[b]);
+        }
+    R.n_walk = (uint32_t)R.order.size();
+    std::vector<std::vector<uint32_t>> by_prog(P);
+    for (uint32_t b = 0; b < B; b++)
+        if (R.route_of_query(prog_of_query[b]) == 1) by_prog[prog_of_query[b]].push_back(b);
+    for (uint32_t p = 0; p < P; p++)
+        if (!by_prog[p].empty()) {
+            R.scan_progs.push_back(p);
+            R.order.insert(R.order.end(), by_prog[p].begin(), by_prog[p].end());
+            R.group_offsets.push_back((uint32_t)R.order.size() - R.n_walk);
+        }
+    R.n_scan = (uint32_t)R.order.size() - R.n_walk;
+    return R;
 }
 
 #endif

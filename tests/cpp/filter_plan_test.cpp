@@ -4,13 +4,15 @@
 // list exactly once (walked word by word the way the kernel walks them, except at 2^30 - 1 ids where the tiles are summed), program
 // chunks cover every program exactly once, the validation refuses what the header says it refuses, the staged layout's offsets
 // are exact in 64 bits, the passes' LDS cells are disjoint and fit, and kdb_filter_run[_words] -- the ONE statement of a program's
-// value -- against a few hand-evaluated programs, W ids at once against one id at a time.
+// value -- against a few hand-evaluated programs, W ids at once against one id at a time.  And the routing plan of a filtered request
+// (kdb_filter_route_of, kdb_filter_route): the rule at its edges, the plan against a brute-force restatement.
 #include "kdb_filter_plan.h"
 
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <utility>
 #include <vector>
 
 #define CHECK(cond)                                                        \
@@ -248,6 +250,82 @@ int main() {
                     CHECK(((m >> w) & 1u) == (uint32_t)kdb_filter_run(p.data(), (uint32_t)p.size(), [&](uint32_t c) { return cells(c, w); }));
             }
         }
+    }
+    // ---- the route of one program (the rule of takes_flat_scan, kektor_hip.hpp): 2 = empty, 1 = exact scan, 0 = walk
+    {
+        const uint32_t MAXK = 1024u; // KDB_FLAT_MAX_K
+        CHECK(kdb_filter_route_of(0, 1000, 10, 0.5, MAXK) == 2 && kdb_filter_route_of(0, 0, 10, 1.0, MAXK) == 2 && kdb_filter_route_of(0, 1000, 2000, 0.0, MAXK) == 2);
+        // the comparison is strict: card == ceil(f * count) walks, one below it scans -- with f * count whole and not whole
+        for (const auto &fc : {std::pair<double, uint32_t>{0.25, 1000u}, {0.1, 1003u}, {0.5, 7u}, {1.0 / 3.0, 100u}, {0.999, 123457u}}) {
+            const uint32_t edge = (uint32_t)ceil(fc.first * (double)fc.second);
+            CHECK(edge >= 2);
+            CHECK(kdb_filter_route_of(edge, fc.second, 10, fc.first, MAXK) == 0);
+            CHECK(kdb_filter_route_of(edge - 1, fc.second, 10, fc.first, MAXK) == 1);
+        }
+        CHECK(kdb_filter_route_of(5, 1000, 1024, 0.5, MAXK) == 1 && kdb_filter_route_of(5, 1000, 1025, 0.5, MAXK) == 0); // k at and above the scan's limit
+        for (uint32_t card : {1u, 2u, 999u, 1000u}) CHECK(kdb_filter_route_of(card, 1000, 10, 0.0, MAXK) == 0);          // f == 0: nothing scans
+        CHECK(kdb_filter_route_of(999, 1000, 10, 1.0, MAXK) == 1 && kdb_filter_route_of(1000, 1000, 10, 1.0, MAXK) == 0); // f == 1: all but the full list
+        CHECK(kdb_filter_route_of(1, 0, 10, 1.0, MAXK) == 0 && kdb_filter_route_of(0, 0, 10, 1.0, MAXK) == 2);            // count == 0
+    }
+    // ---- the plan of a request against a brute-force restatement, a few thousand small random cases
+    {
+        unsigned long long x = 0x9e3779b97f4a7c15ull;
+        auto rnd = [&](uint32_t n) { x ^= x << 13, x ^= x >> 7, x ^= x << 17; return (uint32_t)((x >> 33) % n); };
+        uint32_t n_nothing = 0, n_both = 0;
+        for (int round = 0; round < 4000; round++) {
+            const uint32_t P = 1 + rnd(6), B = 1 + rnd(40), count = rnd(8) ? 1 + rnd(50) : 0, k = rnd(10) ? 1 + rnd(20) : 1020 + rnd(10);
+            const double f = rnd(6) == 0 ? 0.0 : rnd(6) == 0 ? 1.0 : (double)rnd(1000) / 1000.0;
+            std::vector<uint32_t> card(P), prog(B);
+            for (uint32_t &c : card) c = rnd(3) == 0 ? 0 : rnd(count + 1);
+            const uint32_t mode = rnd(8); // now and then: no query filtered, or every query on one program
+            for (uint32_t &p : prog) p = mode == 0 ? KDB_NO_FILTER : mode == 1 ? 0 : rnd(4) == 0 ? KDB_NO_FILTER : rnd(P);
+            const KdbFilterRoute R = kdb_filter_route(card.data(), P, prog.data(), B, count, k, f, 1024u);
+            // the restatement: every query's route, straight from the rule
+            CHECK(R.route_p.size() == P);
+            std::vector<uint8_t> rq(B);
+            for (uint32_t b = 0; b < B; b++) {
+                rq[b] = prog[b] == KDB_NO_FILTER ? 0 : card[prog[b]] == 0 ? 2 : (count > 0 && k <= 1024u && (double)card[prog[b]] < f * (double)count) ? 1 : 0;
+                CHECK(R.route_of_query(prog[b]) == rq[b]);
+                if (prog[b] != KDB_NO_FILTER) CHECK(R.route_p[prog[b]] == rq[b]);
+            }
+            // order: a permutation of exactly the queries whose route is not 2
+            std::vector<uint8_t> seen(B, 0);
+            for (uint32_t b : R.order) {
+                CHECK(b < B && rq[b] != 2 && seen[b]++ == 0);
+            }
+            uint32_t n_run = 0;
+            for (uint32_t b = 0; b < B; b++) n_run += rq[b] != 2;
+            CHECK(R.order.size() == n_run && R.n_walk + R.n_scan == n_run);
+            // the first n_walk: the walked queries in caller order, with their program
+            std::vector<uint32_t> walked;
+            for (uint32_t b = 0; b < B; b++)
+                if (rq[b] == 0) walked.push_back(b);
+            CHECK(R.n_walk == walked.size() && R.of_query.size() == walked.size());
+            for (uint32_t i = 0; i < R.n_walk; i++) CHECK(R.order[i] == walked[i] && R.of_query[i] == prog[walked[i]]);
+            // the rest: grouped by ascending program, caller order inside a group, one entry of group_offsets per non-empty scanned program
+            std::vector<uint32_t> progs;
+            for (uint32_t p = 0; p < P; p++) {
+                bool any = false;
+                for (uint32_t b = 0; b < B; b++) any = any || (rq[b] == 1 && prog[b] == p);
+                if (any) progs.push_back(p);
+            }
+            CHECK(R.scan_progs == progs);
+            CHECK(R.group_offsets.size() == progs.size() + 1 && R.group_offsets.front() == 0 && R.group_offsets.back() == R.n_scan);
+            for (size_t g = 0; g < progs.size(); g++) {
+                CHECK(R.group_offsets[g] < R.group_offsets[g + 1]);
+                std::vector<uint32_t> members;
+                for (uint32_t b = 0; b < B; b++)
+                    if (rq[b] == 1 && prog[b] == progs[g]) members.push_back(b);
+                CHECK(R.group_offsets[g + 1] - R.group_offsets[g] == members.size());
+                for (size_t j = 0; j < members.size(); j++) CHECK(R.order[R.n_walk + R.group_offsets[g] + j] == members[j]);
+            }
+            if (n_run == 0) { // a plan with nothing to run
+                CHECK(R.n_walk + R.n_scan == 0 && R.order.empty() && R.scan_progs.empty() && R.group_offsets.size() == 1);
+                n_nothing++;
+            }
+            n_both += R.n_walk && R.n_scan;
+        }
+        CHECK(n_nothing >= 20 && n_both >= 200); // the cases the assertions above are about did occur
     }
     printf("ok\n");
     return 0;

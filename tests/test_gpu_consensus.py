@@ -286,6 +286,45 @@ def ctr(idx):
     return c["n_dist"], c["n_hops"], c["n_tied"], c["n_dropped"]
 
 
+def test_belief_without_similarities_host_form_equals_dev_form():
+    """out_similarity == NULL (the Python wrapper always asks for the similarities): the host-pointer call against the _dev call on
+    the same inputs, bit for bit, with and without the allow list and the active list; the records equal those of the call that
+    does return similarities"""
+    import torch
+    from test_gpu_search_by_id import setup
+    from kektordb_amd.index import CONSENSUS_DTYPE, _ptr
+    S = setup("A")
+    idx = S.idx
+    B, k, ef = 5, 4, 100
+    d64 = S.prec == I8
+    flags = idx._by_id_flags(False, d64, False, False)
+    Q = np.ascontiguousarray(belief_queries(S, 47)[:B])
+    act = np.full((S.n >> 6) + 1, 0x6db6db6db6db6db6, dtype=np.uint64)      # two ids of three active
+    even = np.ascontiguousarray(S.even, dtype=np.uint64)
+    d_q = torch.from_numpy(Q).cuda()
+    for allow, active in ((None, None), (even, None), (None, act), (even, act)):
+        ids = np.zeros((B, k), dtype=np.uint32)
+        dist = np.full((B, k), np.inf, dtype=np.float64 if d64 else np.float32)
+        cnt = np.zeros(B, dtype=np.uint32)
+        rec = np.zeros(B, dtype=CONSENSUS_DTYPE)
+        assert idx.L.kdb_belief_batch(idx.h, _ptr(Q), B, k, ef, _ptr(allow), _ptr(active), flags, _ptr(ids), _ptr(dist), _ptr(cnt), _ptr(rec), None) == 0
+        oi = torch.full((B, k), -1, dtype=torch.int32, device="cuda")
+        od = torch.full((B, k), -7.0, dtype=torch.float64 if d64 else torch.float32, device="cuda")
+        oc = torch.full((B,), -1, dtype=torch.int32, device="cuda")
+        orec = torch.zeros((B, 32), dtype=torch.uint8, device="cuda")
+        d_al = None if allow is None else torch.from_numpy(allow.view(np.int64)).cuda()
+        d_act = None if active is None else torch.from_numpy(active.view(np.int64)).cuda()
+        torch.cuda.synchronize()
+        idx.belief_dev(d_q, k, ef, oi, od, oc, orec, None, d_al, d_act, dist64=d64)
+        idx.sync()
+        tag = (allow is not None, active is not None)
+        assert same(oi.cpu().numpy().view(np.uint32), ids) and same(od.cpu().numpy(), dist) and same(oc.cpu().numpy().view(np.uint32), cnt), tag
+        assert same(orec.cpu().numpy().view(CONSENSUS_DTYPE).ravel(), rec), tag
+        full = idx.belief(Q, k, ef, allow, active, dist64=d64)
+        assert same(full[0], ids) and same(full[1], dist) and same(full[2], cnt) and same(full[3], rec), tag
+        assert (cnt > 0).all() and (active is None or (rec["n_active"] < rec["n_found"]).any()), tag
+
+
 def belief_queries(S, seed):
     rng = np.random.default_rng(seed)
     return (S.wide[rng.choice(S.live, 203, replace=False)] + np.float32(0.05) * rng.standard_normal((203, S.dim)).astype(np.float32)).astype(np.float32)

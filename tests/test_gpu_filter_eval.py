@@ -174,6 +174,12 @@ def test_raw_programs(hip, big):
     check(h_lists, h_card, want, words + 3, count)
     none, only_card = big["idx"].filter_eval(arr, want_lists=False)
     assert none is None and np.array_equal(only_card, h_card)
+    # ... and lists without cardinalities (out_card == NULL; the Python wrapper always asks for them): bit for bit the _dev lists
+    from kektordb_amd.index import _ptr, pack_programs
+    terms, offs = pack_programs(arr)
+    only_lists = np.full((len(arr), words), 0xee, dtype=np.uint64)
+    assert big["idx"].L.kdb_filter_eval(big["idx"].h, _ptr(terms), _ptr(offs), len(arr), _ptr(only_lists), words, None) == 0
+    assert np.array_equal(only_lists, lists)
 
 
 def test_many_columns_per_chunk(hip):
