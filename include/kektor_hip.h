@@ -772,6 +772,9 @@ KDB_API int kdb_test_select_neighbors(kdb_index *idx, uint32_t n_lists, uint32_t
  * in_count: [G][B]; id_base: NULL or [G] offsets added to shard g's (local, 1-based) ids so that
  * global id = id_base[g] + local id (shard g owns the contiguous id range that starts at id_base[g]+1).
  * Ordering: ascending raw L2 sum, or descending dot for cosine/f32, ties by global id.
+ * A shard's count may carry KDB_COUNT_TIED (it searched with KDB_SEARCH_TIE_FLAG): the length of its list is
+ * in_count & KDB_COUNT_MASK, and out_count[b] carries the bit when the count of ANY shard did for query b (every
+ * merge entry point below does the same).  Behind out_count[b] & KDB_COUNT_MASK: id 0, distance +Inf.
  * kdb_merge_topk takes host pointers (host-side glue of the shim); *_dev device pointers.           */
 KDB_API int kdb_merge_topk(uint32_t metric, uint32_t precision, uint32_t G, uint32_t B, uint32_t k,
                    const uint32_t *in_ids, const float *in_dist, const uint32_t *in_count,
@@ -805,7 +808,11 @@ KDB_API int kdb_merge_topk_packed_f64_dev(kdb_index *idx, uint32_t G, uint32_t B
  * GPU), ONE RCCL all-gather of the per-shard top-k blocks over xGMI, merge under the total order (distance, global id).
  * allow_bits: NULL or a dense bitset over GLOBAL ids (allow_words uint64 words), sliced per shard by the library; the
  * per-shard semantics are those of kdb_search_batch (a list that allows nothing in a shard yields nothing from it).
- * Host pointers; ids returned are global.  kdb_sharded_flat_scan_batch: the exact scan, same exchange.
+ * Host pointers; ids returned are global.  kdb_sharded_flat_scan_batch: the exact scan, same exchange; as for
+ * kdb_flat_scan_batch a list that names NO id at all means no filter, but a list that names ids, none of them in shard g,
+ * brings nothing back from shard g (the emptiness that counts is the whole list's, never a slice's).
+ * flags go to every shard as they are: with KDB_SEARCH_TIE_FLAG out_count[b] carries KDB_COUNT_TIED when the walk of ANY
+ * shard did for query b (mask with KDB_COUNT_MASK); KDB_SEARCH_HEAP_ORDER re-walks the tied queries shard by shard.
  * RCCL (librccl.so.1) is loaded at the first kdb_cluster_create.                                                 */
 typedef struct kdb_cluster kdb_cluster;
 KDB_API int kdb_cluster_create(kdb_index *const *shards, const uint32_t *id_base, uint32_t n_shards, kdb_cluster **out);

@@ -337,8 +337,37 @@ struct CallPlan { // sizes of one call (shared by the preparation and the enqueu
     uint32_t G, nd, spd;
     bool i8, out64;
     size_t bk, L, o_ids, o_dist, o_cnt, qbytes, allow_g_bytes, out_span, h_allow, h_out;
+    std::vector<unsigned char> mute; // [G] exact scan under a list: the shard owns none of the ids the list names (see mute_shards)
 };
 static inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// is any of the bits lo .. hi (inclusive) of a dense list of `words` words set?
+static bool any_bit(const uint64_t *a, size_t words, uint64_t lo, uint64_t hi) {
+    if (words == 0 || lo > hi || (lo >> 6) >= words) return false;
+    if ((hi >> 6) >= words) hi = (uint64_t)words * 64u - 1u;
+    for (size_t w = (size_t)(lo >> 6); w <= (size_t)(hi >> 6); w++) {
+        uint64_t v = a[w];
+        if (w == (size_t)(lo >> 6)) v &= ~0ull << (lo & 63u);
+        if (w == (size_t)(hi >> 6) && (hi & 63u) != 63u) v &= (2ull << (hi & 63u)) - 1ull;
+        if (v) return true;
+    }
+    return false;
+}
+
+// The exact scan takes a list WITHOUT ids for "no filter" (allowList.IsEmpty(), vector_index.go:130), and the scan of one shard
+// sees only its slice: a list that names ids of the corpus, none of them in shard g, would reach that shard as "no filter" and
+// bring back all of its rows.  Such a shard is MUTE for the call: it is not scanned and its block carries count 0.  A list
+// that names nothing at all stays what it is for the reference, no filter, on every shard.  (The graph walk answers a list
+// without ids with nothing, hnsw_index.go:343-366: its slices need no such care.)  One pass over the caller's list, on the host.
+static void mute_shards(const kdb_cluster *c, const uint64_t *allow_bits, size_t allow_words, std::vector<unsigned char> *mute) {
+    const size_t G = c->shards.size();
+    mute->assign(G, 0);
+    bool any = false;
+    for (size_t w = 0; w < allow_words && !any; w++) any = allow_bits[w] != 0;
+    if (!any) return;
+    for (size_t g = 0; g < G; g++)
+        (*mute)[g] = any_bit(allow_bits, allow_words, (uint64_t)c->id_base[g] + 1u, (uint64_t)c->id_base[g] + c->shards[g]->count) ? 0 : 1;
+}
 
 // Everything of a call that may ALLOCATE or wait for a stream: done with the lane held but WITHOUT the enqueue lock, so a
 // batch larger than any before, or a 12.5 MB allow list, holds up nobody else's enqueue.
@@ -427,15 +456,20 @@ static int sharded_enqueue(kdb_cluster *c, int li, const CallPlan &pl, bool flat
         kdb_index *idx = c->shards[g];
         KDB_HIP(hipSetDevice(c->devs[g / spd].device));
         const uint64_t *d_allow = nullptr;
+        uint32_t *blk = d.d_send + (size_t)ls * L;
+        if (have_allow && ls == 0) // (before a mute shard is passed over: the device's other shards slice this copy)
+            KDB_HIP(hipMemcpyAsync(d.d_allow_g, lane.h_pin + pl.h_allow, pl.allow_g_bytes, hipMemcpyHostToDevice, d.stream));
+        if (!pl.mute.empty() && pl.mute[g]) { // no answers from this shard: the merge reads nothing behind a count of 0
+            KDB_HIP(hipMemsetAsync(blk + pl.o_cnt, 0, (size_t)B * 4, d.stream));
+            continue;
+        }
         if (have_allow) {
-            if (ls == 0) KDB_HIP(hipMemcpyAsync(d.d_allow_g, lane.h_pin + pl.h_allow, pl.allow_g_bytes, hipMemcpyHostToDevice, d.stream));
             const size_t n_out = ((size_t)idx->count >> 6) + 1;
             hipLaunchKernelGGL(slice_allow_kernel, dim3((unsigned)((n_out + 255) / 256)), dim3(256), 0, d.stream, d.d_allow_g, allow_words, c->id_base[g],
                                idx->count, d.d_allow[ls]);
             KDB_HIP(hipGetLastError());
             d_allow = d.d_allow[ls];
         }
-        uint32_t *blk = d.d_send + (size_t)ls * L;
         rc = flat ? kdb_flat_scan_batch_dev(idx, d.d_q, B, k, d_allow, sflags, blk + pl.o_ids, reinterpret_cast<float *>(blk + pl.o_dist), blk + pl.o_cnt, d.stream)
                   : kdb_search_batch_dev(idx, d.d_q, B, k, ef, d_allow, sflags, blk + pl.o_ids, reinterpret_cast<float *>(blk + pl.o_dist), blk + pl.o_cnt, d.stream);
         if (rc) return rc;
@@ -528,6 +562,7 @@ static int sharded_call(kdb_cluster *c, bool flat, const float *queries, uint32_
     }
     Lane &lane = c->lanes[li];
     std::lock_guard<std::mutex> hold(lane.mu); // the lane's buffers belong to this call until its answers are home
+    if (flat && allow_bits) mute_shards(c, allow_bits, allow_words, &pl.mute); // (reads shard counts as sharded_prepare does)
     int rc = sharded_prepare(c, li, pl, queries, allow_bits);
     if (rc) return rc; // nothing was queued
     bool inconsistent = false;

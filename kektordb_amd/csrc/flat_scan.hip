@@ -1648,16 +1648,20 @@ merge_topk_kernel(int negate, uint32_t G, uint32_t B, uint32_t k, const uint32_t
                   uint32_t *out_ids, OT *out_dist, uint32_t *out_count) {
     const uint32_t q = blockIdx.x;
     const int lane = kdb_lane();
-    uint32_t total = 0;
+    // a shard's count may carry KDB_COUNT_TIED (bit 31, KDB_SEARCH_TIE_FLAG): not part of the length; the merged count carries
+    // the bit when any shard's did
+    uint32_t total = 0, tied = 0;
     for (uint32_t g = 0; g < G; g++) {
-        uint32_t c = in_count[g * stride_c + q];
+        const uint32_t raw = in_count[g * stride_c + q];
+        const uint32_t c = raw & KDB_COUNT_MASK;
+        tied |= raw & KDB_COUNT_TIED;
         total += c < k ? c : k;
     }
     const uint32_t nout = total < k ? total : k;
     const uint32_t n = G * k;
     for (uint32_t e = (uint32_t)lane; e < n; e += 64) {
         const uint32_t g = e / k, i = e % k;
-        uint32_t cg = in_count[g * stride_c + q];
+        uint32_t cg = in_count[g * stride_c + q] & KDB_COUNT_MASK;
         if (cg > k) cg = k;
         if (i >= cg) continue;
         const DT d = in_dist[g * stride_d + (size_t)q * k + i];
@@ -1665,7 +1669,7 @@ merge_topk_kernel(int negate, uint32_t G, uint32_t B, uint32_t k, const uint32_t
         const DT key = negate ? -d : d;
         uint32_t rank = 0;
         for (uint32_t g2 = 0; g2 < G; g2++) {
-            uint32_t c2 = in_count[g2 * stride_c + q];
+            uint32_t c2 = in_count[g2 * stride_c + q] & KDB_COUNT_MASK;
             if (c2 > k) c2 = k;
             const size_t oi = g2 * stride_i + (size_t)q * k, od = g2 * stride_d + (size_t)q * k;
             const uint32_t b2 = id_base ? id_base[g2] : 0u;
@@ -1685,7 +1689,7 @@ merge_topk_kernel(int negate, uint32_t G, uint32_t B, uint32_t k, const uint32_t
         out_ids[(size_t)q * k + i] = 0u;
         out_dist[(size_t)q * k + i] = (OT)INFINITY;
     }
-    if (lane == 0) out_count[q] = nout;
+    if (lane == 0) out_count[q] = nout | tied;
 }
 
 } // namespace

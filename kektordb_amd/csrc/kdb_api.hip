@@ -2707,8 +2707,10 @@ extern "C" int kdb_merge_topk(uint32_t metric, uint32_t precision, uint32_t G, u
     std::vector<E> buf;
     for (uint32_t q = 0; q < B; q++) {
         buf.clear();
+        uint32_t tied = 0; // bit 31 of a shard's count (KDB_COUNT_TIED) is not part of the length; the merged count carries it
         for (uint32_t g = 0; g < G; g++) {
-            uint32_t c = in_count[(size_t)g * B + q];
+            uint32_t c = in_count[(size_t)g * B + q] & KDB_COUNT_MASK;
+            tied |= in_count[(size_t)g * B + q] & KDB_COUNT_TIED;
             if (c > k) c = k;
             for (uint32_t i = 0; i < c; i++) {
                 const size_t off = ((size_t)g * B + q) * k + i;
@@ -2721,7 +2723,7 @@ extern "C" int kdb_merge_topk(uint32_t metric, uint32_t precision, uint32_t G, u
             out_ids[(size_t)q * k + i] = i < n ? buf[i].id : 0u;
             out_dist[(size_t)q * k + i] = i < n ? buf[i].d : INFINITY;
         }
-        out_count[q] = n;
+        out_count[q] = n | tied;
     }
     return KDB_OK;
 }
@@ -2738,8 +2740,10 @@ extern "C" int kdb_merge_topk_f64(uint32_t G, uint32_t B, uint32_t k, const uint
     std::vector<E> buf;
     for (uint32_t q = 0; q < B; q++) {
         buf.clear();
+        uint32_t tied = 0; // bit 31 of a shard's count (KDB_COUNT_TIED) is not part of the length; the merged count carries it
         for (uint32_t g = 0; g < G; g++) {
-            uint32_t c = in_count[(size_t)g * B + q];
+            uint32_t c = in_count[(size_t)g * B + q] & KDB_COUNT_MASK;
+            tied |= in_count[(size_t)g * B + q] & KDB_COUNT_TIED;
             if (c > k) c = k;
             for (uint32_t i = 0; i < c; i++) {
                 const size_t off = ((size_t)g * B + q) * k + i;
@@ -2752,7 +2756,7 @@ extern "C" int kdb_merge_topk_f64(uint32_t G, uint32_t B, uint32_t k, const uint
             out_ids[(size_t)q * k + i] = i < n ? buf[i].id : 0u;
             out_dist[(size_t)q * k + i] = i < n ? buf[i].d : (double)INFINITY;
         }
-        out_count[q] = n;
+        out_count[q] = n | tied;
     }
     return KDB_OK;
 }

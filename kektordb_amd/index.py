@@ -859,8 +859,10 @@ class HipIndex:
                 "similarities": [float(sim[0, i]) for i in found]}
 
 
-def merge_topk(metric: int, ids, dist, count, k: int, id_base=None, precision: int = F32):
-    """Host shard merge through the C ABI (kdb_merge_topk): ids/dist [G,B,k], count [G,B], id_base [G]."""
+def merge_topk(metric: int, ids, dist, count, k: int, id_base=None, precision: int = F32, out=None):
+    """Host shard merge through the C ABI (kdb_merge_topk): ids/dist [G,B,k], count [G,B], id_base [G].
+    A count may carry COUNT_TIED (bit 31): it is not part of the length, and the merged count carries it when a shard's did.
+    out: (ids [B,k] uint32, dist [B,k] float32 -- float64 for int8 doubles --, count [B] uint32) to write into instead of new arrays."""
     L = _lib.load()
     ids = np.ascontiguousarray(ids, dtype=np.uint32)
     count = np.ascontiguousarray(count, dtype=np.uint32)
@@ -870,15 +872,15 @@ def merge_topk(metric: int, ids, dist, count, k: int, id_base=None, precision: i
         # (chosen by the index's precision, not by the array's dtype alone: a float64 array of an f32 cosine index holds DOTS --
         # it is cast to float32 and merged on the key -dot below, as before)
         dist = np.ascontiguousarray(dist, dtype=np.float64)
-        o_ids = np.zeros((B, k), dtype=np.uint32)
-        o_dist = np.zeros((B, k), dtype=np.float64)
-        o_cnt = np.zeros(B, dtype=np.uint32)
+        o_ids, o_dist, o_cnt = out if out is not None else (np.zeros((B, k), dtype=np.uint32), np.zeros((B, k), dtype=np.float64),
+                                                            np.zeros(B, dtype=np.uint32))
+        assert o_ids.dtype == np.uint32 and o_dist.dtype == np.float64 and o_cnt.dtype == np.uint32 and o_dist.shape == (B, k)
         check(L.kdb_merge_topk_f64(G, B, k, _ptr(ids), _ptr(dist), _ptr(count), _ptr(base), _ptr(o_ids), _ptr(o_dist), _ptr(o_cnt)), "kdb_merge_topk_f64")
         return o_ids, o_dist, o_cnt
     dist = np.ascontiguousarray(dist, dtype=np.float32)
-    o_ids = np.zeros((B, k), dtype=np.uint32)
-    o_dist = np.zeros((B, k), dtype=np.float32)
-    o_cnt = np.zeros(B, dtype=np.uint32)
+    o_ids, o_dist, o_cnt = out if out is not None else (np.zeros((B, k), dtype=np.uint32), np.zeros((B, k), dtype=np.float32),
+                                                        np.zeros(B, dtype=np.uint32))
+    assert o_ids.dtype == np.uint32 and o_dist.dtype == np.float32 and o_cnt.dtype == np.uint32 and o_dist.shape == (B, k)
     check(L.kdb_merge_topk(metric, precision, G, B, k, _ptr(ids), _ptr(dist), _ptr(count), _ptr(base), _ptr(o_ids),
                            _ptr(o_dist), _ptr(o_cnt)), "kdb_merge_topk")
     return o_ids, o_dist, o_cnt
