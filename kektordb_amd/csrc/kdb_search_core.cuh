@@ -99,6 +99,14 @@ __device__ __forceinline__ uint32_t uni(uint32_t x) { return (uint32_t)__builtin
 __device__ __forceinline__ float unif(float x) {
     return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, x)));
 }
+// The lane index computed AGAIN, where it stands: a rare path (VisHash::migrate) that used the kernel's one `lane` -- or a loop count
+// derived from it -- kept those values alive across the whole hop loop, in scratch at three waves per SIMD, and their reloads were
+// placed in the blocks every hop runs.  Two instructions inside the rare path instead (volatile: neither merged with kdb_lane() nor hoisted).
+__device__ __forceinline__ uint32_t kdb_lane_again() {
+    uint32_t l;
+    asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
+    return l;
+}
 __device__ __forceinline__ float readlane_f(float x, uint32_t l) {
     return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, x), (int)l));
 }
@@ -1150,8 +1158,9 @@ struct VisBitset {
     bool record;
     static constexpr bool kHash = false;
     __device__ __forceinline__ bool overflowed() const { return false; }
+    template <bool AGAIN = false> // AGAIN: from a rare path of the hop loop (kdb_lane_again)
     __device__ __forceinline__ void clear_all() {
-        const uint32_t lane = (uint32_t)kdb_lane();
+        const uint32_t lane = AGAIN ? kdb_lane_again() : (uint32_t)kdb_lane();
         uint4 z = make_uint4(0, 0, 0, 0);
         uint4 *v4 = reinterpret_cast<uint4 *>(bits);
         const uint32_t n4 = words >> 2;
@@ -1198,7 +1207,9 @@ struct VisBitset {
     }
 };
 
-struct VisHash { // hybrid: LDS hash set that migrates into the wave's HBM bitset if it fills up
+// RARE: migrate() holds nothing of the walk's own registers (the three-wave planes kernel, whose hop loop has none to spare)
+template <bool RARE = false>
+struct VisHashT { // hybrid: LDS hash set that migrates into the wave's HBM bitset if it fills up
     uint32_t *tab;   // LDS, `size` words, 0 = empty, else node id
     uint32_t full_size; // words available (power of two); upper layers (ef = 1: a few dozen ids) use and clear 1024 of them
     uint32_t size;   // power of two
@@ -1228,8 +1239,8 @@ struct VisHash { // hybrid: LDS hash set that migrates into the wave's HBM bitse
     }
     __device__ __forceinline__ void end_layer() {}
     __device__ __forceinline__ void migrate() { // rare: the set outgrew LDS -> continue on the HBM bitset
-        const uint32_t lane = (uint32_t)kdb_lane();
-        bs.clear_all();
+        const uint32_t lane = RARE ? kdb_lane_again() : (uint32_t)kdb_lane();
+        bs.template clear_all<RARE>();
         for (uint32_t i = lane; i < size; i += 64) {
             const uint32_t id = tab[i];
             if (id) atomicOr(&bs.bits[id >> 5], 1u << (id & 31));
@@ -1254,6 +1265,7 @@ struct VisHash { // hybrid: LDS hash set that migrates into the wave's HBM bitse
         return fresh;
     }
 };
+using VisHash = VisHashT<false>;
 
 // ------------------------------------------------------------------------------------------------
 // Traversal-only candidates: soft-deleted nodes and a non-allowed entry point are pushed on the reference's candidate
@@ -1697,6 +1709,7 @@ __device__ void search_layer(const KdbView &v, const WaveLds &s, BeamT &b, VisT 
     const int lane = kdb_lane();
     b.reset(ef);
     constexpr bool WK = BeamT::kWide; // int8: 64-bit distance keys (the reference orders float64 distances)
+    constexpr bool LEAN = PL != 0 && BeamT::kSlots == 1; // (search_kernel.cuh: kdb_hop_loop_lean -- this is the one-wave walk)
     NrListT<WK> nr;
     nr.bind(s);
     vis.begin_layer(level > 0);
@@ -1733,6 +1746,9 @@ __device__ void search_layer(const KdbView &v, const WaveLds &s, BeamT &b, VisT 
         uint32_t cur;
         if (!pop_candidate(b, nr, ef, cur)) break;
         if (cur - 1u >= v.count) continue; // never an address from an id that names no node (a wrong key may cost recall, never a fault)
+        // (the three-wave planes kernel: the popped id is wave-uniform -- said so, the list's base is a scalar pair and a lane's word a 32-bit offset from
+        // it; left to itself the compiler kept adj0 + 4 * lane as a 64-bit vector address across the hop loop, in scratch at three waves)
+        if constexpr (LEAN) cur = uni(cur);
         const uint32_t *adj = v.adj0 + (size_t)cur * v.deg0;
         if (level > 0) { // the node's level and its first upper slot are requested together (one wait, not two dependent ones)
             const int lv = (int)v.levels[cur];
@@ -1742,7 +1758,9 @@ __device__ void search_layer(const KdbView &v, const WaveLds &s, BeamT &b, VisT 
         }
         ctr.n_hops++;
         KDB_T(const unsigned long long tq0 = __builtin_readcyclecounter(); if (level == 0) ctr.t_pop += tq0 - tq_a;)
-        const uint32_t nbx = adj[(uint32_t)lane < deg ? (uint32_t)lane : deg - 1u]; // (unconditional: a lane past the list re-reads its last word)
+        // (... and the lane's index into the list is made here, kdb_lane_again: not a register pair that waits in scratch from hop to hop)
+        const uint32_t li = LEAN ? kdb_lane_again() : (uint32_t)lane;
+        const uint32_t nbx = adj[li < deg ? li : deg - 1u]; // (unconditional: a lane past the list re-reads its last word)
         const uint32_t nb = (uint32_t)lane < deg ? nbx : 0u;
         KDB_T(asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); const unsigned long long tq_v = __builtin_readcyclecounter();)
         // visited test-and-set (:2539-2542)

@@ -417,7 +417,8 @@ __global__ void __launch_bounds__(256) walk_planes_kernel(const float *__restric
     for (int o = 8; o >= 1; o >>= 1) {
         sd += __shfl_xor(sd, o, 64);
         sx += __shfl_xor(sx, o, 64);
-        bad = bad || __shfl_xor((int)bad, o, 64) != 0;
+        const int other = __shfl_xor((int)bad, o, 64); // (not under `bad ||`: a lane that skips the exchange answers its partner with 0)
+        bad = bad || other != 0;
     }
     if (act && t == 0u) {
         const double e = (sqrt(sd) + 0x1p-18 * sqrt(sx)) * (1.0 + 0x1p-30); // (the double roundings of the sums and roots)

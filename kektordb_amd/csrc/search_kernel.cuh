@@ -60,7 +60,7 @@ __device__ __forceinline__ size_t q_lds_bytes(uint32_t ld) {
 #define KDB_PLANES_MINW 3 // the planes kernel with the one-slot beam (ef <= 64): 12 walks per CU instead of 8.  It is bound by the
                           // bytes it keeps in flight, not by HBM bandwidth; measured at 1M x 768, ef 60, 32768 queries, alternating runs:
                           // 7.31 (parent) / 6.96 (this source at 2 waves/SIMD, no spills) / 6.38 ms (3 waves/SIMD, 47 VGPRs spilled
-                          // outside the hop loop's row trips) -- DESIGN 5.1
+                          // outside the hop loop's row trips; since then 25, none of them inside a hop loop) -- DESIGN 5.1
 #endif
 #ifndef KDB_WIDE4_MINW
 #define KDB_WIDE4_MINW 4 // waves per SIMD the four-wave kernels are compiled for (0 = as the one-wave kernels): measured 1M x 768,
@@ -94,6 +94,11 @@ constexpr int kdb_search_minw() {
     if (PREC == KDB_PREC_F16) return NCH > 16 ? 2 : KDB_F16_MINW; // (1536 columns: three waves per SIMD spilled ~40 registers -- and the gate found a reload ahead of an exec restore there)
     return NCH > 12 ? 2 : NCH > 6 ? KDB_F32_MINW : NCH > 4 ? KDB_F32_MINW6 : NCH == 0 ? KDB_GENERIC_MINW : KDB_SEARCH_MINW; // wide rows keep 16+ float4 per lane in flight
 }
+// The planes kernel that is compiled for three waves per SIMD (one-slot beam, one wave per query) has no register to spare in its hop
+// loop: it alone takes the forms that keep loop-invariant per-lane values out of it (compile-time LDS layout, kdb_lane_again in the rare
+// paths and at the list load, uniform popped id / allow-list index); every other kernel is the code it was.
+template <int PL, int BS, int WIDE>
+constexpr bool kdb_hop_loop_lean() { return PL != 0 && BS == 1 && WIDE == 1; }
 // PL = 1: a planes kernel (one wave per query only): rows are read from the walk planes (v.walk_hi / walk_lo / walk_err, compute_dists).
 template <int PREC, int METRIC, int NCH>
 constexpr bool kdb_planes_kernel() { return PREC == KDB_PREC_F32 && METRIC == KDB_METRIC_COSINE && NCH == 12; } // (768 columns: kdb_walk_planes_shape)
@@ -109,7 +114,10 @@ hnsw_search_kernel(KdbView v, const void *__restrict__ queries, const float *__r
     WaveLds s;
     size_t off = 0;
     s.q = reinterpret_cast<float *>(smem + off);
-    off += q_lds_bytes<PREC>(v.ld);
+    // (the three-wave planes kernel: v.ld == 64 * NCH, so every LDS array up to the hash table sits at a compile-time address -- an immediate offset of
+    // the access, not an address register held across the hop loop: those were what the three-wave kernel reloaded from scratch per hop)
+    constexpr bool HOP3 = kdb_hop_loop_lean<PL, BS, WIDE>();
+    off += HOP3 ? q_lds_bytes<PREC>(64u * (uint32_t)NCH) : q_lds_bytes<PREC>(v.ld);
     s.beam_d = reinterpret_cast<float *>(smem + off);
     if (BS == 0) off += (size_t)beam_cap * 4;
     s.beam_id = reinterpret_cast<uint32_t *>(smem + off);
@@ -136,6 +144,10 @@ hnsw_search_kernel(KdbView v, const void *__restrict__ queries, const float *__r
         off += ins_n * 4;
         s.ins_cap = ins_n;
     }
+    if (HOP3) { // the three-wave planes kernel: the hash table (every hop) ahead of the pending list (indexes with deleted nodes only), at a compile-time address too
+        s.marks = reinterpret_cast<uint32_t *>(smem + off);
+        off += (size_t)vis_size * 4;
+    }
     s.nr_d = reinterpret_cast<float *>(smem + off); // traversal-only candidates (deleted nodes, filtered-out entry)
     off += (size_t)nr_cap * 4;
     s.nr_id = reinterpret_cast<uint32_t *>(smem + off);
@@ -143,11 +155,11 @@ hnsw_search_kernel(KdbView v, const void *__restrict__ queries, const float *__r
     s.nr_lo = reinterpret_cast<uint32_t *>(smem + off);
     if (PREC == KDB_PREC_I8) off += (size_t)nr_cap * 4;
     s.nr_cap = nr_cap;
-    s.marks = reinterpret_cast<uint32_t *>(smem + off); // VIS=0: un-mark list; VIS=1: the hash table
+    if (!HOP3) s.marks = reinterpret_cast<uint32_t *>(smem + off); // VIS=0: un-mark list; VIS=1: the hash table
     s.beam_cap = beam_cap;
 
     const int lane = kdb_lane();
-    typename VisSel<VIS>::type vis;
+    typename std::conditional<HOP3 && VIS == 1, VisHashT<true>, typename VisSel<VIS>::type>::type vis;
     if constexpr (VIS == 1) {
         vis.tab = s.marks;
         vis.full_size = vis_size; // (size / shift / limit: set per layer by begin_layer)
@@ -198,7 +210,8 @@ hnsw_search_kernel(KdbView v, const void *__restrict__ queries, const float *__r
         const uint32_t *q_allow = allow;
         uint32_t ep = entry;
         if (ma.group_entry) { // of_query == nullptr: the whole batch shares list 0
-            const uint32_t g = ma.of_query ? ma.of_query[qi] : 0u;
+            uint32_t g = ma.of_query ? ma.of_query[qi] : 0u;
+            if constexpr (HOP3) g = uni(g); // (one list per query: the list's address is a scalar pair, not two vector registers across the walk)
             if (g == 0xffffffffu) q_allow = nullptr;
             else {
                 q_allow = allow + (size_t)g * ma.words32;
