@@ -858,6 +858,15 @@ KDB_API int kdb_probe_poison_lds(kdb_index *idx, uint32_t pattern);
  * Host-side bookkeeping only: the tests use it to assert that a case reached the template instantiation it was written for.   */
 #define KDB_LAUNCH_SHAPE_WORDS 16u
 KDB_API int kdb_probe_launch_shape(kdb_index *idx, uint32_t last_n, uint32_t *out);
+/* TEST HOOK: the plan of the heap-order pass (KDB_SEARCH_HEAP_ORDER) that a search of B queries with this k and efSearch would
+ * launch on the index as it stands.  out[KDB_HEAP_PLAN_WORDS]:
+ *   [0] words of the LDS visited hash (0 = the HBM bitset alone)   [1] 1 = the result heap in registers
+ *   [2] candidate-heap entries kept in LDS (nl_c)                  [3] ... and in all, LDS + HBM tail (cap_c): a walk whose
+ *       candidate heap outgrows it keeps the fast walk's answer and its tie bit and is counted in n_dropped
+ *   [4] LDS bytes per workgroup   [5] workgroups of a pass behind the search kernel   [6] bytes of all their HBM tails
+ * Launches nothing.  The tests take their thresholds from it: which walks reach the tail, which overflow.                    */
+#define KDB_HEAP_PLAN_WORDS 7u
+KDB_API int kdb_probe_heap_plan(kdb_index *idx, uint32_t k, uint32_t ef, uint32_t B, uint64_t *out);
 
 KDB_API int kdb_get_counters(kdb_index *idx, kdb_counters *out);
 /* Statistics of the last `last_n` (<= 64) search / flat-scan / distance launches, oldest first: each

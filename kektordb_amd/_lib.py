@@ -25,7 +25,7 @@ ABI_SYMBOLS = [
     "kdb_distance_batch_dev", "kdb_index_build", "kdb_merge_topk", "kdb_merge_topk_dev", "kdb_merge_topk_packed_dev", "kdb_search_batch_multi_dev", "kdb_index_append_nodes", "kdb_index_patch_adjacency", "kdb_index_set_entry", "kdb_flat_scan_groups_dev", "kdb_get_counters", "kdb_get_launch_stats",
     "kdb_index_sync", "kdb_index_set_launch_timing", "kdb_test_select_neighbors", "kdb_cluster_create", "kdb_cluster_destroy", "kdb_cluster_info",
     "kdb_sharded_search_batch", "kdb_sharded_flat_scan_batch", "kdb_index_compress", "kdb_index_get_quantizer", "kdb_index_add_batch", "kdb_merge_topk_packed_f64_dev",
-    "kdb_cluster_comm_info", "kdb_cluster_debug_fail_next", "kdb_index_reserve", "kdb_index_drop_f16_shadow", "kdb_probe_gather", "kdb_probe_stream", "kdb_probe_poison_lds", "kdb_probe_launch_shape", "kdb_index_caller_stats", "kdb_merge_topk_f64", "kdb_index_refine",
+    "kdb_cluster_comm_info", "kdb_cluster_debug_fail_next", "kdb_index_reserve", "kdb_index_drop_f16_shadow", "kdb_probe_gather", "kdb_probe_stream", "kdb_probe_poison_lds", "kdb_probe_launch_shape", "kdb_probe_heap_plan", "kdb_index_caller_stats", "kdb_merge_topk_f64", "kdb_index_refine",
     "kdb_index_vacuum", "kdb_index_dead_link_scan", "kdb_index_drop_walk_planes", "kdb_index_add",
     "kdb_index_decode_rows", "kdb_index_decode_rows_dev", "kdb_search_by_id", "kdb_search_by_id_dev", "kdb_flat_scan_by_id", "kdb_flat_scan_by_id_dev",
     "kdb_consensus_batch", "kdb_consensus_batch_dev", "kdb_belief_batch", "kdb_belief_batch_dev",
@@ -204,6 +204,7 @@ def load():
     L.kdb_probe_stream.argtypes = [vp, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_uint64)]
     L.kdb_probe_poison_lds.argtypes = [vp, u32]
     L.kdb_probe_launch_shape.argtypes = [vp, u32, vp]
+    L.kdb_probe_heap_plan.argtypes = [vp, u32, u32, u32, vp]
     L.kdb_index_reserve.argtypes = [vp, u32]
     L.kdb_index_drop_f16_shadow.argtypes = [vp, C.c_int]
     L.kdb_index_drop_walk_planes.argtypes = [vp, C.c_int]

@@ -2889,6 +2889,23 @@ extern "C" int kdb_probe_launch_shape(kdb_index *idx, uint32_t last_n, uint32_t 
     return KDB_OK;
 }
 
+// TEST HOOK: the plan of the heap-order pass a search of B queries with (k, ef) would launch on this index (kdb_heap_walk_plan)
+extern "C" int kdb_probe_heap_plan(kdb_index *idx, uint32_t k, uint32_t ef, uint32_t B, uint64_t *out) {
+    KDB_CHECK_IDX(idx);
+    if (!out || k == 0 || B == 0) {
+        kdb_set_error("probe_heap_plan: out, k and B must not be zero");
+        return KDB_ERR_INVALID;
+    }
+    std::lock_guard<std::mutex> lk(idx->mu);
+    KDB_HIP(hipSetDevice(idx->device));
+    const KdbView v = kdb_make_view(idx);
+    KdbHeapPlan p{};
+    const int rc = kdb_heap_walk_plan(idx, v, ef, k, B, &p);
+    if (rc) return rc;
+    out[0] = p.hsize, out[1] = p.reg_results, out[2] = p.nl_c, out[3] = p.cap_c, out[4] = p.lds, out[5] = p.grid, out[6] = p.tail_bytes;
+    return KDB_OK;
+}
+
 extern "C" int kdb_index_set_launch_timing(kdb_index *idx, int on) {
     KDB_CHECK_IDX(idx);
     std::lock_guard<std::mutex> lk(idx->mu);

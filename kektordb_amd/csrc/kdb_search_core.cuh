@@ -1897,7 +1897,7 @@ __device__ void search_layer_wide(const KdbView &v, const WaveLds &s, BeamT &b, 
 }
 
 // LDS hash-set size (words) for ef; 0 = use the HBM bitset
-__host__ __device__ inline uint32_t kdb_vis_hash_size(uint32_t ef) {
+__host__ __device__ constexpr uint32_t kdb_vis_hash_size(uint32_t ef) { // (constexpr: search_heap.hip checks kdb_heap_plan.h's rule against it)
     if (ef <= 100) return 2048; // the set holds the ~9*ef ids a query evaluates
     if (ef <= 260) return 4096;
     return 0;

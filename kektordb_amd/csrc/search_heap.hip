@@ -743,41 +743,24 @@ int heap_dispatch(const KdbView &v, bool hash, bool reg, bool ov, F f) {
 // accepted neighbour of a layer search minus one pop per hop: a few ef at its largest) -- so that a few thousand tied queries all
 // walk at once; the rest of the candidate heap (up to cap_c entries: 16 ef, at least 2048) in HBM scratch, per workgroup.  (Round 4
 // gave every wave 60 KB and 64 ef entries of tail whatever ef was: two waves per CU, 480 MB of tails per scratch lane.)
+// The arithmetic is kdb_heap_plan.h's (tests/cpp/heap_plan_test.cpp checks it against the carve of heap_walk_kernel above); it
+// restates two rules of the fast walk, checked here at every boundary:
+static_assert(KDB_HEAP_MARKS == KDB_UP_MARK_CAP, "the plan sizes the un-mark list the layer search fills");
+static_assert(kdb_heap_hash_words(1) == kdb_vis_hash_size(1) && kdb_heap_hash_words(100) == kdb_vis_hash_size(100) &&
+                  kdb_heap_hash_words(101) == kdb_vis_hash_size(101) && kdb_heap_hash_words(260) == kdb_vis_hash_size(260) &&
+                  kdb_heap_hash_words(261) == kdb_vis_hash_size(261) && kdb_heap_hash_words(0xffffffffu) == kdb_vis_hash_size(0xffffffffu),
+              "the plan sizes the visited hash the fast walk uses");
 int kdb_heap_walk_plan(kdb_index *idx, const KdbView &v, uint32_t ef, uint32_t k, uint32_t B, KdbHeapPlan *out) {
     const uint32_t eff = kdb_mixed_effective_ef(ef, k, false); // (a mixed launch: its capacity and its stride -- LDS and heaps hold every query of it)
-    const bool wk = v.precision == KDB_PREC_I8;
-    const size_t ew = wk ? 12 : 8;
     KdbHeapPlan p{};
-    p.hsize = kdb_vis_hash_size(eff); // 2048 / 4096 words up to ef 260, beyond: the HBM bitset
-    p.reg_results = p.hsize != 0 && eff + 2u <= 64u; // the result heap in registers (entry i in lane i)
-    const size_t fixed = (wk ? ((size_t)v.ld + 15) / 16 * 16 : (size_t)v.ld * 4) + 64 * (wk ? 12 : 8) + (p.hsize ? (size_t)p.hsize * 4 : KDB_UP_MARK_CAP * 4) +
-                         (p.reg_results ? 1 : 2) * (size_t)(eff + 2u) * ew;
-    const uint64_t cap64 = (uint64_t)16u * eff > 2048u ? (uint64_t)16u * eff : 2048u;
-    p.cap_c = (uint32_t)(cap64 < (uint64_t)v.count + 2u ? cap64 : (uint64_t)v.count + 2u); // (a heap never holds more entries than there are nodes)
-    const size_t want = fixed + (size_t)(8u * eff > 64u ? 8u * eff : 64u) * ew;
-    size_t tier = 0;
-    for (size_t waves : {8, 6, 4, 3, 2}) {
-        const size_t t = (160u * 1024u) / waves - 512u;
-        if (t >= want) {
-            tier = t;
-            break;
-        }
-    }
-    if (!tier) tier = fixed + 64 * ew + 64 < 158u * 1024u ? (want < 158u * 1024u ? want : 158u * 1024u) : fixed + 64 * ew;
-    size_t n = tier > fixed ? (tier - fixed) / ew : 64;
-    if (n > 4095) n = 4095; // twelve levels of the heap on chip
-    if (n < 64) n = 64;
-    if (n > p.cap_c) n = p.cap_c;
-    p.nl_c = (uint32_t)n;
-    p.lds = fixed + (size_t)p.nl_c * ew;
-    if (p.lds + 16 > 160u * 1024u) {
+    if (!kdb_heap_plan_lds(v.precision == KDB_PREC_I8, v.ld, v.count, eff, &p)) { // hash words, result heap, cap_c, nl_c, lds (kdb_heap_plan.h)
         kdb_set_error("heap-order walk: ef=%u needs %zu bytes of LDS per wave (limit 160 KiB)", eff, p.lds);
         return KDB_ERR_UNSUPPORTED;
     }
     const int occ = heap_dispatch(v, p.hsize != 0, p.reg_results != 0, false, [&](auto kern, int) { return heap_occupancy(kern, p.lds); });
     const uint32_t room = (uint32_t)idx->n_cu * (uint32_t)(occ < 1 ? 1 : occ);
     p.grid = B < room ? B : room;
-    p.tail_bytes = (size_t)p.grid * (size_t)(p.cap_c - p.nl_c) * 12u;
+    p.tail_bytes = kdb_heap_tail_bytes(p.grid, p.cap_c, p.nl_c);
     *out = p;
     return KDB_OK;
 }

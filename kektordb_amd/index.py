@@ -678,6 +678,17 @@ class HipIndex:
         check(self.L.kdb_probe_launch_shape(self.h, last_n, _ptr(arr)), "kdb_probe_launch_shape")
         return [dict(zip(self.LAUNCH_SHAPE_FIELDS, (int(x) for x in row))) for row in arr]
 
+    HEAP_PLAN_FIELDS = ("hash_words", "reg_results", "nl_c", "cap_c", "lds_bytes", "grid", "tail_bytes")
+
+    def heap_plan(self, k: int, ef: int, B: int):
+        """test hook: the plan of the heap-order pass a search of B queries with (k, ef) would launch on this index as it stands
+        (kdb_probe_heap_plan) -- a dict over HEAP_PLAN_FIELDS: a tied walk's candidate heap keeps its first nl_c entries in LDS,
+        the rest up to cap_c in HBM; a walk that outgrows cap_c keeps the fast walk's answer and its tie bit.  Launches nothing."""
+        self._live()
+        arr = np.zeros(len(self.HEAP_PLAN_FIELDS), dtype=np.uint64)
+        check(self.L.kdb_probe_heap_plan(self.h, int(k), int(ef), int(B), _ptr(arr)), "kdb_probe_heap_plan")
+        return dict(zip(self.HEAP_PLAN_FIELDS, (int(x) for x in arr)))
+
     def probe_stream(self, shadow: bool = False):
         """measurement hook: GB/s of one coalesced pass over this index's rows (or its half-precision copy)"""
         ms, nbytes = C.c_float(), C.c_uint64()

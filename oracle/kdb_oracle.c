@@ -520,6 +520,7 @@ typedef struct {
     uint8_t deleted;
 } orc_node;
 
+#define ORC_PEAK_LEVELS 32
 typedef struct orc_index {
     int dim, metric, precision, m, mmax0, efc;
     double ml;
@@ -540,6 +541,9 @@ typedef struct orc_index {
     orc_bitset visited;
     orc_heap cands, results;
     orc_counters ctr;
+    /* largest candidate-heap length search_layer reached, per layer, since the last orc_search began (levels above
+     * ORC_PEAK_LEVELS - 1 share the last slot).  Test infrastructure: sizes the cases of the GPU heap-order walk. */
+    size_t peak_cands[ORC_PEAK_LEVELS];
 } orc_index;
 
 static inline uint64_t splitmix64(uint64_t *s) {
@@ -724,6 +728,8 @@ static int search_layer(orc_index *h, const orc_query *q, uint32_t ep, int k, in
     double dist = query_node(h, q, ep);
     orc_cand epc = {ep, dist};
     heap_push(cands, epc);
+    size_t *peak = &h->peak_cands[level < 0 ? 0 : level < ORC_PEAK_LEVELS ? level : ORC_PEAK_LEVELS - 1];
+    if (cands->len > *peak) *peak = cands->len;
     bs_add(visited, ep);
     int ep_valid = 1;
     if (filt && !allow_contains(allow, ep)) ep_valid = 0;
@@ -753,6 +759,7 @@ static int search_layer(orc_index *h, const orc_query *q, uint32_t ep, int k, in
             if ((int)results->len < ef || d < worst) {
                 orc_cand nc = {nb, d};
                 heap_push(cands, nc);
+                if (cands->len > *peak) *peak = cands->len;
                 if (!nn->deleted) {
                     heap_push(results, nc);
                     if ((int)results->len > ef) (void)heap_pop(results);
@@ -1105,6 +1112,7 @@ ORC_EXPORT int orc_search(orc_index *h, const float *query, int k, const uint64_
                           orc_counters *ctr) {
     h->ctr.n_dist = 0;
     h->ctr.n_hops = 0;
+    memset(h->peak_cands, 0, sizeof h->peak_cands);
     if (ctr) { ctr->n_dist = 0; ctr->n_hops = 0; }
     if (h->max_level == -1 || k <= 0) return 0;
     uint32_t ep = h->entry;
@@ -1173,6 +1181,11 @@ done:
     free(qf); free(q16); free(q8);
     return result;
 }
+
+/* The largest length the candidate heap had on level 0 during the handle's last orc_search (0: it never got there).  The
+ * reference's heap only grows by accepted neighbours and shrinks by one pop per hop; deleted nodes are pushed as candidates
+ * and never fill the result set, so an index between Delete and Vacuum is where it grows longest.                         */
+ORC_EXPORT uint64_t orc_index_last_peak_candidates(const orc_index *h) { return (uint64_t)h->peak_cands[0]; }
 
 /* Layer-level entry for tests (searchLayerUnlocked with a prepared f32 query
  * that is used as-is: no normalisation).                                    */

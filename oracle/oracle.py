@@ -93,6 +93,8 @@ def lib():
     L.orc_search.restype = C.c_int
     L.orc_search.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_int,
                              C.c_void_p, C.c_void_p, C.POINTER(Counters)]
+    L.orc_index_last_peak_candidates.restype = C.c_uint64
+    L.orc_index_last_peak_candidates.argtypes = [C.c_void_p]
     L.orc_search_layer_raw.restype = C.c_int
     L.orc_search_layer_raw.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_int, C.c_int,
                                        C.c_void_p, C.c_void_p]
@@ -248,6 +250,10 @@ class OracleIndex:
         if counters:
             return ids[:n].copy(), dist[:n].copy(), (int(ctr.n_dist), int(ctr.n_hops))
         return ids[:n].copy(), dist[:n].copy()
+
+    def last_peak_candidates(self):
+        """the largest length the candidate heap had on level 0 during this handle's last search()"""
+        return int(self.L.orc_index_last_peak_candidates(self.h))
 
     def search_many(self, queries, k, ef, handle=None):
         q = np.ascontiguousarray(queries, dtype=np.float32)
