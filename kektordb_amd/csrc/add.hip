@@ -217,7 +217,7 @@ static int add_impl(kdb_index *idx, uint32_t first, uint32_t nb, const uint8_t *
         const int top = (int)st.level < st.max_level ? (int)st.level : st.max_level; // links only up to the current top (:694-697)
         for (int l = top; l >= 0; l--) {
             hipLaunchKernelGGL(klink, dim3(1), dim3(256), lds_link, s, v, idx->d_adj0, idx->d_adj_up, first + i, l, l == top ? st.max_level : -1, st.entry, efc,
-                               wl.beam_cap, wl.nr_cap, idx->d_visited, d_st, d_ctr);
+                               wl.beam_cap, wl.nr_cap, kdb_cur(idx).d_visited, d_st, d_ctr);
             hipLaunchKernelGGL(krev, dim3(l == 0 ? idx->deg0 : idx->deg_up), dim3(256), lds_rev, s, v, idx->d_adj0, idx->d_adj_up, first + i, (uint32_t)l,
                                (const uint32_t *)d_st, d_ctr);
         }

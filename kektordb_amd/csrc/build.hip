@@ -720,11 +720,11 @@ int build_impl(kdb_index *idx, uint32_t count, const kdb_build_params *bp) {
         KDB_HIP(hipMemsetAsync(bv.cand_cnt, 0, (size_t)n_tasks * 4, s));
         KDB_HIP(hipMemsetAsync(bv.n_touched, 0, 4, s));
         KDB_HIP(hipMemsetAsync(bv.ov_cnt, 0, 4, s));
-        KDB_HIP(hipMemsetAsync(idx->d_work, 0, 4, s));
+        KDB_HIP(hipMemsetAsync(kdb_cur(idx).d_work, 0, 4, s));
         KdbView v = kdb_make_view(idx);
         v.count = next + nb - 1;
         uint32_t grid = slots_vis < nb ? slots_vis : nb;
-        hipLaunchKernelGGL(ksearch, dim3(grid), dim3(64), wl.bytes, s, v, bv, wl.beam_cap, wl.nr_cap, idx->d_visited, idx->d_work);
+        hipLaunchKernelGGL(ksearch, dim3(grid), dim3(64), wl.bytes, s, v, bv, wl.beam_cap, wl.nr_cap, kdb_cur(idx).d_visited, kdb_cur(idx).d_work);
         KDB_HIP(hipGetLastError());
         hipLaunchKernelGGL(kselect, dim3(n_tasks), dim3(256), lds_prune, s, v, bv);
         KDB_HIP(hipGetLastError());
@@ -895,10 +895,10 @@ int add_batch_ref_impl(kdb_index *idx, uint32_t first, uint32_t nb, const uint8_
     KDB_TRY(hipMemsetAsync(d_cnt, 0, L * 4, s));
     KDB_TRY(hipMemsetAsync(d_cur, 0, L * 4, s));
     KDB_TRY(hipMemsetAsync(d_out, 0, 256, s)); // [0] requests, [1] touched targets, [2] requests above a node's level, [3] big unions, [4] -, [5] grown level
-    KDB_TRY(hipMemsetAsync(idx->d_work, 0, 4, s));
+    KDB_TRY(hipMemsetAsync(kdb_cur(idx).d_work, 0, 4, s));
     // ---- phase 1: every new node searches the graph as it was (entry point / maxLevel frozen, :1796-1801)
     KdbView v = kdb_make_view(idx); // count = new_count: the new ids are valid wherever a walk meets them (the re-used slot)
-    hipLaunchKernelGGL(ksearch, dim3(slots_vis < nb ? slots_vis : nb), dim3(64), wl.bytes, s, v, bv, wl.beam_cap, wl.nr_cap, idx->d_visited, idx->d_work);
+    hipLaunchKernelGGL(ksearch, dim3(slots_vis < nb ? slots_vis : nb), dim3(64), wl.bytes, s, v, bv, wl.beam_cap, wl.nr_cap, kdb_cur(idx).d_visited, kdb_cur(idx).d_work);
     KDB_TRY(hipGetLastError());
     // ---- phases 2 + 3
     const uint32_t reuse_id = reuse ? first : 0u;

@@ -1,10 +1,10 @@
 // by_id.hip -- stored rows as queries: the device side of GetNodeData / VGetMany (pkg/core/hnsw/hnsw_index.go:2909-2959) and the
-// small epilogue of the by-id entry points (kdb_search_by_id / kdb_flat_scan_by_id, kdb_api.hip).
+// small epilogue of the by-id entry points (kdb_search_by_id / kdb_flat_scan_by_id, kdb_api_query.hip).
 //
 //   decode_rows_kernel   ids[n] -> out[n][dim] float32, the vector GetNodeData hands to its callers: float32 rows as stored, float16
 //                        rows widened, int8 rows through Quantizer.Dequantize (quantizer.go:181-198).  An id that is 0, above count
 //                        or marked deleted is "not found" (:2921-2931): found[i] = 0 and the row is filled with `miss` -- zeros for
-//                        the public decode and the exact scan, a quiet NaN for the graph search (see kdb_api.hip).
+//                        the public decode and the exact scan, a quiet NaN for the graph search (see kdb_api_query.hip).
 //   by_id_finish_kernel  the [B][k] answers of the caller from the [B][kin] answers of the inner call: not-found sources get no
 //                        results; KDB_BY_ID_DROP_SELF (kin = k + 1) removes the source's own id, or else the last entry.
 //

@@ -143,7 +143,7 @@ int kdb_launch_filter_eval(kdb_index *idx, const kdb_filter_term *terms, const u
     }
     int rc = kdb_ensure_scratch(idx, (size_t)L.total);
     if (rc) return rc;
-    unsigned char *d = reinterpret_cast<unsigned char *>(idx->d_scratch);
+    unsigned char *d = reinterpret_cast<unsigned char *>(kdb_cur(idx).d_scratch);
     KDB_HIP(hipMemcpyAsync(d, img.data(), (size_t)L.total, hipMemcpyHostToDevice, s));
     if (d_card) KDB_HIP(hipMemsetAsync(d_card, 0, (size_t)P * 4u, s));
     uint32_t lds = 0; // the cells of the chunk that needs most

@@ -1767,7 +1767,7 @@ struct FsCall {
 
 // a region of the scratch buffer, by the offset the plan gives it
 template <class T>
-static T *fs_at(const kdb_index *idx, size_t offset) { return reinterpret_cast<T *>(reinterpret_cast<unsigned char *>(idx->d_scratch) + offset); }
+static T *fs_at(const kdb_index *idx, size_t offset) { return reinterpret_cast<T *>(reinterpret_cast<unsigned char *>(kdb_cur(idx).d_scratch) + offset); }
 
 // measurement switches of the `make dbg` build (KDB_FB_DBG: big-tile kernel, KDB_FSS_DBG: small kernel); no other build reads them
 static uint32_t fs_dbg_switches(const char *name) {
@@ -2177,7 +2177,7 @@ int kdb_launch_flat_scan_groups(kdb_index *idx, const KdbView &v, const void *d_
     if (total == 0) {
         rc = kdb_ensure_scratch(idx, fs_group_count_bytes(G));
         if (rc) return rc;
-        uint32_t *d_gn0 = reinterpret_cast<uint32_t *>(idx->d_scratch);
+        uint32_t *d_gn0 = reinterpret_cast<uint32_t *>(kdb_cur(idx).d_scratch);
         hipLaunchKernelGGL(group_count_kernel, ggrid, dim3(256), 0, s, v.deleted, d_lists, words32, v.count, d_gn0);
         KDB_HIP(hipGetLastError());
         std::vector<uint32_t> gn(chunk_words);

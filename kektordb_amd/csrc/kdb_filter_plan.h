@@ -1,5 +1,5 @@
 // kdb_filter_plan.h -- the plan of filter_eval_kernel (filter.hip): tile geometry, program chunking, term validation and the layout
-// of the staged programs.  Shared by the host (kdb_api.hip plans and validates with it) and the kernel (which indexes with it), so
+// of the staged programs.  Shared by the host (kdb_api_filter.hip plans and validates with it) and the kernel (which indexes with it), so
 // the two cannot disagree.  Plain C++, no HIP header: host and device under hipcc, and tests/cpp/filter_plan_test.cpp builds it alone.
 //
 // GEOMETRY.  One lane per id, one wave per workgroup.  A wave's ballot of a program's verdict over 64 consecutive ids is one word of
@@ -220,7 +220,7 @@ KDB_FILTER_HD inline bool kdb_filter_run(const kdb_filter_term *terms, uint32_t 
     return kdb_filter_run_words(terms, n, 1u, [&](uint32_t col, uint32_t) { return cell(col); }) != 0u;
 }
 
-// ---- routing of a filtered request (kdb_search_filtered, kdb_api.hip) -- host only ------------------------------------------------
+// ---- routing of a filtered request (kdb_search_filtered, kdb_api_filter.hip) -- host only ------------------------------------------------
 // The route of one program from its cardinality: 2 = it matches nothing (answered by the host), 1 = the exact scan, 0 = the walk.
 // The rule of the micro-batcher's takes_flat_scan (kektor_hip.hpp), per program; flat_max_k is the exact scan's limit (KDB_FLAT_MAX_K).
 inline uint8_t kdb_filter_route_of(uint32_t card, uint32_t count, uint32_t k, double flat_selectivity, uint32_t flat_max_k) {

@@ -128,18 +128,18 @@ struct kdb_group {
     size_t dist_bytes = 4;
 };
 struct kdb_lane {
-    uint32_t *d_visited = nullptr;
+    uint32_t *d_visited = nullptr;  // slots * vis_words
     uint32_t vis_slots = 0;
-    void *d_scratch = nullptr;
+    void *d_scratch = nullptr;      // general scratch (flat-scan partials, traces, ...)
     size_t scratch_bytes = 0;
-    void *d_qbuf = nullptr;
+    void *d_qbuf = nullptr;         // prepared queries (stored form, padded to ld) + query norms
     size_t qbuf_bytes = 0;
-    uint32_t *d_gentry = nullptr;
+    uint32_t *d_gentry = nullptr;   // entry point per allow list of a search batch (hnsw_index.go:437-447), chosen on the device
     uint32_t gentry_cap = 0;
-    uint32_t *d_work = nullptr;
-    void *d_tie = nullptr;      // heap-order second pass: [count, cursor, tied query indices ...] | candidate-heap tails
+    uint32_t *d_work = nullptr;     // work counters / misc small device words (64 words; 8: first allowed id, 12: max norm bits, 13: LDS poison sink, 32..41 = the graph search's self-resetting accumulators {n_dist, n_hops, work | done, dropped, tied} as five 64-bit words)
+    void *d_tie = nullptr;          // heap-order second pass (search_heap.hip): [count, cursor, tied query indices ...] | candidate-heap tails
     size_t tie_bytes = 0;
-    void *d_byid = nullptr;     // by-id entry points: decoded source rows | found flags | the inner call's k + 1 answers
+    void *d_byid = nullptr;         // by-id entry points (by_id.hip): decoded source rows | found flags | the inner call's k + 1 answers -- none of the buffers the walk and the scan use
     size_t byid_bytes = 0;
     hipStream_t last_stream = nullptr;
     hipEvent_t done = nullptr;
@@ -191,26 +191,13 @@ struct kdb_index {
     // metadata columns (filter.hip): slot c holds (cap + 1) entries of col_kind[c] (0: the slot is empty, nothing allocated)
     void *d_col[KDB_MAX_COLUMNS] = {};
     uint32_t col_kind[KDB_MAX_COLUMNS] = {};
-    // scratch
-    uint32_t *d_visited = nullptr;  // slots * vis_words
-    uint32_t vis_slots = 0;
-    void *d_scratch = nullptr;      // general scratch (flat-scan partials, traces, ...)
-    size_t scratch_bytes = 0;
-    void *d_qbuf = nullptr;         // prepared queries (stored form, padded to ld) + query norms
-    size_t qbuf_bytes = 0;
+    // scratch that belongs to the index (a call's own scratch: kdb_lane, below)
     void *d_iobuf = nullptr;        // staging of the host-pointer calls that do not fit a slot (big_mu)
     size_t iobuf_bytes = 0;
-    uint32_t *d_gentry = nullptr;    // entry point per allow list of a search batch (hnsw_index.go:437-447), chosen on the device
-    uint32_t gentry_cap = 0;
-    void *d_tie = nullptr;           // (current lane's) scratch of the heap-order second pass (search_heap.hip)
-    size_t tie_bytes = 0;
-    void *d_byid = nullptr;          // (current lane's) decode buffer of the by-id entry points (by_id.hip): none of the buffers the walk and the scan use
-    size_t byid_bytes = 0;
     void *d_build = nullptr;        // graph-construction workspace
     size_t build_bytes = 0;
     int last_kind = 0;              // 1 search, 2 flat scan, 3 distance tile
     uint32_t last_B = 0, last_C = 0;
-    uint32_t *d_work = nullptr;     // work counters / misc small device words (64 words; 8: first allowed id, 12: max norm bits, 13: LDS poison sink, 32..41 = the graph search's self-resetting accumulators {n_dist, n_hops, work | done, dropped, tied} as five 64-bit words)
     unsigned long long *d_ctr = nullptr; // n_dist, n_hops
     // trace
     uint32_t *trace_ndist = nullptr, *trace_nhops = nullptr;
@@ -228,7 +215,7 @@ struct kdb_index {
     // written by launch_search_bs / kdb_launch_heap_walk for the slot kdb_stats_begin has just opened; zero for every other kind
     uint32_t ring_shape[RING][KDB_LAUNCH_SHAPE_WORDS] = {};
     uint64_t launch_seq = 0;
-    std::mutex mu;
+    alignas(64) std::mutex mu; // (a cache line boundary: what is guarded by mu does not share a line with the statistics ring in front of it)
     // concurrent host-pointer calls (see kdb_slot): all guarded by mu
     kdb_slot slots[KDB_MAX_SLOTS];
     int n_slots = 0;
@@ -241,21 +228,29 @@ struct kdb_index {
     uint32_t release_seq = 0;      // ... every other freed slot is theirs when both they and a forming group wait (no starvation)
     kdb_group groups[KDB_GROUP_POOL];
     uint32_t *h_done_pool = nullptr;          // KDB_GROUP_POOL x KDB_GROUP_CAP completion words, page-locked
-    std::atomic<uint32_t> flag_waiters{0};    // callers watching completion words right now (the first few spin, the others sleep)
+    // what the watchers of completion words write OUTSIDE mu, on cache lines of its own: every caller adds to these words when it
+    // leaves, and a line they shared with words the launching thread reads under mu (the current lane's buffers, combine_mixed, the
+    // combiner's statistics) would travel between the cores with every call -- the layout is stated, not left to what sits in front
+    alignas(64) std::atomic<uint32_t> flag_waiters{0};    // callers watching completion words right now (the first few spin, the others sleep)
     std::atomic<uint32_t> walk_ns{150000};    // running estimate of join -> own answer, nanoseconds (first sleep of a watcher)
-    std::mutex big_mu;             // calls too large for a slot share d_iobuf / stream / stream2: one at a time
+    alignas(64) std::atomic<uint64_t> ns_to_launch{0}, ns_launch_to_done{0}, ns_in_launch{0}, n_naps{0}, n_combined_calls{0}; // where a combined call's time goes (a line apart from the two above, as they always were: 256 callers add to both)
+    alignas(64) std::mutex big_mu;             // calls too large for a slot share d_iobuf / stream / stream2: one at a time
     uint64_t n_groups = 0, n_group_members = 0, largest_group = 0; // statistics of the combiner (kdb_index_caller_stats)
     uint64_t n_mixed_launches = 0, n_mixed_calls = 0, n_mixed_refused = 0; // kdb_index_mixed_stats
     bool combine_mixed = true;     // KDB_COMBINE_MIXED (read at creation): concurrent callers combine across (k, ef); 0: exact-key joining
-    std::atomic<uint64_t> ns_to_launch{0}, ns_launch_to_done{0}, ns_in_launch{0}, n_naps{0}, n_combined_calls{0}; // where a combined call's time goes
-    // scratch lanes: the fields d_visited / d_scratch / d_qbuf / d_gentry / d_work above always name the CURRENT lane's
-    // buffers (kdb_lane_acquire copies them in, kdb_lane_release copies them back: calls are serialised by `mu`)
-    kdb_lane lanes[KDB_LANES];
+    // scratch lanes: a lane's buffers live in the lane and nowhere else; cur_lane is the one the call that holds `mu` took
+    // (kdb_lane_acquire), and kdb_cur(idx), below, names its buffers.  Code that takes no lane (builders under KdbWriteLock took
+    // theirs in the entry point; probe.hip takes none) works on the lane that was current last.
+    alignas(64) kdb_lane lanes[KDB_LANES];
     int cur_lane = 0;
     uint64_t lane_clock = 0;
     // cached device facts (one query per index, not per launch)
     int n_cu = 0;
 };
+
+// the current lane: the scratch of the call that holds idx->mu
+inline kdb_lane &kdb_cur(kdb_index *idx) { return idx->lanes[idx->cur_lane]; }
+inline const kdb_lane &kdb_cur(const kdb_index *idx) { return idx->lanes[idx->cur_lane]; }
 
 // take the scratch set for a call on stream s (device-side wait on its previous user if that was another stream) ...
 int kdb_lane_acquire(kdb_index *idx, hipStream_t s);
@@ -264,8 +259,8 @@ int kdb_lane_release(kdb_index *idx, hipStream_t s);
 // Writers (upload, delete, build, reserve ...) exclude host-pointer calls in flight the way the reference's activeMu.Lock excludes
 // its RLock holders: take mu, announce, wait until no call's kernels can still be running.  (Calls of the _dev entry points run on
 // streams of the caller, who orders them -- as before.)
-void kdb_launch_forming(kdb_index *idx, std::unique_lock<std::mutex> &lk); // kdb_api.hip: under mu; no-op unless a group waits and a slot is free
-void kdb_close_session(kdb_index *idx); // kdb_api.hip: under mu; the open launch (if any) stops accepting queries: its kernel may end
+void kdb_launch_forming(kdb_index *idx, std::unique_lock<std::mutex> &lk); // kdb_api_calls.hip: under mu; no-op unless a group waits and a slot is free
+void kdb_close_session(kdb_index *idx); // kdb_api_calls.hip: under mu; the open launch (if any) stops accepting queries: its kernel may end
 struct KdbWriteLock {
     kdb_index *idx;
     std::unique_lock<std::mutex> lk;

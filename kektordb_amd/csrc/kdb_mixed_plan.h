@@ -2,7 +2,7 @@
 // a query's effective ef, the capacity a launch needs for its largest one, when a query is valid in a launch, when a late caller
 // may join a running open launch, and the output stride of a launch that stays open.
 //
-// ONE function states each rule: the host plans with them (kdb_api.hip), the kernels apply them per query (search_kernel.cuh,
+// ONE function states each rule: the host plans with them (kdb_api_calls.hip, kdb_api_query.hip), the kernels apply them per query (search_kernel.cuh,
 // search_heap.hip), so the two cannot disagree.  Plain C++, no HIP header: host and device under hipcc, and
 // tests/cpp/mixed_plan_test.cpp builds it alone.
 #ifndef KDB_MIXED_PLAN_H

@@ -194,7 +194,7 @@ extern "C" int kdb_probe_poison_lds(kdb_index *idx, uint32_t pattern) {
     KDB_HIP(hipSetDevice(idx->device));
     constexpr uint32_t LDS_BYTES = 160u * 1024u;
     KDB_HIP(hipFuncSetAttribute((const void *)lds_poison_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BYTES));
-    hipLaunchKernelGGL(lds_poison_kernel, dim3((uint32_t)idx->n_cu * 4u), dim3(256), LDS_BYTES, idx->stream, pattern, LDS_BYTES / 4u, idx->d_work + 13);
+    hipLaunchKernelGGL(lds_poison_kernel, dim3((uint32_t)idx->n_cu * 4u), dim3(256), LDS_BYTES, idx->stream, pattern, LDS_BYTES / 4u, kdb_cur(idx).d_work + 13);
     KDB_HIP(hipGetLastError());
     KDB_HIP(hipStreamSynchronize(idx->stream));
     return KDB_OK;

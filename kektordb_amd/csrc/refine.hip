@@ -271,8 +271,8 @@ int refine_impl(kdb_index *idx, const std::vector<uint32_t> &nodes, uint32_t efc
         rv.t0 = task_of[c0];
         const uint32_t ct = task_of[c0 + rv.cn] - rv.t0;
         KDB_HIP(hipMemsetAsync(rv.cand_cnt, 0, (size_t)ct * 4, s));
-        KDB_HIP(hipMemsetAsync(idx->d_work, 0, 4, s));
-        hipLaunchKernelGGL(ksearch, dim3(slots_vis < rv.cn ? slots_vis : rv.cn), dim3(64), wl.bytes, s, v, rv, wl.beam_cap, wl.nr_cap, idx->d_visited, idx->d_work);
+        KDB_HIP(hipMemsetAsync(kdb_cur(idx).d_work, 0, 4, s));
+        hipLaunchKernelGGL(ksearch, dim3(slots_vis < rv.cn ? slots_vis : rv.cn), dim3(64), wl.bytes, s, v, rv, wl.beam_cap, wl.nr_cap, kdb_cur(idx).d_visited, kdb_cur(idx).d_work);
         KDB_HIP(hipGetLastError());
         hipLaunchKernelGGL(kselect, dim3(ct), dim3(256), lds_prune, s, v, rv);
         KDB_HIP(hipGetLastError());
@@ -394,8 +394,8 @@ int vacuum_scan_launch(kdb_index *idx, hipStream_t s, uint32_t **d_flags, unsign
     const size_t fw = ((size_t)idx->count >> 5) + 1, fb = (fw * 4 + 255) & ~(size_t)255;
     int rc = kdb_ensure_scratch(idx, fb + 256);
     if (rc) return rc;
-    *d_flags = reinterpret_cast<uint32_t *>(idx->d_scratch);
-    *d_links = reinterpret_cast<unsigned long long *>(reinterpret_cast<unsigned char *>(idx->d_scratch) + fb);
+    *d_flags = reinterpret_cast<uint32_t *>(kdb_cur(idx).d_scratch);
+    *d_links = reinterpret_cast<unsigned long long *>(reinterpret_cast<unsigned char *>(kdb_cur(idx).d_scratch) + fb);
     KDB_HIP(hipMemsetAsync(*d_links, 0, 8, s));
     uint32_t lg = 4;
     while ((1u << lg) < idx->deg0) lg++;

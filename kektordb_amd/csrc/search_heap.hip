@@ -787,7 +787,7 @@ int kdb_launch_heap_walk(kdb_index *idx, const KdbView &v, const void *d_q, cons
         static const bool give_up = getenv("KDB_HEAP_OVERLAP_GIVE_UP") != nullptr;
         if (give_up) a.mode = 3u;
     }
-    a.visited_pool = idx->d_visited + (size_t)vis_first * v.vis_words;
+    a.visited_pool = kdb_cur(idx).d_visited + (size_t)vis_first * v.vis_words;
     a.hsize = plan.hsize;
     a.nl_c = plan.nl_c;
     a.cap_c = plan.cap_c;

@@ -455,8 +455,8 @@ static int launch_search_bs(kdb_index *idx, const KdbView &v, const void *d_q, c
             hplan.tail_bytes = ((size_t)hplan.grid * (size_t)(hplan.cap_c - hplan.nl_c) * 12u + 255u) & ~(size_t)255u;
             rc0 = kdb_ensure_tie_scratch(idx, list_bytes + hplan.tail_bytes + 256u + (overlap ? KdbTieStash::bytes(B, k) : 0u));
             if (rc0) return rc0;
-            d_tie_list = reinterpret_cast<uint32_t *>(idx->d_tie);
-            d_tails = reinterpret_cast<unsigned char *>(idx->d_tie) + list_bytes;
+            d_tie_list = reinterpret_cast<uint32_t *>(kdb_cur(idx).d_tie);
+            d_tails = reinterpret_cast<unsigned char *>(kdb_cur(idx).d_tie) + list_bytes;
             if (overlap) d_stash = d_tails + hplan.tail_bytes;
             KDB_HIP(hipMemsetAsync(d_tie_list, 0, 16, s));
             if (overlap) KDB_HIP(hipMemsetAsync(d_tie_list + 4, 0xff, (size_t)B * 4u, s)); // an entry is there once it is not all ones
@@ -485,14 +485,14 @@ static int launch_search_bs(kdb_index *idx, const KdbView &v, const void *d_q, c
         // belong to the call's SCRATCH LANE (words 32..41 of its d_work), not to the statistics ring: two launches that share
         // a lane are ordered by the lane protocol (same stream, or an event wait on the previous user), so a launch never
         // finds the words of another one that is still running -- whatever the number of launches in flight on other streams
-        unsigned long long *d_acc = reinterpret_cast<unsigned long long *>(idx->d_work + 32);
+        unsigned long long *d_acc = reinterpret_cast<unsigned long long *>(kdb_cur(idx).d_work + 32);
         if (idx->time_launches) KDB_HIP(hipEventRecord(idx->ev0, s));
         if (overlap) { // everything queued on s so far (prepared queries, the armed list) is done before the pass starts
             KDB_HIP(hipEventRecord(ln.side_ev0, s));
             KDB_HIP(hipStreamWaitEvent(ln.side, ln.side_ev0, 0));
         }
         hipLaunchKernelGGL(kern, dim3(grid), dim3(64u * waves), lds, s, vk, d_q, d_qnorm, raw_l, B, k, eff, d_allow, ma, entry, beam_cap, nr_cap, vis_size,
-                           idx->d_visited, reinterpret_cast<uint32_t *>(d_acc + 2), d_ctr, d_out_ids, d_out_dist, d_out_count, d_tr_ndist, d_tr_nhops,
+                           kdb_cur(idx).d_visited, reinterpret_cast<uint32_t *>(d_acc + 2), d_ctr, d_out_ids, d_out_dist, d_out_count, d_tr_ndist, d_tr_nhops,
                            d_tie_list, d_stash);
         KDB_HIP(hipGetLastError());
         if (heap_pass) { // (its workgroups return at once when the search kernel queued nothing; the closing event covers both passes:

@@ -1,5 +1,5 @@
 """The shard merge and the allow-list slice restated in plain numpy / Python -- the reference merge_topk_kernel (flat_scan.hip),
-kdb_merge_topk / kdb_merge_topk_f64 (kdb_api.hip) and slice_allow_kernel (cluster.hip) are pinned to.  Same role as filter_ref.py:
+kdb_merge_topk / kdb_merge_topk_f64 (kdb_api_merge.hip) and slice_allow_kernel (cluster.hip) are pinned to.  Same role as filter_ref.py:
 nothing of the library is used here.
 
 The merge has no counterpart in the upstream project (it is single process); its definition is SURVEY section 8e: per query the

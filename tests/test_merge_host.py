@@ -1,4 +1,4 @@
-"""kdb_merge_topk / kdb_merge_topk_f64 (the host merge of the id-range shard, kdb_api.hip) against merge_ref on lists made to
+"""kdb_merge_topk / kdb_merge_topk_f64 (the host merge of the id-range shard, kdb_api_merge.hip) against merge_ref on lists made to
 collide: few distinct distances, short lists, counts that carry KDB_COUNT_TIED, id bases that turn the local id order round.
 No GPU: the two entry points are host code.  tie_heavy_lists is also what tests/test_gpu_shard_merge.py feeds the device merges."""
 import numpy as np
