@@ -85,7 +85,12 @@
  *     components is answered with NO results (out_count 0 -- the reference's "log and return an empty slice" for a search that
  *     fails, hnsw_index.go:356-359; the reference itself compares the NaN distances that follow like any others and returns
  *     whatever its heaps then hold: nothing to be bit-exact with) and never walks; the other queries of the batch -- and of a
- *     launch it was combined into -- are answered bit for bit as alone.  A stored row that yields a distance that is not a
+ *     launch it was combined into -- are answered bit for bit as alone.  "Not finite" is judged on the PREPARED query, the form
+ *     the rows are compared with: on a float16 index a finite component of 65520 or more is an infinity after the float16 round
+ *     trip and the query is such a query (an int8 query is judged on the caller's values: its prepared form is integers); with
+ *     KDB_SEARCH_PREPARED the caller's values are the prepared form.  ONE rule for every entry point: the graph search (either
+ *     walk order), the search by stored id, the exact scans -- out_count 0, ids 0, distances +Inf -- and kdb_distance_batch[_dev],
+ *     which reports +Inf for every candidate of such a query.  A stored row that yields a distance that is not a
  *     number is "infinitely far" in a walk, never nearer than anything.  Every node id is range-checked before a row or list
  *     address is formed from it;
  *   - there is NO CPU fallback: every compute entry point fails with KDB_ERR_NO_DEVICE when no gfx950

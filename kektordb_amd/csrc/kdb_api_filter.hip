@@ -251,6 +251,7 @@ extern "C" int kdb_search_filtered(kdb_index *idx, const float *queries, uint32_
                 rc = kdb_launch_flat_scan_groups(idx, v, d_pq, d_qnorm, n_scan, k, (uint32_t)scan_progs.size(), group_offsets.data(),
                                                  reinterpret_cast<const uint32_t *>(d + o_slists), (uint32_t)(wpl * 2), scan_total, d_ids + (size_t)n_walk * k,
                                                  d_dist + (size_t)n_walk * k, d_cnt + n_walk, 1, s);
+            if (!rc) rc = kdb_launch_void_dead_queries(d_qnorm, n_scan, k, d_ids + (size_t)n_walk * k, d_dist + (size_t)n_walk * k, d_cnt + n_walk, false, s);
         } else if (!rc && n_scan) {
             for (size_t g = 0; g < scan_progs.size() && !rc; g++) {
                 const size_t a = (size_t)n_walk + group_offsets[g];

@@ -315,7 +315,8 @@ int kdb_flat_dev_locked(kdb_index *idx, const float *d_queries, uint32_t B, uint
     rc = kdb_launch_flat_scan(idx, v, d_q, d_qnorm, B, k, d_allow, d_first, d_out_ids, d_out_dist, d_out_count,
                               ((flags & KDB_SEARCH_PREPARED) ? 0 : 1) | ((flags & KDB_SEARCH_DIST_F64) ? 2 : 0), s);
     if (rc) return rc;
-    return KDB_OK;
+    // a query that is not finite once prepared gets no results, as from a walk (include/kektor_hip.h, "Conventions")
+    return kdb_launch_void_dead_queries(d_qnorm, B, k, d_out_ids, d_out_dist, d_out_count, (flags & KDB_SEARCH_DIST_F64) != 0, s);
 }
 
 extern "C" int kdb_flat_scan_groups_dev(kdb_index *idx, const float *d_queries, uint32_t B, uint32_t k, uint32_t G,
@@ -352,10 +353,12 @@ extern "C" int kdb_flat_scan_groups_dev(kdb_index *idx, const float *d_queries, 
     if (rc) return rc;
     rc = kdb_prepare_queries(idx, v, d_queries, B, Bpad, flags, &d_q, &d_qnorm, s);
     if (rc) return rc;
-    return kdb_launch_flat_scan_groups(idx, v, d_q, d_qnorm, B, k, G, group_offsets,
-                                       reinterpret_cast<const uint32_t *>(d_allow_lists), (uint32_t)(words_per_list * 2),
-                                       max_total_allowed, d_out_ids, d_out_dist, d_out_count,
-                                       (flags & KDB_SEARCH_PREPARED) ? 0 : 1, s);
+    rc = kdb_launch_flat_scan_groups(idx, v, d_q, d_qnorm, B, k, G, group_offsets,
+                                     reinterpret_cast<const uint32_t *>(d_allow_lists), (uint32_t)(words_per_list * 2),
+                                     max_total_allowed, d_out_ids, d_out_dist, d_out_count,
+                                     (flags & KDB_SEARCH_PREPARED) ? 0 : 1, s);
+    if (rc) return rc;
+    return kdb_launch_void_dead_queries(d_qnorm, B, k, d_out_ids, d_out_dist, d_out_count, false, s);
 }
 
 extern "C" int kdb_flat_scan_batch_dev(kdb_index *idx, const float *d_queries, uint32_t B, uint32_t k,
@@ -483,8 +486,8 @@ static int by_id_dev_locked(kdb_index *idx, bool flat, const uint32_t *d_ids, ui
     uint32_t *const i_cnt = drop ? reinterpret_cast<uint32_t *>(p + o_cnt) : d_out_count;
     // A source that is not found (id 0, above count, deleted) must get no results.  Graph search: its decoded row is a quiet NaN in
     // every column, and the documented guarantee for queries that are not finite (kektor_hip.h, "Conventions") does the rest -- no
-    // results, a zeroed id row, no walk, no counter touched, the other queries answered bit for bit as alone.  The exact scan has no
-    // such rule: there the row is zeros (an ordinary query) and the epilogue kernel discards its answer.
+    // results, a zeroed id row, no walk, no counter touched, the other queries answered bit for bit as alone.  The exact scan still
+    // scans such a query before it voids the answer: there the row is zeros (an ordinary query) and the epilogue kernel discards it.
     const KdbView v = kdb_make_view(idx);
     rc = kdb_launch_decode_rows(v, d_ids, B, d_q, d_found, flat ? 0u : 0x7fc00000u, s);
     if (rc) return rc;

@@ -312,6 +312,9 @@ inline uint32_t *kdb_stats_shape(kdb_index *idx) { return idx->ring_shape[(idx->
 // search.hip
 int kdb_launch_prep_queries(const KdbView &v, const float *d_in, uint32_t B, void *d_out, float *d_qnorm,
                             int normalize, hipStream_t s);
+// behind an exact scan: the queries prep_queries_kernel marked (d_qnorm <= 0) get the answer a walk gives them -- count 0, ids 0, +Inf
+int kdb_launch_void_dead_queries(const float *d_qnorm, uint32_t B, uint32_t k, uint32_t *d_out_ids, float *d_out_dist, uint32_t *d_out_count,
+                                 bool dist64, hipStream_t s);
 int kdb_launch_group_entries(const KdbView &v, const uint32_t *d_allow_lists, uint32_t G, uint32_t words32, uint32_t entry,
                              uint32_t *d_group_entry, hipStream_t s);
 int kdb_launch_search(kdb_index *idx, const KdbView &v, const void *d_q, const float *d_qnorm, uint32_t raw, uint32_t B,

@@ -523,7 +523,8 @@ __device__ __forceinline__ void compute_dists(const KdbView &v, const WaveLds &s
 // stays untouched (every lane runs the same sequential sum on broadcast LDS reads: no divergence); float16 indexes: the RNE
 // round trip of float16.Fromfloat32 (:425).  Else: a prepared f32 row of `ld` floats.  Shared by the fast walk and the
 // heap-order walk: one preparation, one bit pattern.
-// *dead (wave-uniform): the query holds a component that is not a finite number (a client's bug: one request of a batch).  The
+// *dead (wave-uniform): the query holds a component that is not a finite number, before OR after its preparation -- a float16 index
+// turns a finite component of 65520 or more into an infinity (a client's bug either way: one request of a batch).  The
 // reference compares the NaN distances that follow like any others and returns whatever its heaps then hold
 // (hnsw_index.go:2566-2590) -- nothing to be bit-exact with; here such a query is answered with NO results (out_count = 0, the
 // reference's own "swallow to empty" for a search that fails, :356-359) and never walks; the rest of its batch is untouched.
@@ -573,8 +574,12 @@ __device__ __forceinline__ float kdb_load_query(const KdbView &v, const WaveLds 
                 for (uint32_t i = (uint32_t)lane; i < v.dim; i += 64) s.q[i] = s.q[i] * inv;
             }
         }
-        if (PREC == KDB_PREC_F16) // RNE round trip, as float16.Fromfloat32 (hnsw_index.go:425)
-            for (uint32_t i = (uint32_t)lane; i < v.dim; i += 64) s.q[i] = (float)(_Float16)s.q[i];
+        if (PREC == KDB_PREC_F16) // RNE round trip, as float16.Fromfloat32 (hnsw_index.go:425); a finite component of 65520 or more
+            for (uint32_t i = (uint32_t)lane; i < v.dim; i += 64) { // becomes an infinity here: the PREPARED query decides (as below)
+                const float x = (float)(_Float16)s.q[i];
+                bad = bad || not_finite(x);
+                s.q[i] = x;
+            }
     } else {
         const float4 *src = reinterpret_cast<const float4 *>(reinterpret_cast<const float *>(queries) + (size_t)qi * v.ld);
         float4 *dst = reinterpret_cast<float4 *>(s.q);

@@ -83,7 +83,9 @@ distance_tile_kernel(KdbView v, const void *__restrict__ queries, const float *_
         float key = s.nb_d[lane];
         if constexpr (PREC == KDB_PREC_I8) key = (float)kdb_i8_key_double(key, s.nb_lo[lane]);
         float raw = (PREC == KDB_PREC_F32 && METRIC == KDB_METRIC_COSINE) ? -key : key;
-        out[(size_t)b * C + c0 + lane] = id == 0 ? INFINITY : raw;
+        // a query that prep_queries_kernel marked (a component that is not finite): infinitely far from every row, as it gets no
+        // results from a search
+        out[(size_t)b * C + c0 + lane] = (id == 0 || !(qnorms[b] > 0.f)) ? INFINITY : raw;
     }
 }
 
@@ -136,6 +138,11 @@ prep_queries_kernel(KdbView v, const float *__restrict__ in, uint32_t B, void *o
     }
     __syncthreads();
     const uint32_t i8row = (v.ld + 15) / 16 * 16;
+    // bit r: query b0 + r holds a component that is not finite -- float32 / float16: in its PREPARED form (a float16 index turns a
+    // finite component of 65520 or more into an infinity; a raw NaN or infinity stays one); int8: in the caller's values.  Such a
+    // query is marked with a negative norm (kdb_load_query: no results, no walk; the exact scan and the distance tile: the same)
+    __shared__ uint32_t s_bad;
+    uint32_t badr = 0u;
     if (v.precision != KDB_PREC_I8) { // elementwise: scale (and f16 round trip) with coalesced reads/writes
         for (uint32_t c0 = 0; c0 < v.ld; c0 += 64) {
 #pragma unroll
@@ -147,17 +154,21 @@ prep_queries_kernel(KdbView v, const float *__restrict__ in, uint32_t B, void *o
                     const _Float16 h = (_Float16)x; // RNE, as float16.Fromfloat32 (hnsw_index.go:425)
                     x = (float)h;
                 }
+                if (!(__builtin_fabsf(x) <= 3.402823466e38f)) badr |= 1u << r;
                 reinterpret_cast<float *>(out)[(size_t)(b0 + r) * v.ld + c0 + t] = x;
             }
         }
+        if (t == 0) s_bad = 0u;
+        __syncthreads();
+        if (badr) atomicOr(&s_bad, badr);
+        __syncthreads();
+        if (t < nq) qnorm_out[b] = ((s_bad >> t) & 1u) ? -1.f : 1.f;
         return;
     }
     // int8: Quantizer.Quantize (quantizer.go:150-176) is elementwise too; the query norm (:2411-2418) is an
     // exact integer sum, accumulated per query by one lane
     long long nsum = 0;
-    __shared__ uint32_t s_bad; // bit r: query b0 + r holds a component that is not finite (kdb_load_query: no results, no walk)
     if (t == 0) s_bad = 0u;
-    uint32_t badr = 0u;
     for (uint32_t c0 = 0; c0 < i8row; c0 += 64) {
         __syncthreads();
 #pragma unroll
@@ -192,6 +203,21 @@ prep_queries_kernel(KdbView v, const float *__restrict__ in, uint32_t B, void *o
         const float qn = (float)sqrt((double)nsum);
         qnorm_out[b] = ((s_bad >> t) & 1u) ? -1.f : (qn == 0.f ? 1.f : qn);
     }
+}
+
+// Behind an exact scan, one wave per query: a query that prep_queries_kernel marked with a negative norm (a component that is not
+// finite, in the form the rows are compared with) gets what a walk answers it with -- count 0, ids 0, distances +Inf.
+__global__ void __launch_bounds__(256)
+void_dead_queries_kernel(const float *__restrict__ qnorm, uint32_t B, uint32_t k, uint32_t *out_ids, float *out_dist, uint32_t *out_count,
+                         int dist64) {
+    const uint32_t b = blockIdx.x * 4u + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
+    if (b >= B || qnorm[b] > 0.f) return;
+    for (uint32_t p = lane; p < k; p += 64u) {
+        out_ids[(size_t)b * k + p] = 0u;
+        if (dist64) reinterpret_cast<double *>(out_dist)[(size_t)b * k + p] = (double)INFINITY;
+        else out_dist[(size_t)b * k + p] = INFINITY;
+    }
+    if (lane == 0) out_count[b] = 0u;
 }
 
 // Entry point per allow list of a heterogeneous batch (hnsw_index.go:437-447), one workgroup per list:
@@ -292,6 +318,14 @@ int kdb_launch_prep_queries(const KdbView &v, const float *d_in, uint32_t B, voi
                             int normalize, hipStream_t s) {
     if (B == 0) return KDB_OK;
     hipLaunchKernelGGL(prep_queries_kernel, dim3((B + PQ - 1) / PQ), dim3(64), 0, s, v, d_in, B, d_out, d_qnorm, normalize);
+    KDB_HIP(hipGetLastError());
+    return KDB_OK;
+}
+
+int kdb_launch_void_dead_queries(const float *d_qnorm, uint32_t B, uint32_t k, uint32_t *d_out_ids, float *d_out_dist, uint32_t *d_out_count,
+                                 bool dist64, hipStream_t s) {
+    if (B == 0) return KDB_OK;
+    hipLaunchKernelGGL(void_dead_queries_kernel, dim3((B + 3) / 4), dim3(256), 0, s, d_qnorm, B, k, d_out_ids, d_out_dist, d_out_count, dist64 ? 1 : 0);
     KDB_HIP(hipGetLastError());
     return KDB_OK;
 }
