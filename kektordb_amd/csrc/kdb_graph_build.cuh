@@ -11,12 +11,6 @@ using namespace kdbcore;
 
 namespace {
 
-static_assert(KDB_WALK_MARKS == KDB_UP_MARK_CAP, "the walk plan sizes the un-mark list the layer search fills");
-constexpr bool walk_bs_agrees(uint32_t efc) { return kdb_walk_bs(efc) == (kdb_beam_slots(efc) == 1 ? 2u : (uint32_t)kdb_beam_slots(efc)); }
-static_assert(walk_bs_agrees(1) && walk_bs_agrees(64) && walk_bs_agrees(65) && walk_bs_agrees(128) && walk_bs_agrees(129) && walk_bs_agrees(256) &&
-                  walk_bs_agrees(257) && walk_bs_agrees(512),
-              "the walk plan's beam storage is kdb_beam_slots' (one slot promoted to two)");
-
 constexpr int PR_KC = 128;            // K-chunk (floats) staged per step
 constexpr int PR_STRIDE = PR_KC + 4;  // LDS row stride: 33 sixteen-byte slots -> conflict-free b128 reads
 constexpr int PR_BLK = 32;            // candidates resolved per step

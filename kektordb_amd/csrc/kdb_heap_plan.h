@@ -10,8 +10,8 @@
 #include <initializer_list>
 #include <stddef.h>
 #include <stdint.h>
+#include "kdb_search_plan.h" // the fast walk's visited hash (kdb_vis_hash_size) and un-mark list (KDB_UP_MARK_CAP)
 
-#define KDB_HEAP_MARKS 256u              // un-mark list of the upper layers when the visited set is the HBM bitset (KDB_UP_MARK_CAP)
 #define KDB_HEAP_LDS_LIMIT (160u * 1024u) // LDS of a CU: a plan whose lds + 16 passes it is refused
 
 struct KdbHeapPlan {
@@ -24,10 +24,6 @@ struct KdbHeapPlan {
     size_t tail_bytes; // HBM scratch of all workgroups' candidate-heap tails
 };
 
-// words of the LDS visited hash for an effective ef, 0 = the HBM bitset alone: kdb_vis_hash_size's rule (kdb_search_core.cuh;
-// search_heap.hip asserts the agreement at every boundary -- this header takes no HIP include and cannot call it)
-constexpr uint32_t kdb_heap_hash_words(uint32_t eff) { return eff <= 100u ? 2048u : eff <= 260u ? 4096u : 0u; }
-
 // bytes of one heap entry: id, key, and the low word of a 64-bit key (int8)
 constexpr size_t kdb_heap_entry_bytes(bool wk) { return wk ? 12 : 8; }
 
@@ -35,7 +31,7 @@ constexpr size_t kdb_heap_entry_bytes(bool wk) { return wk ? 12 : 8; }
 // result heap (ef + 2 entries) unless it is in registers | the drain arrays (ef + 2 entries)
 inline size_t kdb_heap_fixed_lds(bool wk, uint32_t ld, uint32_t eff, uint32_t hsize, bool reg_results) {
     const size_t ew = kdb_heap_entry_bytes(wk);
-    return (wk ? ((size_t)ld + 15) / 16 * 16 : (size_t)ld * 4) + 64 * (wk ? 12 : 8) + (hsize ? (size_t)hsize * 4 : KDB_HEAP_MARKS * 4) +
+    return (wk ? ((size_t)ld + 15) / 16 * 16 : (size_t)ld * 4) + 64 * (wk ? 12 : 8) + (hsize ? (size_t)hsize * 4 : KDB_UP_MARK_CAP * 4) +
            (reg_results ? 1 : 2) * (size_t)(eff + 2u) * ew;
 }
 
@@ -51,7 +47,7 @@ inline size_t kdb_heap_tail_bytes(uint32_t grid, uint32_t cap_c, uint32_t nl_c) 
 inline bool kdb_heap_plan_lds(bool wk, uint32_t ld, uint32_t count, uint32_t eff, KdbHeapPlan *out) {
     const size_t ew = kdb_heap_entry_bytes(wk);
     KdbHeapPlan p{};
-    p.hsize = kdb_heap_hash_words(eff); // 2048 / 4096 words up to ef 260, beyond: the HBM bitset
+    p.hsize = kdb_vis_hash_size(eff); // 2048 / 4096 words up to ef 260, beyond: the HBM bitset
     p.reg_results = p.hsize != 0 && eff + 2u <= 64u; // the result heap in registers (entry i in lane i)
     const size_t fixed = kdb_heap_fixed_lds(wk, ld, eff, p.hsize, p.reg_results != 0);
     const uint64_t cap64 = (uint64_t)16u * eff > 2048u ? (uint64_t)16u * eff : 2048u;

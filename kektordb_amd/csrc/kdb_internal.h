@@ -9,6 +9,7 @@
 #include <string>
 #include <vector>
 #include "../../include/kektor_hip.h"
+#include "kdb_search_plan.h" // KDB_UP_MARK_CAP, kdb_beam_slots, kdb_vis_hash_size: the class rules of a walk
 #include "kdb_mixed_plan.h"
 #include "kdb_heap_plan.h"
 
@@ -16,7 +17,6 @@
 #define KDB_F_EXPANDED 0x80000000u  // beam entry already expanded (popped)
 #define KDB_F_NORESULT 0x40000000u  // traversal-only entry: deleted node / entry point outside the allow-list
 #define KDB_MAX_DEG0 64u            // mMax0 = 2m <= 64
-#define KDB_UP_MARK_CAP 256u        // upper-layer visited un-mark list (per wave, LDS); overflow -> full clear
 
 constexpr uint32_t KDB_NO_SLOT = 0xffffffffu;
 
@@ -212,7 +212,7 @@ struct kdb_index {
     bool time_launches = true;  // HIP events around the graph-search kernel (kdb_index_set_launch_timing)
     uint32_t ring_B[RING] = {}, ring_C[RING] = {};
     // which hnsw_search_kernel (and heap_walk_kernel) a graph-search launch took: the words of kdb_probe_launch_shape (test hook),
-    // written by launch_search_bs / kdb_launch_heap_walk for the slot kdb_stats_begin has just opened; zero for every other kind
+    // written by kdb_launch_search_cell / kdb_launch_heap_walk for the slot kdb_stats_begin has just opened; zero for every other kind
     uint32_t ring_shape[RING][KDB_LAUNCH_SHAPE_WORDS] = {};
     uint64_t launch_seq = 0;
     alignas(64) std::mutex mu; // (a cache line boundary: what is guarded by mu does not share a line with the statistics ring in front of it)

@@ -10,6 +10,7 @@
 #include <stddef.h>
 #include <stdint.h>
 #include "../../include/kektor_hip.h"
+#include "kdb_search_plan.h"
 
 #if defined(__HIPCC__)
 #define KDB_MIXED_HD __host__ __device__
@@ -40,14 +41,10 @@ KDB_MIXED_HD constexpr uint32_t kdb_mixed_effective_ef(uint32_t ef, uint32_t k, 
     return e < k ? k : e;
 }
 
-// Beam storage for an effective ef: 1, 2 or 4 register slots of 64 entries, 0 = the beam lives in LDS (kdb_beam_slots' rule:
-// kdb_search_core.cuh checks the two against each other)
-KDB_MIXED_HD constexpr int kdb_mixed_beam_class(uint32_t eff) { return eff <= 64u ? 1 : eff <= 128u ? 2 : eff <= 256u ? 4 : 0; }
-
-// Capacity of a launch from its largest effective ef: the top of the register class (a smaller ef inside the class costs the same
-// LDS and registers), the value itself for the LDS beam
+// Capacity of a launch from its largest effective ef: the top of the register class (kdb_beam_slots, kdb_search_plan.h: 1, 2 or 4
+// slots of 64 entries -- a smaller ef inside the class costs the same LDS and registers), the value itself for the LDS beam
 KDB_MIXED_HD constexpr uint32_t kdb_mixed_ef_cap(uint32_t eff_max) {
-    const int c = kdb_mixed_beam_class(eff_max);
+    const int c = kdb_beam_slots(eff_max);
     return c ? 64u * (uint32_t)c : eff_max;
 }
 

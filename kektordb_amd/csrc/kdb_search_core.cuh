@@ -1901,32 +1901,6 @@ __device__ void search_layer_wide(const KdbView &v, const WaveLds &s, BeamT &b, 
     ctr.n_dropped += nr.dropped;
 }
 
-// LDS hash-set size (words) for ef; 0 = use the HBM bitset
-__host__ __device__ constexpr uint32_t kdb_vis_hash_size(uint32_t ef) { // (constexpr: search_heap.hip checks kdb_heap_plan.h's rule against it)
-    if (ef <= 100) return 2048; // the set holds the ~9*ef ids a query evaluates
-    if (ef <= 260) return 4096;
-    return 0;
-}
-
-// ... and for walks whose batch leaves LDS free (one round of waves at this footprint): ef 261 .. 1040
-__host__ __device__ inline uint32_t kdb_vis_hash_size_large(uint32_t ef) {
-    if (ef <= 260) return 0;
-    if (ef <= 520) return 8192;   // 32 KB: four waves per CU
-    if (ef <= 1040) return 16384; // 64 KB: two waves per CU
-    return 0;
-}
-
-// beam slots needed for ef (the beam never holds more than ef entries); 0 = use the LDS beam
-__host__ __device__ constexpr int kdb_beam_slots(uint32_t ef) { // (constexpr: kdb_graph_build.cuh checks the walk plan's rule against it)
-    const uint32_t need = ef;
-    if (need <= 64) return 1; // one entry per lane: every beam operation stays inside one register
-    if (need <= 128) return 2;
-    if (need <= 256) return 4;
-    return 0; // (six register slots, ef 257..384, lost to the LDS beam's one merge per hop: 1M x 768, k=100, 1024 queries, ef 384: 3.63 ms
-              //  against 2.89 ms at ef 400 -- scripts/ef_probe.py, round 4; the slot count 6 is gone)
-}
-static_assert(kdb_beam_slots(64) == kdb_mixed_beam_class(64) && kdb_beam_slots(65) == kdb_mixed_beam_class(65) && kdb_beam_slots(128) == kdb_mixed_beam_class(128) &&
-                  kdb_beam_slots(129) == kdb_mixed_beam_class(129) && kdb_beam_slots(256) == kdb_mixed_beam_class(256) && kdb_beam_slots(257) == kdb_mixed_beam_class(257),
-              "kdb_mixed_plan.h sizes a mixed launch by kdb_beam_slots' classes");
+// (the class rules of a walk -- kdb_beam_slots, kdb_vis_hash_size, kdb_vis_hash_size_large, KDB_UP_MARK_CAP: kdb_search_plan.h)
 
 } // namespace kdbcore

@@ -6,14 +6,15 @@
 #ifndef KDB_WALK_LDS_H
 #define KDB_WALK_LDS_H
 #include <stdint.h>
+#include "kdb_search_plan.h"
+
+#define KDB_WALK_MARKS KDB_UP_MARK_CAP // un-mark list of the upper layers: the layer search's own constant under the name walk_plan_test.cpp checks
 
 #if defined(__HIPCC__)
 #define KDB_WALK_HD __host__ __device__
 #else
 #define KDB_WALK_HD
 #endif
-
-#define KDB_WALK_MARKS 256u // un-mark list of the upper layers (KDB_UP_MARK_CAP)
 
 // NrList: a walk can never hold more of them than the index has deleted nodes (+ the entry point when a filter excludes it), so
 // up to 2047 deleted nodes the list cannot overflow; beyond that it holds the 2048 nearest pending ones and counts what it drops
@@ -22,9 +23,9 @@ KDB_WALK_HD static inline uint32_t kdb_nr_cap(uint32_t n_deleted) {
     return ((n_deleted < 2047u ? n_deleted : 2047u) + 1u + 3u) & ~3u; // traversal-only candidates (deleted nodes)
 }
 
-// register slots of 64 beam entries for efConstruction, 0 = the beam lives in LDS: kdb_beam_slots' rule with one slot promoted to
-// two (kdb_graph_build.cuh asserts the agreement at every boundary; this header takes no HIP include and cannot call it)
-KDB_WALK_HD constexpr uint32_t kdb_walk_bs(uint32_t efc) { return efc <= 128 ? 2u : efc <= 256 ? 4u : 0u; }
+// register slots of 64 beam entries for efConstruction, 0 = the beam lives in LDS: kdb_beam_slots' rule (kdb_search_plan.h) with
+// one slot promoted to two
+KDB_WALK_HD constexpr uint32_t kdb_walk_bs(uint32_t efc) { return kdb_beam_slots(efc) == 1 ? 2u : (uint32_t)kdb_beam_slots(efc); }
 
 // Byte offsets, in this order: query row | beam_d | beam_id | beam_lo | nr_d | nr_id | nr_lo | nb_id | nb_d | nb_lo | marks.
 // A region the walk does not have is empty and shares its offset with the one behind it: the beam is in LDS only when bs == 0
@@ -57,7 +58,7 @@ KDB_WALK_HD static inline KdbWalkLds kdb_walk_lds_cut(bool i8, uint32_t ld, uint
     w.nb_id = take(64 * 4);
     w.nb_d = take(64 * 4);
     w.nb_lo = take(64 * 4 * lo);
-    w.marks = take(KDB_WALK_MARKS * 4);
+    w.marks = take(KDB_UP_MARK_CAP * 4); // un-mark list of the upper layers
     w.bytes = off;
     return w;
 }

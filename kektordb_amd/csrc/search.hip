@@ -19,6 +19,10 @@
 //     evaluate the rows of a hop, wave 1 owns the visited set and prepares the next node while wave 0 inserts
 //     (search_layer_wide / wide_visitor_loop in kdb_search_core.cuh) -- same walk, same counters.
 #include "search_kernel.cuh"
+#include <map>
+#include <mutex>
+#include <stdlib.h>
+#include <tuple>
 
 using namespace kdbcore;
 
@@ -474,14 +478,13 @@ bool kdb_walk_planes_shape(const kdb_index *idx) {
            !(idx->desc.reserved & KDB_INDEX_NO_WALK_PLANES);
 }
 
-// One heap-order pass BESIDE its search kernel at a time per process (launch_any below): the last such launch's closing event.
+// One heap-order pass BESIDE its search kernel at a time per process (kdb_launch_search_cell below): the last such launch's closing event.
 namespace {
 std::mutex g_ov_mu;
 hipEvent_t g_ov_event = nullptr;
 hipStream_t g_ov_stream = nullptr;
 const kdb_index *g_ov_owner = nullptr;
 bool g_ov_pending = false;
-} // namespace
 bool kdb_heap_overlap_begin(const kdb_index *idx, hipStream_t s) { // true: the turn is this launch's (until ..._launched)
     std::lock_guard<std::mutex> lk(g_ov_mu);
     if (g_ov_pending) return false;
@@ -502,6 +505,7 @@ void kdb_heap_overlap_launched(const kdb_index *idx, hipStream_t s, hipEvent_t e
     g_ov_stream = s;
     g_ov_owner = idx;
 }
+} // namespace
 void kdb_heap_overlap_forget(const kdb_index *idx) { // the index is going away (its streams are idle): its events with it
     std::lock_guard<std::mutex> lk(g_ov_mu);
     if (g_ov_owner == idx) {
@@ -511,21 +515,198 @@ void kdb_heap_overlap_forget(const kdb_index *idx) { // the index is going away 
     }
 }
 
+// resident workgroups per CU of a kernel at a given LDS size: asked once per (kernel, size), not per launch
+// (the query costs tens of microseconds on the host -- visible in the latency of small batches)
+int kdb_search_occupancy(KdbSearchKernel kern, int threads, size_t lds) {
+    static std::mutex mu;
+    static std::map<std::tuple<const void *, size_t, int, int>, int> cache; // occupancy is a per-device, per-block-size fact
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    const std::tuple<const void *, size_t, int, int> key(reinterpret_cast<const void *>(kern), lds, dev, threads);
+    std::lock_guard<std::mutex> lk(mu);
+    auto it = cache.find(key);
+    if (it != cache.end()) return it->second;
+    int nb = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, threads, lds) != hipSuccess || nb < 1) nb = 1;
+    cache[key] = nb;
+    return nb;
+}
+
+// The walk planes for a launch that has picked the planes kernel: made by the first such launch, under idx->mu.  *use = false (no
+// room, opted out, another shape): the walk reads the float32 rows as ever.
+int kdb_search_use_planes(kdb_index *idx, KdbView &vk, hipStream_t s, bool *use) {
+    *use = false;
+    if (vk.ld != idx->ld || vk.rows != idx->d_rows || !kdb_walk_planes_shape(idx)) return KDB_OK;
+    const int rc = kdb_ensure_walk_planes(idx, s);
+    if (rc) return rc;
+    if (!idx->d_walk_hi) return KDB_OK;
+    vk.walk_hi = idx->d_walk_hi;
+    vk.walk_lo = idx->d_walk_lo;
+    vk.walk_err = idx->d_walk_err;
+    *use = true;
+    return KDB_OK;
+}
+
+namespace {
+// the launch of a kernel given as a pointer: every argument converted to the parameter's own type, then passed by address
+template <typename... P>
+hipError_t launch_kernel_ptr(void (*kern)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t s, std::common_type_t<P>... p) {
+    void *args[] = {static_cast<void *>(&p)...};
+    return hipLaunchKernel(reinterpret_cast<const void *>(kern), grid, block, args, lds, s);
+}
+} // namespace
+
+// The launch of the cell launch_search_bs (search_kernel.cuh) has picked, with everything around it: the grid, the heap-order pass
+// (reserved and armed before the launch, run behind or beside it), the visited bitsets, the statistics slot and its launch-shape words.
+int kdb_launch_search_cell(const KdbSearchLaunch &a, const KdbView &vk, const KdbSearchCell &c) {
+    kdb_index *const idx = a.idx;
+    const KdbView &v = a.v;
+    const KdbMultiAllow &ma = a.ma;
+    const uint32_t raw = a.raw, B = a.B, k = a.k, eff = c.eff, waves = c.rung.waves, ncu = (uint32_t)idx->n_cu;
+    const size_t lds = c.rung.lds;
+    hipStream_t s = a.s;
+    uint32_t grid = ncu * (uint32_t)kdb_search_occupancy(c.kern, (int)(64u * waves), lds);
+    if (grid > B) grid = B;
+    if (ma.sess_ctl && grid > ma.sess_grid) grid = ma.sess_grid; // an open launch: the first queries' workgroups + spare ones
+    if (grid == 0) return KDB_OK;
+    // KDB_SEARCH_HEAP_ORDER (raw & 16): queries whose walk meets equal distances are queued by the kernel and walked again by
+    // heap_walk_kernel (search_heap.hip) behind it -- everything it needs is allocated and armed BEFORE the launch
+    const bool heap_pass = (raw & 16u) != 0u;
+    uint32_t hgrid = 0;
+    KdbHeapPlan hplan{};
+    uint32_t *d_tie_list = nullptr;
+    unsigned char *d_tails = nullptr, *d_stash = nullptr;
+    // Large batches: the heap-order pass runs BESIDE the search kernel, on the lane's side stream -- its workgroups take tied
+    // queries as the search kernel queues them (the pass used to take as long as its longest walk, 1.2 ms behind 7.7, with the
+    // chip nearly idle).  The search kernel leaves room for ov_wg (1) of them per CU; the rest of the pass's grid
+    // moves in as search workgroups leave.  The search kernel is launched FIRST: if the two streams share a hardware queue the
+    // pass simply runs behind it, as before.  Small launches (and open ones) keep the pass behind the kernel on the same stream.
+    static const uint32_t ov_min_b = [] { const char *e = getenv("KDB_HEAP_OVERLAP_MIN_B"); return e ? (uint32_t)atoi(e) : 4096u; }();
+    constexpr uint32_t ov_wg = 1u;
+    bool overlap = false;
+    uint32_t raw_l = raw;
+    struct OvGuard { // (an error between the reservation and the launch gives the turn back)
+        bool armed = false;
+        ~OvGuard() { if (armed) kdb_heap_overlap_launched(nullptr, nullptr, nullptr); }
+    } ov_guard;
+    if (heap_pass) {
+        int rc0 = kdb_heap_walk_plan(idx, v, eff, k, B, &hplan);
+        if (rc0) return rc0;
+        hgrid = hplan.grid;
+        const size_t lds_room = 160u * 1024u - 2048u; // (allocation granularity)
+        if (ov_min_b && B >= ov_min_b && waves == 1u && !ma.sess_ctl && !ma.done_flags && lds + hplan.lds <= lds_room) {
+            uint32_t per_cu = grid / ncu; // grid == ncu * occupancy here (B >= 4096)
+            if (per_cu >= 2u && grid == per_cu * ncu) {
+                while (per_cu > 1u && (size_t)per_cu * lds + (size_t)ov_wg * hplan.lds > lds_room) per_cu--;
+                // were every workgroup of the pass resident before the first of the search kernel, one of those would still fit
+                // on some CU: the pass waits for the search kernel, never the other way round
+                // ... and never more than ov_cap (7) per CU (measured at 1637 tied of 32768: cap 7 8.94 ms, 5 9.32, 3 9.53,
+                // 1 11.8 -- under a search kernel that saturates HBM the walks are slow, most ties are still there when it ends)
+                constexpr uint32_t ov_cap = 7u;
+                uint32_t per_cu_h = (uint32_t)((lds_room - lds) / hplan.lds);
+                if (per_cu_h > ov_cap) per_cu_h = ov_cap;
+                const uint32_t h_cap = ncu * per_cu_h;
+                // ONE such launch at a time per process (two passes waiting for two search kernels could hold every CU's LDS between
+                // them): the previous one has finished, or it is ordered before this one (same stream)
+                if (h_cap >= ncu && kdb_heap_overlap_begin(idx, s)) {
+                    overlap = true;
+                    ov_guard.armed = true;
+                    grid = per_cu * ncu;
+                    if (hgrid > h_cap) hgrid = h_cap;
+                    hplan.grid = hgrid;
+                    raw_l |= 32u;
+                }
+            }
+        }
+        // (Round 6 tried the pass BESIDE the kernel for open launches too -- 16 workgroups on the side stream taking tied queries as
+        // tickets while the launch still accepts callers.  64 one-query callers with the flag: 172 k QPS / p99 1.10 ms before,
+        // 141 k / 1.11 with it: a tied query's latency is its heap-order WALK (0.3 - 1.2 ms, long walks tie), not the wait for the
+        // launch to close, and three launches + two memsets per open launch cost the launching thread more than they saved.)
+        const size_t list_bytes = (((size_t)B + 4u) * 4u + 255u) & ~(size_t)255u;
+        hplan.tail_bytes = ((size_t)hplan.grid * (size_t)(hplan.cap_c - hplan.nl_c) * 12u + 255u) & ~(size_t)255u;
+        rc0 = kdb_ensure_tie_scratch(idx, list_bytes + hplan.tail_bytes + 256u + (overlap ? KdbTieStash::bytes(B, k) : 0u));
+        if (rc0) return rc0;
+        d_tie_list = reinterpret_cast<uint32_t *>(kdb_cur(idx).d_tie);
+        d_tails = reinterpret_cast<unsigned char *>(kdb_cur(idx).d_tie) + list_bytes;
+        if (overlap) d_stash = d_tails + hplan.tail_bytes;
+        KDB_HIP(hipMemsetAsync(d_tie_list, 0, 16, s));
+        if (overlap) KDB_HIP(hipMemsetAsync(d_tie_list + 4, 0xff, (size_t)B * 4u, s)); // an entry is there once it is not all ones
+    }
+    // (side by side, the two kernels' workgroups have visited bitsets of their own)
+    int rc = kdb_ensure_visited(idx, overlap ? grid + hgrid : (grid > hgrid ? grid : hgrid), s);
+    if (rc) return rc;
+    struct kdb_lane &ln = idx->lanes[idx->cur_lane];
+    if (overlap) {
+        if (!ln.side) {
+            int lo = 0, hi = 0;
+            (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
+            KDB_HIP(hipStreamCreateWithPriority(&ln.side, hipStreamNonBlocking, hi));
+            KDB_HIP(hipEventCreateWithFlags(&ln.side_ev0, hipEventDisableTiming));
+            KDB_HIP(hipEventCreateWithFlags(&ln.side_ev1, hipEventDisableTiming));
+        }
+    }
+    unsigned long long *d_ctr = kdb_stats_begin(idx, 1, B, 0);
+    { // test hook (kdb_probe_launch_shape): the instantiation this launch takes, in the statistics slot just opened
+        uint32_t *const shp = kdb_stats_shape(idx);
+        shp[0] = 1u, shp[1] = (uint32_t)c.prec, shp[2] = (uint32_t)c.metric, shp[3] = (uint32_t)c.nch, shp[4] = (uint32_t)c.bs;
+        shp[5] = c.rung.vis_words, shp[6] = waves, shp[7] = c.rung.planes ? 1u : 0u, shp[8] = heap_pass ? 1u : 0u;
+        shp[13] = grid, shp[14] = (uint32_t)lds, shp[15] = B;
+    }
+    // the launch's accumulators {n_dist, n_hops, work | done, dropped}: zero between launches (see the kernel's end).  They
+    // belong to the call's SCRATCH LANE (words 32..41 of its d_work), not to the statistics ring: two launches that share
+    // a lane are ordered by the lane protocol (same stream, or an event wait on the previous user), so a launch never
+    // finds the words of another one that is still running -- whatever the number of launches in flight on other streams
+    unsigned long long *d_acc = reinterpret_cast<unsigned long long *>(kdb_cur(idx).d_work + 32);
+    if (idx->time_launches) KDB_HIP(hipEventRecord(idx->ev0, s));
+    if (overlap) { // everything queued on s so far (prepared queries, the armed list) is done before the pass starts
+        KDB_HIP(hipEventRecord(ln.side_ev0, s));
+        KDB_HIP(hipStreamWaitEvent(ln.side, ln.side_ev0, 0));
+    }
+    KDB_HIP(launch_kernel_ptr(c.kern, dim3(grid), dim3(64u * waves), lds, s, vk, a.d_q, a.d_qnorm, raw_l, B, k, eff, a.d_allow, ma, a.entry, c.beam_cap, c.nr_cap,
+                              c.rung.vis_words, kdb_cur(idx).d_visited, reinterpret_cast<uint32_t *>(d_acc + 2), d_ctr, a.d_out_ids, a.d_out_dist,
+                              a.d_out_count, a.d_tr_ndist, a.d_tr_nhops, d_tie_list, d_stash));
+    if (heap_pass) { // (its workgroups return at once when the search kernel queued nothing; the closing event covers both passes:
+        // the second one adds its counters to the slot the first one published)
+        rc = kdb_launch_heap_walk(idx, v, a.d_q, a.d_qnorm, raw_l, B, k, eff, a.d_allow, ma, a.entry, d_tie_list, d_tails, hplan, d_ctr, a.d_out_ids,
+                                  a.d_out_dist, a.d_out_count, a.d_tr_ndist, a.d_tr_nhops, overlap ? ln.side : s, overlap ? grid : 0u, d_stash, overlap ? 1u : 0u);
+        if (overlap) { // s carries on when the pass is done (the search kernel closes the list as it ends, whatever happened here)
+            if (rc == KDB_OK && hipEventRecord(ln.side_ev1, ln.side) != hipSuccess) rc = KDB_ERR_HIP;
+            if (hipStreamWaitEvent(s, ln.side_ev1, 0) != hipSuccess && rc == KDB_OK) rc = KDB_ERR_HIP;
+            kdb_heap_overlap_launched(idx, s, ln.side_ev1);
+            ov_guard.armed = false;
+            // the sweep: entries the pass did not walk (none, unless its workgroups gave up waiting) -- workgroups that find
+            // every entry marked return at once
+            if (rc == KDB_OK) {
+                KdbHeapPlan sweep = hplan; // (one workgroup per CU: enough for what is never there)
+                if (sweep.grid > ncu) sweep.grid = ncu;
+                rc = kdb_launch_heap_walk(idx, v, a.d_q, a.d_qnorm, raw_l, B, k, eff, a.d_allow, ma, a.entry, d_tie_list, d_tails, sweep, d_ctr, a.d_out_ids,
+                                          a.d_out_dist, a.d_out_count, a.d_tr_ndist, a.d_tr_nhops, s, grid, d_stash, 2u);
+            }
+        }
+        if (rc) return rc;
+    }
+    if (idx->time_launches) KDB_HIP(hipEventRecord(idx->ev1, s));
+    return KDB_OK;
+}
+
 // hnsw_search_kernel is instantiated by search_inst.hip, one translation unit per (precision, metric, row-width group)
-#define KDB_DECL_INST(P, M, G) int kdb_launch_search_inst_##P##_##M##_##G(KDB_LAUNCH_SEARCH_PARAMS);
+#define KDB_DECL_INST(P, M, G) int kdb_launch_search_inst_##P##_##M##_##G(const KdbSearchLaunch &a);
 KDB_DECL_INST(0, 0, 0) KDB_DECL_INST(0, 0, 1) KDB_DECL_INST(0, 0, 2)
 KDB_DECL_INST(0, 1, 0) KDB_DECL_INST(0, 1, 1) KDB_DECL_INST(0, 1, 2)
 KDB_DECL_INST(1, 0, 0) KDB_DECL_INST(2, 1, 0)
 #undef KDB_DECL_INST
 
-int kdb_launch_search(KDB_LAUNCH_SEARCH_PARAMS) {
+int kdb_launch_search(kdb_index *idx, const KdbView &v, const void *d_q, const float *d_qnorm, uint32_t raw, uint32_t B, uint32_t k, uint32_t ef,
+                      const uint32_t *d_allow, KdbMultiAllow ma, uint32_t entry, uint32_t *d_out_ids, float *d_out_dist, uint32_t *d_out_count,
+                      uint32_t *d_tr_ndist, uint32_t *d_tr_nhops, hipStream_t s) {
+    const KdbSearchLaunch a{idx, v, d_q, d_qnorm, raw, B, k, ef, d_allow, ma, entry, d_out_ids, d_out_dist, d_out_count, d_tr_ndist, d_tr_nhops, s};
     if (v.precision == KDB_PREC_F32) { // common row widths get fully unrolled row loads (NCH = ld/64): group 0 = 128..512, 1 = 768 / 1024, 2 = 1536 + any other
         const int g = ((v.ld > 64 && v.ld <= 128) || v.ld == 256 || v.ld == 384 || v.ld == 512) ? 0 : (v.ld == 768 || v.ld == 1024) ? 1 : 2;
-        if (v.metric == KDB_METRIC_L2) return g == 0 ? kdb_launch_search_inst_0_0_0(KDB_LAUNCH_SEARCH_ARGS) : g == 1 ? kdb_launch_search_inst_0_0_1(KDB_LAUNCH_SEARCH_ARGS) : kdb_launch_search_inst_0_0_2(KDB_LAUNCH_SEARCH_ARGS);
-        if (v.metric == KDB_METRIC_COSINE) return g == 0 ? kdb_launch_search_inst_0_1_0(KDB_LAUNCH_SEARCH_ARGS) : g == 1 ? kdb_launch_search_inst_0_1_1(KDB_LAUNCH_SEARCH_ARGS) : kdb_launch_search_inst_0_1_2(KDB_LAUNCH_SEARCH_ARGS);
+        if (v.metric == KDB_METRIC_L2) return g == 0 ? kdb_launch_search_inst_0_0_0(a) : g == 1 ? kdb_launch_search_inst_0_0_1(a) : kdb_launch_search_inst_0_0_2(a);
+        if (v.metric == KDB_METRIC_COSINE) return g == 0 ? kdb_launch_search_inst_0_1_0(a) : g == 1 ? kdb_launch_search_inst_0_1_1(a) : kdb_launch_search_inst_0_1_2(a);
     }
-    if (v.precision == KDB_PREC_F16 && v.metric == KDB_METRIC_L2) return kdb_launch_search_inst_1_0_0(KDB_LAUNCH_SEARCH_ARGS);
-    if (v.precision == KDB_PREC_I8 && v.metric == KDB_METRIC_COSINE) return kdb_launch_search_inst_2_1_0(KDB_LAUNCH_SEARCH_ARGS);
+    if (v.precision == KDB_PREC_F16 && v.metric == KDB_METRIC_L2) return kdb_launch_search_inst_1_0_0(a);
+    if (v.precision == KDB_PREC_I8 && v.metric == KDB_METRIC_COSINE) return kdb_launch_search_inst_2_1_0(a);
     kdb_set_error("unsupported precision/metric combination");
     return KDB_ERR_UNSUPPORTED;
 }

@@ -743,13 +743,8 @@ int heap_dispatch(const KdbView &v, bool hash, bool reg, bool ov, F f) {
 // accepted neighbour of a layer search minus one pop per hop: a few ef at its largest) -- so that a few thousand tied queries all
 // walk at once; the rest of the candidate heap (up to cap_c entries: 16 ef, at least 2048) in HBM scratch, per workgroup.  (Round 4
 // gave every wave 60 KB and 64 ef entries of tail whatever ef was: two waves per CU, 480 MB of tails per scratch lane.)
-// The arithmetic is kdb_heap_plan.h's (tests/cpp/heap_plan_test.cpp checks it against the carve of heap_walk_kernel above); it
-// restates two rules of the fast walk, checked here at every boundary:
-static_assert(KDB_HEAP_MARKS == KDB_UP_MARK_CAP, "the plan sizes the un-mark list the layer search fills");
-static_assert(kdb_heap_hash_words(1) == kdb_vis_hash_size(1) && kdb_heap_hash_words(100) == kdb_vis_hash_size(100) &&
-                  kdb_heap_hash_words(101) == kdb_vis_hash_size(101) && kdb_heap_hash_words(260) == kdb_vis_hash_size(260) &&
-                  kdb_heap_hash_words(261) == kdb_vis_hash_size(261) && kdb_heap_hash_words(0xffffffffu) == kdb_vis_hash_size(0xffffffffu),
-              "the plan sizes the visited hash the fast walk uses");
+// The arithmetic is kdb_heap_plan.h's (tests/cpp/heap_plan_test.cpp checks it against the carve of heap_walk_kernel above); the
+// visited hash and the un-mark list are the fast walk's (kdb_search_plan.h).
 int kdb_heap_walk_plan(kdb_index *idx, const KdbView &v, uint32_t ef, uint32_t k, uint32_t B, KdbHeapPlan *out) {
     const uint32_t eff = kdb_mixed_effective_ef(ef, k, false); // (a mixed launch: its capacity and its stride -- LDS and heaps hold every query of it)
     KdbHeapPlan p{};

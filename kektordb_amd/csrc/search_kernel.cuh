@@ -1,24 +1,41 @@
-// search_kernel.cuh -- hnsw_search_kernel and its launch logic, shared by the translation units that instantiate it
+// search_kernel.cuh -- hnsw_search_kernel and the templated step of its launch (the plan: kdb_search_plan.h; the launch: search.hip), shared by the translation units that instantiate it
 // (search_inst.hip, compiled once per precision / metric / row-width group so that `make -j` builds them side by side: the one
 // file took 8.5 minutes to compile).  Design notes: search.hip.
 #pragma once
 #include "kdb_search_core.cuh"
 #include "kdb_walk_lds.h"
-#include <map>
-#include <tuple>
-#include <mutex>
 #include <stdio.h>
-#include <stdlib.h>
 
-// one heap-order pass BESIDE its search kernel at a time per process (search.hip)
-bool kdb_heap_overlap_begin(const kdb_index *idx, hipStream_t s);
-void kdb_heap_overlap_launched(const kdb_index *idx, hipStream_t s, hipEvent_t ev);
-
-#define KDB_LAUNCH_SEARCH_PARAMS                                                                                                    \
-    kdb_index *idx, const KdbView &v, const void *d_q, const float *d_qnorm, uint32_t raw, uint32_t B, uint32_t k, uint32_t ef,        \
-        const uint32_t *d_allow, KdbMultiAllow ma, uint32_t entry, uint32_t *d_out_ids, float *d_out_dist, uint32_t *d_out_count,      \
-        uint32_t *d_tr_ndist, uint32_t *d_tr_nhops, hipStream_t s
-#define KDB_LAUNCH_SEARCH_ARGS idx, v, d_q, d_qnorm, raw, B, k, ef, d_allow, ma, entry, d_out_ids, d_out_dist, d_out_count, d_tr_ndist, d_tr_nhops, s
+// What kdb_launch_search was called with: filled once there, passed by reference down to the launch
+struct KdbSearchLaunch {
+    kdb_index *idx;
+    const KdbView &v;
+    const void *d_q;
+    const float *d_qnorm;
+    uint32_t raw, B, k, ef;
+    const uint32_t *d_allow;
+    const KdbMultiAllow &ma;
+    uint32_t entry, *d_out_ids;
+    float *d_out_dist;
+    uint32_t *d_out_count, *d_tr_ndist, *d_tr_nhops;
+    hipStream_t s;
+};
+// every instantiation of hnsw_search_kernel has this signature
+using KdbSearchKernel = void (*)(KdbView, const void *, const float *, uint32_t, uint32_t, uint32_t, uint32_t, const uint32_t *, KdbMultiAllow, uint32_t,
+                                 uint32_t, uint32_t, uint32_t, uint32_t *, uint32_t *, unsigned long long *, uint32_t *, float *, uint32_t *, uint32_t *,
+                                 uint32_t *, uint32_t *, unsigned char *);
+// The cell a launch has picked: the instantiation (what the launch-shape hook reports of it), the rung of its ladder
+// (kdb_search_plan.h), and the sizes the kernel is told
+struct KdbSearchCell {
+    KdbSearchKernel kern;
+    int prec, metric, nch, bs;
+    KdbSearchRung rung; // (rung.planes: the planes kernel was picked -- the view passed carries the walk planes)
+    uint32_t eff, beam_cap, nr_cap;
+};
+// search.hip: what a launch needs from the device, once in the library
+int kdb_search_occupancy(KdbSearchKernel kern, int threads, size_t lds);
+int kdb_search_use_planes(kdb_index *idx, KdbView &vk, hipStream_t s, bool *use);
+int kdb_launch_search_cell(const KdbSearchLaunch &a, const KdbView &vk, const KdbSearchCell &c);
 
 namespace {
 using namespace kdbcore;
@@ -347,291 +364,55 @@ hnsw_search_kernel(KdbView v, const void *__restrict__ queries, const float *__r
     }
 }
 
-// resident workgroups per CU of a kernel at a given LDS size: asked once per (kernel, size), not per launch
-// (the query costs tens of microseconds on the host -- visible in the latency of small batches)
-template <typename K>
-int occupancy_blocks(K kern, int threads, size_t lds) {
-    static std::mutex mu;
-    static std::map<std::tuple<const void *, size_t, int, int>, int> cache; // occupancy is a per-device, per-block-size fact
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    const std::tuple<const void *, size_t, int, int> key(reinterpret_cast<const void *>(kern), lds, dev, threads);
-    std::lock_guard<std::mutex> lk(mu);
-    auto it = cache.find(key);
-    if (it != cache.end()) return it->second;
-    int nb = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, threads, lds) != hipSuccess || nb < 1) nb = 1;
-    cache[key] = nb;
-    return nb;
+// the instantiation of a rung: the only templated part of the launch, and what instantiates the kernels
+template <int PREC, int METRIC, int NCH, int BS>
+static KdbSearchKernel search_kernel_of(const KdbSearchRung &r, bool planes) {
+    if constexpr (BS != 0) { // register beams: the LDS hash, always
+        if constexpr (kdb_planes_kernel<PREC, METRIC, NCH>()) {
+            if (planes) return hnsw_search_kernel<PREC, METRIC, NCH, BS, 1, 1, 1>;
+        }
+        return r.waves == 4u ? hnsw_search_kernel<PREC, METRIC, NCH, BS, 1, 4> : r.waves == 2u ? hnsw_search_kernel<PREC, METRIC, NCH, BS, 1, 2> : hnsw_search_kernel<PREC, METRIC, NCH, BS, 1>;
+    } else {
+        if (r.hash) return r.waves == 4u ? hnsw_search_kernel<PREC, METRIC, NCH, 0, 1, 4> : r.waves == 2u ? hnsw_search_kernel<PREC, METRIC, NCH, 0, 1, 2> : hnsw_search_kernel<PREC, METRIC, NCH, 0, 1>;
+        return r.waves == 4u ? hnsw_search_kernel<PREC, METRIC, NCH, 0, 0, 4> : r.waves == 2u ? hnsw_search_kernel<PREC, METRIC, NCH, 0, 0, 2> : hnsw_search_kernel<PREC, METRIC, NCH, 0, 0>;
+    }
 }
 
 template <int PREC, int METRIC, int NCH, int BS>
-static int launch_search_bs(kdb_index *idx, const KdbView &v, const void *d_q, const float *d_qnorm, uint32_t raw, uint32_t B,
-                            uint32_t k, uint32_t ef, const uint32_t *d_allow, KdbMultiAllow ma, uint32_t entry, uint32_t *d_out_ids,
-                            float *d_out_dist, uint32_t *d_out_count, uint32_t *d_tr_ndist, uint32_t *d_tr_nhops,
-                            hipStream_t s) {
-    // ef = max(efSearch, k) (:2377-2380); a mixed launch: k is the stride and ef the capacity the caller worked out (ef_cap)
-    const uint32_t eff = ma.k_of_query ? ef : kdb_mixed_effective_ef(ef, k, false);
-    const uint32_t beam_cap = ((eff + 2) + 63) / 64 * 64; // LDS beam (BS == 0)
-    const uint32_t nr_cap = kdb_nr_cap(idx->n_deleted); // traversal-only candidates (NrList): the rule is kdb_walk_lds.h's, shared with the construction walks
-    const size_t qb = PREC == KDB_PREC_I8 ? ((size_t)v.ld + 15) / 16 * 16 : (size_t)v.ld * 4;
-    constexpr bool WK = PREC == KDB_PREC_I8; // 64-bit distance keys: one more word per beam / neighbour / pending entry
-    const size_t lds_common = qb + (BS == 0 ? (size_t)beam_cap * (WK ? 12 : 8) : 0) + 64 * (WK ? 12 : 8) + (size_t)nr_cap * (WK ? 12 : 8) +
-                              (BS >= 2 ? (size_t)64 * BS * 8 : 0); // (scatter scratch of the one-pass insertion of a multi-slot register beam)
-    // visited set: LDS hash (spilling to the HBM bitset if it ever fills) on the register-beam kernels,
-    // the HBM bitset alone for large ef
-    const uint32_t hsize = (BS == 1 || BS == 2 || BS == 4) ? kdb_vis_hash_size(eff) : 0u;
-    const size_t lds1 = lds_common + (hsize ? (size_t)hsize * 4 : KDB_UP_MARK_CAP * 4);
-    if (lds1 + 16 > 160 * 1024) {
-        kdb_set_error("ef=%u needs %zu bytes of LDS per wave (limit 160 KiB)", eff, lds1);
+static int launch_search_bs(const KdbSearchLaunch &a, uint32_t eff) {
+    const uint32_t nr_cap = kdb_nr_cap(a.idx->n_deleted); // traversal-only candidates (NrList): the rule is kdb_walk_lds.h's, shared with the construction walks
+    const KdbSearchLadder lad = kdb_search_ladder(PREC == KDB_PREC_I8, a.v.ld, eff, nr_cap);
+    if (!lad.n) {
+        kdb_set_error("ef=%u needs %zu bytes of LDS per wave (limit 160 KiB)", eff, lad.lds1);
         return KDB_ERR_UNSUPPORTED;
     }
-    const uint32_t ncu = (uint32_t)idx->n_cu;
-    // latency mode: a four times larger hash set (LDS is plentiful with one or two workgroups per CU): the visited test is a
-    // compare-and-swap probe loop that ends when the slowest of 32 lanes has found its slot -- at a load below 7 % that is
-    // two rounds, not three
-    const uint32_t hsize_w = hsize ? (hsize * 4u > 16384u ? 16384u : hsize * 4u) : 0u;
-    KdbView vk = v; // the search kernel's view: with the walk planes once a planes kernel has been picked (use_planes)
-    auto launch_any = [&](auto kern, uint32_t vis_size, uint32_t waves, size_t lds, bool planes = false) -> int {
-        if (lds > 64 * 1024) KDB_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        uint32_t grid = ncu * (uint32_t)occupancy_blocks(kern, (int)(64u * waves), lds);
-        if (grid > B) grid = B;
-        if (ma.sess_ctl && grid > ma.sess_grid) grid = ma.sess_grid; // an open launch: the first queries' workgroups + spare ones
-        if (grid == 0) return KDB_OK;
-        // KDB_SEARCH_HEAP_ORDER (raw & 16): queries whose walk meets equal distances are queued by the kernel and walked again by
-        // heap_walk_kernel (search_heap.hip) behind it -- everything it needs is allocated and armed BEFORE the launch
-        const bool heap_pass = (raw & 16u) != 0u;
-        uint32_t hgrid = 0;
-        KdbHeapPlan hplan{};
-        uint32_t *d_tie_list = nullptr;
-        unsigned char *d_tails = nullptr, *d_stash = nullptr;
-        // Large batches: the heap-order pass runs BESIDE the search kernel, on the lane's side stream -- its workgroups take tied
-        // queries as the search kernel queues them (the pass used to take as long as its longest walk, 1.2 ms behind 7.7, with the
-        // chip nearly idle).  The search kernel leaves room for ov_wg (1) of them per CU; the rest of the pass's grid
-        // moves in as search workgroups leave.  The search kernel is launched FIRST: if the two streams share a hardware queue the
-        // pass simply runs behind it, as before.  Small launches (and open ones) keep the pass behind the kernel on the same stream.
-        static const uint32_t ov_min_b = [] { const char *e = getenv("KDB_HEAP_OVERLAP_MIN_B"); return e ? (uint32_t)atoi(e) : 4096u; }();
-        constexpr uint32_t ov_wg = 1u;
-        bool overlap = false;
-        uint32_t raw_l = raw;
-        struct OvGuard { // (an error between the reservation and the launch gives the turn back)
-            bool armed = false;
-            ~OvGuard() { if (armed) kdb_heap_overlap_launched(nullptr, nullptr, nullptr); }
-        } ov_guard;
-        if (heap_pass) {
-            int rc0 = kdb_heap_walk_plan(idx, v, eff, k, B, &hplan);
-            if (rc0) return rc0;
-            hgrid = hplan.grid;
-            const size_t lds_room = 160u * 1024u - 2048u; // (allocation granularity)
-            if (ov_min_b && B >= ov_min_b && waves == 1u && !ma.sess_ctl && !ma.done_flags && lds + hplan.lds <= lds_room) {
-                uint32_t per_cu = grid / ncu; // grid == ncu * occupancy here (B >= 4096)
-                if (per_cu >= 2u && grid == per_cu * ncu) {
-                    while (per_cu > 1u && (size_t)per_cu * lds + (size_t)ov_wg * hplan.lds > lds_room) per_cu--;
-                    // were every workgroup of the pass resident before the first of the search kernel, one of those would still fit
-                    // on some CU: the pass waits for the search kernel, never the other way round
-                    // ... and never more than ov_cap (7) per CU (measured at 1637 tied of 32768: cap 7 8.94 ms, 5 9.32, 3 9.53,
-                    // 1 11.8 -- under a search kernel that saturates HBM the walks are slow, most ties are still there when it ends)
-                    constexpr uint32_t ov_cap = 7u;
-                    uint32_t per_cu_h = (uint32_t)((lds_room - lds) / hplan.lds);
-                    if (per_cu_h > ov_cap) per_cu_h = ov_cap;
-                    const uint32_t h_cap = ncu * per_cu_h;
-                    // ONE such launch at a time per process (two passes waiting for two search kernels could hold every CU's LDS between
-                    // them): the previous one has finished, or it is ordered before this one (same stream)
-                    if (h_cap >= ncu && kdb_heap_overlap_begin(idx, s)) {
-                        overlap = true;
-                        ov_guard.armed = true;
-                        grid = per_cu * ncu;
-                        if (hgrid > h_cap) hgrid = h_cap;
-                        hplan.grid = hgrid;
-                        raw_l |= 32u;
-                    }
-                }
-            }
-            // (Round 6 tried the pass BESIDE the kernel for open launches too -- 16 workgroups on the side stream taking tied queries as
-            // tickets while the launch still accepts callers.  64 one-query callers with the flag: 172 k QPS / p99 1.10 ms before,
-            // 141 k / 1.11 with it: a tied query's latency is its heap-order WALK (0.3 - 1.2 ms, long walks tie), not the wait for the
-            // launch to close, and three launches + two memsets per open launch cost the launching thread more than they saved.)
-            const size_t list_bytes = (((size_t)B + 4u) * 4u + 255u) & ~(size_t)255u;
-            hplan.tail_bytes = ((size_t)hplan.grid * (size_t)(hplan.cap_c - hplan.nl_c) * 12u + 255u) & ~(size_t)255u;
-            rc0 = kdb_ensure_tie_scratch(idx, list_bytes + hplan.tail_bytes + 256u + (overlap ? KdbTieStash::bytes(B, k) : 0u));
-            if (rc0) return rc0;
-            d_tie_list = reinterpret_cast<uint32_t *>(kdb_cur(idx).d_tie);
-            d_tails = reinterpret_cast<unsigned char *>(kdb_cur(idx).d_tie) + list_bytes;
-            if (overlap) d_stash = d_tails + hplan.tail_bytes;
-            KDB_HIP(hipMemsetAsync(d_tie_list, 0, 16, s));
-            if (overlap) KDB_HIP(hipMemsetAsync(d_tie_list + 4, 0xff, (size_t)B * 4u, s)); // an entry is there once it is not all ones
-        }
-        // (side by side, the two kernels' workgroups have visited bitsets of their own)
-        int rc = kdb_ensure_visited(idx, overlap ? grid + hgrid : (grid > hgrid ? grid : hgrid), s);
-        if (rc) return rc;
-        struct kdb_lane &ln = idx->lanes[idx->cur_lane];
-        if (overlap) {
-            if (!ln.side) {
-                int lo = 0, hi = 0;
-                (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
-                KDB_HIP(hipStreamCreateWithPriority(&ln.side, hipStreamNonBlocking, hi));
-                KDB_HIP(hipEventCreateWithFlags(&ln.side_ev0, hipEventDisableTiming));
-                KDB_HIP(hipEventCreateWithFlags(&ln.side_ev1, hipEventDisableTiming));
-            }
-        }
-        unsigned long long *d_ctr = kdb_stats_begin(idx, 1, B, 0);
-        { // test hook (kdb_probe_launch_shape): the instantiation this launch takes, in the statistics slot just opened
-            uint32_t *const shp = kdb_stats_shape(idx);
-            shp[0] = 1u, shp[1] = (uint32_t)PREC, shp[2] = (uint32_t)METRIC, shp[3] = (uint32_t)NCH, shp[4] = (uint32_t)BS;
-            shp[5] = vis_size, shp[6] = waves, shp[7] = planes ? 1u : 0u, shp[8] = heap_pass ? 1u : 0u;
-            shp[13] = grid, shp[14] = (uint32_t)lds, shp[15] = B;
-        }
-        // the launch's accumulators {n_dist, n_hops, work | done, dropped}: zero between launches (see the kernel's end).  They
-        // belong to the call's SCRATCH LANE (words 32..41 of its d_work), not to the statistics ring: two launches that share
-        // a lane are ordered by the lane protocol (same stream, or an event wait on the previous user), so a launch never
-        // finds the words of another one that is still running -- whatever the number of launches in flight on other streams
-        unsigned long long *d_acc = reinterpret_cast<unsigned long long *>(kdb_cur(idx).d_work + 32);
-        if (idx->time_launches) KDB_HIP(hipEventRecord(idx->ev0, s));
-        if (overlap) { // everything queued on s so far (prepared queries, the armed list) is done before the pass starts
-            KDB_HIP(hipEventRecord(ln.side_ev0, s));
-            KDB_HIP(hipStreamWaitEvent(ln.side, ln.side_ev0, 0));
-        }
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(64u * waves), lds, s, vk, d_q, d_qnorm, raw_l, B, k, eff, d_allow, ma, entry, beam_cap, nr_cap, vis_size,
-                           kdb_cur(idx).d_visited, reinterpret_cast<uint32_t *>(d_acc + 2), d_ctr, d_out_ids, d_out_dist, d_out_count, d_tr_ndist, d_tr_nhops,
-                           d_tie_list, d_stash);
-        KDB_HIP(hipGetLastError());
-        if (heap_pass) { // (its workgroups return at once when the search kernel queued nothing; the closing event covers both passes:
-            // the second one adds its counters to the slot the first one published)
-            rc = kdb_launch_heap_walk(idx, v, d_q, d_qnorm, raw_l, B, k, eff, d_allow, ma, entry, d_tie_list, d_tails, hplan, d_ctr, d_out_ids,
-                                      d_out_dist, d_out_count, d_tr_ndist, d_tr_nhops, overlap ? ln.side : s, overlap ? grid : 0u, d_stash, overlap ? 1u : 0u);
-            if (overlap) { // s carries on when the pass is done (the search kernel closes the list as it ends, whatever happened here)
-                if (rc == KDB_OK && hipEventRecord(ln.side_ev1, ln.side) != hipSuccess) rc = KDB_ERR_HIP;
-                if (hipStreamWaitEvent(s, ln.side_ev1, 0) != hipSuccess && rc == KDB_OK) rc = KDB_ERR_HIP;
-                kdb_heap_overlap_launched(idx, s, ln.side_ev1);
-                ov_guard.armed = false;
-                // the sweep: entries the pass did not walk (none, unless its workgroups gave up waiting) -- workgroups that find
-                // every entry marked return at once
-                if (rc == KDB_OK) {
-                    KdbHeapPlan sweep = hplan; // (one workgroup per CU: enough for what is never there)
-                    if (sweep.grid > ncu) sweep.grid = ncu;
-                    rc = kdb_launch_heap_walk(idx, v, d_q, d_qnorm, raw_l, B, k, eff, d_allow, ma, entry, d_tie_list, d_tails, sweep, d_ctr, d_out_ids,
-                                              d_out_dist, d_out_count, d_tr_ndist, d_tr_nhops, s, grid, d_stash, 2u);
-                }
-            }
+    KdbSearchCell c{nullptr, PREC, METRIC, NCH, BS, lad.rung[0], eff, lad.beam_cap, nr_cap};
+    KdbView vk = a.v; // the search kernel's view: with the walk planes once a planes kernel has been picked
+    for (uint32_t i = 0; i < lad.n; i++) {
+        c.rung = lad.rung[i];
+        // Walk planes: asked for only HERE, by a launch that has come down to the one-wave register-beam kernel of an index the planes
+        // serve (latency-mode launches, the LDS beam of ef > 256, L2 and quantised indexes never allocate them)
+        if (c.rung.planes && kdb_planes_kernel<PREC, METRIC, NCH>()) {
+            const int rc = kdb_search_use_planes(a.idx, vk, a.s, &c.rung.planes);
             if (rc) return rc;
-        }
-        if (idx->time_launches) KDB_HIP(hipEventRecord(idx->ev1, s));
-        return KDB_OK;
-    };
-    auto launch = [&](auto kern, uint32_t vis_size, uint32_t waves = 1u, bool planes = false) -> int {
-        return launch_any(kern, vis_size, waves, lds1 + (waves > 1u ? 64u + 512u + (size_t)(hsize_w - hsize) * 4 : 0u), planes);
-    };
-    auto launch_lds = [&](auto kern, uint32_t vis_size, size_t lds) -> int { return launch_any(kern, vis_size, 1u, lds); };
-    (void)launch_lds;
-    // Walk planes: asked for only HERE, by a launch that has picked the one-wave register-beam kernel of an index the planes serve
-    // (latency-mode launches, the LDS beam of ef > 256, L2 and quantised indexes never allocate them); made by the first such launch, under idx->mu.  *use = false (no room,
-    // opted out, another shape): the walk reads the float32 rows as ever.
-    auto use_planes = [&](bool *use) -> int {
-        *use = false;
-        if constexpr (kdb_planes_kernel<PREC, METRIC, NCH>()) {
-            if (v.ld != 64u * NCH || v.rows != idx->d_rows || !kdb_walk_planes_shape(idx)) return KDB_OK;
-            const int rc = kdb_ensure_walk_planes(idx, s);
-            if (rc) return rc;
-            if (!idx->d_walk_hi) return KDB_OK;
-            vk.walk_hi = idx->d_walk_hi;
-            vk.walk_lo = idx->d_walk_lo;
-            vk.walk_err = idx->d_walk_err;
-            *use = true;
-        }
-        return KDB_OK;
-    };
-    if constexpr (BS == 1 || BS == 2 || BS == 4) {
-        // latency mode: a batch that leaves most of the chip idle gives every query four waves: wave 0 walks, the other
-        // three evaluate a hop's rows (one HBM round trip per hop instead of three), wave 1 prepares the next node while
-        // wave 0 inserts (search_layer_wide); same walk, same results, same counters -- as long as every query gets its own
-        // resident workgroup (512 at 768-d float32).  Round 5: the four-slot beam (ef 129 .. 256) too -- with the hash at its
-        // ordinary size there (the enlarged one would leave two workgroups per CU)
-        if (hsize) {
-            const uint32_t hw = BS == 4 ? hsize : hsize_w;
-            const size_t wlds = lds1 + 64 + 512 + (size_t)(hw - hsize) * 4;
-            auto wk = hnsw_search_kernel<PREC, METRIC, NCH, BS, 1, 4>;
-            if (wlds > 64 * 1024) KDB_HIP(hipFuncSetAttribute((const void *)wk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)wlds));
-            const uint32_t wide_max = ncu * (uint32_t)occupancy_blocks(wk, 256, wlds);
-            if (B <= wide_max) return launch_any(wk, hw, 4u, wlds);
-            // twice as many queries than that: two waves per query -- the walker and one wave that prepares nodes and evaluates rows
-            auto wk2 = hnsw_search_kernel<PREC, METRIC, NCH, BS, 1, 2>;
-            if (wlds > 64 * 1024) KDB_HIP(hipFuncSetAttribute((const void *)wk2, hipFuncAttributeMaxDynamicSharedMemorySize, (int)wlds));
-            const uint32_t wide2_max = ncu * (uint32_t)occupancy_blocks(wk2, 128, wlds);
-            if (B <= wide2_max) return launch_any(wk2, hw, 2u, wlds);
-        }
+        } else c.rung.planes = false;
+        c.kern = search_kernel_of<PREC, METRIC, NCH, BS>(c.rung, c.rung.planes);
+        if (c.rung.lds > 64 * 1024) KDB_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(c.kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)c.rung.lds));
+        if (!c.rung.bounded || a.B <= (uint32_t)a.idx->n_cu * (uint32_t)kdb_search_occupancy(c.kern, (int)(64u * c.rung.waves), c.rung.lds)) break;
     }
-    // (Round 6 built "two queries per wave" for short rows -- docs/probes/r06_search_pair.cuh: one walk per 32-lane half, every
-    // wave-uniform value of this walk kept per half, ballots split, cross-lane reads inside the half; bit-exact at the first run -- and
-    // measured it on the GloVe-100 shape, 8192 queries: efS 20 0.450 ms against 0.455 here, efS 100 1.27 ms against 0.93: what is scalar
-    // bookkeeping for one query per wave becomes vector work per half (a half-ballot is five instructions, not one), and a four-slot
-    // beam per half triples the insertion: more instructions per QUERY, not fewer.  Not shipped.)
-    if constexpr (BS == 1 || BS == 2 || BS == 4) {
-        if (hsize) {
-            if constexpr (kdb_planes_kernel<PREC, METRIC, NCH>()) {
-                bool planes = false;
-                const int rc = use_planes(&planes);
-                if (rc) return rc;
-                if (planes) return launch(hnsw_search_kernel<PREC, METRIC, NCH, BS, 1, 1, 1>, hsize, 1u, true);
-            }
-            return launch(hnsw_search_kernel<PREC, METRIC, NCH, BS, 1>, hsize);
-        }
-    }
-    if constexpr (BS == 0) {
-        // ef 261 .. 1040: the visited set of a walk (~9 ef ids) still fits LDS when the batch leaves LDS free -- 32 KB (64 KB above
-        // ef 520) per wave, four (two) waves per CU.  A batch that fits ONE round of such waves takes the LDS hash and loses the HBM
-        // bitset's dependent round trip per hop (atomicOr at the device's coherence point); larger batches keep the bitset, whose
-        // eight waves per CU hide more latency than the hash saves.  (The hash still migrates to the bitset if a walk outgrows it.)
-        const uint32_t hbig = kdb_vis_hash_size_large(eff);
-        if (hbig) {
-            auto kh = hnsw_search_kernel<PREC, METRIC, NCH, BS, 1>;
-            const size_t lds_h = lds_common + (size_t)hbig * 4;
-            if (lds_h + 16 <= 160 * 1024) {
-                // Round 5: the latency mode for the LDS beam as well (k = 100 / ef = 400 on 1024 queries: every query its own four
-                // waves -- the rows of a hop in one round trip, the visit of the next node beside the one-merge insertion)
-                const size_t wlds = lds_h + 64 + 512;
-                if (wlds + 16 <= 160 * 1024) {
-                    auto wk = hnsw_search_kernel<PREC, METRIC, NCH, BS, 1, 4>;
-                    KDB_HIP(hipFuncSetAttribute((const void *)wk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)wlds));
-                    if (B <= ncu * (uint32_t)occupancy_blocks(wk, 256, wlds)) return launch_any(wk, hbig, 4u, wlds);
-                    auto wk2 = hnsw_search_kernel<PREC, METRIC, NCH, BS, 1, 2>;
-                    KDB_HIP(hipFuncSetAttribute((const void *)wk2, hipFuncAttributeMaxDynamicSharedMemorySize, (int)wlds));
-                    if (B <= ncu * (uint32_t)occupancy_blocks(wk2, 128, wlds)) return launch_any(wk2, hbig, 2u, wlds);
-                }
-                KDB_HIP(hipFuncSetAttribute((const void *)kh, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_h));
-                const uint32_t one_round = ncu * (uint32_t)occupancy_blocks(kh, 64, lds_h);
-                if (B <= one_round) return launch_lds(kh, hbig, lds_h);
-            }
-        }
-    }
-    if constexpr (BS == 0) { // beyond the large hash (ef > 1040, or a batch too large for it): the latency mode over the HBM bitset --
-        // wave 1 owns the bitset, the walker never waits for its atomics
-        const size_t wlds = lds1 + 64 + 512;
-        if (wlds + 16 <= 160 * 1024) {
-            auto wk = hnsw_search_kernel<PREC, METRIC, NCH, BS, 0, 4>;
-            if (wlds > 64 * 1024) KDB_HIP(hipFuncSetAttribute((const void *)wk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)wlds));
-            if (B <= ncu * (uint32_t)occupancy_blocks(wk, 256, wlds)) return launch_any(wk, 0u, 4u, wlds);
-            auto wk2 = hnsw_search_kernel<PREC, METRIC, NCH, BS, 0, 2>;
-            if (wlds > 64 * 1024) KDB_HIP(hipFuncSetAttribute((const void *)wk2, hipFuncAttributeMaxDynamicSharedMemorySize, (int)wlds));
-            if (B <= ncu * (uint32_t)occupancy_blocks(wk2, 128, wlds)) return launch_any(wk2, 0u, 2u, wlds);
-        }
-    }
-    return launch(hnsw_search_kernel<PREC, METRIC, NCH, BS, 0>, 0u);
+    return kdb_launch_search_cell(a, vk, c);
 }
 
 template <int PREC, int METRIC, int NCH>
-static int launch_search_t(kdb_index *idx, const KdbView &v, const void *d_q, const float *d_qnorm, uint32_t raw, uint32_t B,
-                           uint32_t k, uint32_t ef, const uint32_t *d_allow, KdbMultiAllow ma, uint32_t entry, uint32_t *d_out_ids,
-                           float *d_out_dist, uint32_t *d_out_count, uint32_t *d_tr_ndist, uint32_t *d_tr_nhops,
-                           hipStream_t s) {
-    const uint32_t eff = ma.k_of_query ? ef : kdb_mixed_effective_ef(ef, k, false);
-#define KDB_A idx, v, d_q, d_qnorm, raw, B, k, ef, d_allow, ma, entry, d_out_ids, d_out_dist, d_out_count, d_tr_ndist, d_tr_nhops, s
+static int launch_search_t(const KdbSearchLaunch &a) {
+    // ef = max(efSearch, k) (:2377-2380); a mixed launch: k is the stride and ef the capacity the caller worked out (ef_cap)
+    const uint32_t eff = a.ma.k_of_query ? a.ef : kdb_mixed_effective_ef(a.ef, a.k, false);
     switch (kdb_beam_slots(eff)) { // beam in registers (1/2/4 slots of 64 entries) or in LDS
-    case 1: return launch_search_bs<PREC, METRIC, NCH, 1>(KDB_A);
-    case 2: return launch_search_bs<PREC, METRIC, NCH, 2>(KDB_A);
-    case 4: return launch_search_bs<PREC, METRIC, NCH, 4>(KDB_A);
-    default: return launch_search_bs<PREC, METRIC, NCH, 0>(KDB_A);
+    case 1: return launch_search_bs<PREC, METRIC, NCH, 1>(a, eff);
+    case 2: return launch_search_bs<PREC, METRIC, NCH, 2>(a, eff);
+    case 4: return launch_search_bs<PREC, METRIC, NCH, 4>(a, eff);
+    default: return launch_search_bs<PREC, METRIC, NCH, 0>(a, eff);
     }
-#undef KDB_A
 }
 
 } // namespace

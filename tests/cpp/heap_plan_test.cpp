@@ -40,8 +40,8 @@ static size_t kernel_carve(bool wk, uint32_t ld, uint32_t ef, uint32_t hsize, bo
 }
 
 int main() {
-    static_assert(kdb_heap_hash_words(100) == 2048 && kdb_heap_hash_words(101) == 4096 && kdb_heap_hash_words(260) == 4096 &&
-                      kdb_heap_hash_words(261) == 0, "the visited hash's boundaries");
+    static_assert(kdb_vis_hash_size(100) == 2048 && kdb_vis_hash_size(101) == 4096 && kdb_vis_hash_size(260) == 4096 &&
+                      kdb_vis_hash_size(261) == 0, "the visited hash's boundaries");
     unsigned long refused = 0, planned = 0;
     for (bool wk : {false, true})
         for (uint32_t ld : {32u, 128u, 768u, 1536u})

@@ -46,18 +46,18 @@ int main() {
     CHECK(kdb_mixed_effective_ef(100, 100, true) == 200);
     CHECK(kdb_mixed_effective_ef(150, 256, true) == 256);
     // class and capacity on both sides of every boundary
-    CHECK(kdb_mixed_beam_class(1) == 1 && kdb_mixed_ef_cap(1) == 64);
-    CHECK(kdb_mixed_beam_class(64) == 1 && kdb_mixed_ef_cap(64) == 64);
-    CHECK(kdb_mixed_beam_class(65) == 2 && kdb_mixed_ef_cap(65) == 128);
-    CHECK(kdb_mixed_beam_class(128) == 2 && kdb_mixed_ef_cap(128) == 128);
-    CHECK(kdb_mixed_beam_class(129) == 4 && kdb_mixed_ef_cap(129) == 256);
-    CHECK(kdb_mixed_beam_class(256) == 4 && kdb_mixed_ef_cap(256) == 256);
-    CHECK(kdb_mixed_beam_class(257) == 0 && kdb_mixed_ef_cap(257) == 257);
-    CHECK(kdb_mixed_beam_class(1200) == 0 && kdb_mixed_ef_cap(1200) == 1200);
+    CHECK(kdb_beam_slots(1) == 1 && kdb_mixed_ef_cap(1) == 64);
+    CHECK(kdb_beam_slots(64) == 1 && kdb_mixed_ef_cap(64) == 64);
+    CHECK(kdb_beam_slots(65) == 2 && kdb_mixed_ef_cap(65) == 128);
+    CHECK(kdb_beam_slots(128) == 2 && kdb_mixed_ef_cap(128) == 128);
+    CHECK(kdb_beam_slots(129) == 4 && kdb_mixed_ef_cap(129) == 256);
+    CHECK(kdb_beam_slots(256) == 4 && kdb_mixed_ef_cap(256) == 256);
+    CHECK(kdb_beam_slots(257) == 0 && kdb_mixed_ef_cap(257) == 257);
+    CHECK(kdb_beam_slots(1200) == 0 && kdb_mixed_ef_cap(1200) == 1200);
     for (uint32_t e = 1; e <= 2000; e++) { // the capacity holds the ef it was made for, and asking again changes nothing
         CHECK(kdb_mixed_ef_cap(e) >= e);
         CHECK(kdb_mixed_ef_cap(kdb_mixed_ef_cap(e)) == kdb_mixed_ef_cap(e));
-        CHECK(kdb_mixed_beam_class(kdb_mixed_ef_cap(e)) == kdb_mixed_beam_class(e));
+        CHECK(kdb_beam_slots(kdb_mixed_ef_cap(e)) == kdb_beam_slots(e));
     }
     // validity against (stride, ef_cap)
     CHECK(kdb_mixed_query_valid(10, 64, 10, 64));   // k == stride, ef == cap

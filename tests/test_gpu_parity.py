@@ -1469,7 +1469,7 @@ def test_tied_walks_with_deleted_nodes_filters_and_int8(oracle, hip):
                 if ef != 70:
                     continue
                 # 4800 queries: the heap-order pass runs BESIDE the search kernel (other stream, tickets taken while the list
-                # fills -- search.hip launch_any): the same answers and counters, query for query, and the same totals
+                # fills -- search.hip kdb_launch_search_cell): the same answers and counters, query for query, and the same totals
                 c0 = idx.counters()
                 assert (c0["n_dist"], c0["n_hops"]) == (int(nd.sum()), int(nh.sum())), (prec, metric, c0)
                 Qr = np.tile(Q, (200, 1))

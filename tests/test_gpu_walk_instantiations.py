@@ -1,5 +1,5 @@
 """Walk parity, instantiation by instantiation: every (precision, metric, row width NCH, beam BS) cell of hnsw_search_kernel, in every
-launch geometry launch_search_bs can pick for it, against the oracle's walk (ARITH_HIP_WAVE) bit for bit -- ids, distance bits,
+launch geometry its ladder (kdb_search_ladder, kdb_search_plan.h) holds for it, against the oracle's walk (ARITH_HIP_WAVE) bit for bit -- ids, distance bits,
 n_dist, n_hops -- the way test_small_scan_chunk_instantiations walks through the exact scan's instantiations.
 
 Each case reads back which kernel it ran (HipIndex.launch_shape, the kdb_probe_launch_shape test hook) and asserts that it is the
@@ -12,6 +12,9 @@ is in play at every width).  12 queries -- six stored rows (the duplicated one a
 batch sizes; the first and the last 12 queries of every rung are compared, none left out: once under KDB_SEARCH_HEAP_ORDER (ids,
 distance bits and counters of the oracle for every query, ties included) and once without it (the fast walk's own answer)."""
 import functools
+import os
+import subprocess
+import tempfile
 
 import numpy as np
 import pytest
@@ -73,13 +76,13 @@ def _class(ef):
 #     float32 x 768 / 1024: four waves up to 1024, then one
 # Extra rungs: where the ladder misses a geometry that a batch size does reach.  (cell, ef) -> batch sizes
 EXTRA_RUNGS = {}
-# Geometries no batch size reaches for a cell on this device, each with the line of launch_search_bs that excludes it.
+# Geometries no batch size reaches for a cell on this device, each with the rungs of its ladder (kdb_search_ladder) that exclude it.
 UNREACHABLE = {}
-_WHY_WIDE2 = ("`if (B <= wide2_max)` behind `if (B <= wide_max)`: the latency modes' footprint (over 32 KB with the 8192-word hash) lets "
-              "LDS hold four workgroups per CU (three above 40 KB) whatever their wave count, and the four-wave kernel reaches that: wide2_max == wide_max")
-_WHY_REGS2 = ("`if (B <= wide2_max)` (register beams) / `if (B <= ncu * occupancy_blocks(wk2, 128, wlds))` (bitset): the two-wave NCH 12 / 16 kernels' "
+_WHY_WIDE2 = ("the hash x 2 rung behind the hash x 4 rung of a register beam: the latency modes' footprint (over 32 KB with the 8192-word hash) lets "
+              "LDS hold four workgroups per CU (three above 40 KB) whatever their wave count, and the four-wave kernel reaches that: both rungs admit the same batches")
+_WHY_REGS2 = ("the hash x 2 rung (register beams) / the bitset x 2 rung (bitset) behind their four-wave rung: the two-wave NCH 12 / 16 kernels' "
               "registers leave four workgroups per CU (kdb_search_minw: two waves per SIMD): the 1024 queries the four-wave kernel already takes")
-_WHY_LDS_HASH = ("`if (B <= ncu * occupancy_blocks(wk2, 128, wlds))` and `if (B <= one_round)` behind the four-wave test of the LDS beam: with the "
+_WHY_LDS_HASH = ("the hash x 2 and hash x 1 rungs behind the hash x 4 rung of the LDS beam: with the "
                  "large hash a workgroup needs 38 .. 80 KB, LDS holds four (8192 words) or two (16384 words) per CU whatever their wave count, and "
                  "the four-wave kernel reaches that")
 for _key in PAIRS:
@@ -103,6 +106,30 @@ for _key in PAIRS:
     else:
         UNREACHABLE[_key + (300,)] = ({(HASH, 2), (HASH, 1)}, _WHY_LDS_HASH)
     UNREACHABLE[_key + (700,)] = ({(HASH, 2), (HASH, 1)}, _WHY_LDS_HASH)
+
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+@functools.lru_cache(maxsize=None)
+def _plan_ladders():
+    """(precision, metric, dim, ef) -> {(visited set, waves): (visited words, LDS bytes)}: the ladder of every cell of this module from
+    kdb_search_plan.h itself, through tests/cpp/search_plan_test.cpp (the program of tests/test_search_plan.py, in its `ladder` mode)"""
+    cells = [key + (ef,) for key in PAIRS for ef in BEAMS]
+    args = []
+    for prec, metric, dim, ef in cells:       # int8 keys, columns of a stored row, effective ef (K <= ef), deleted nodes (every 13th id)
+        args += [int(prec == I8), dim, ef, N_ROWS.get((prec, metric, dim), N_DEFAULT) // 13]
+    with tempfile.TemporaryDirectory() as tmp:
+        exe = os.path.join(tmp, "search_plan_test")
+        subprocess.run(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-I", os.path.join(ROOT, "kektordb_amd", "csrc"),
+                        os.path.join(ROOT, "tests", "cpp", "search_plan_test.cpp"), "-o", exe], check=True, capture_output=True, text=True)
+        r = subprocess.run([exe, "ladder"] + [str(a) for a in args], check=True, capture_output=True, text=True, timeout=60)
+    out = {cell: {} for cell in cells}
+    for line in r.stdout.splitlines():
+        t, is_hash, waves, words, lds, _bounded, _planes = (int(x) for x in line.split())
+        out[cells[t]][(HASH if is_hash else BITS, waves)] = (words, lds)
+    assert all(out.values()), r.stdout
+    return out
 
 
 class Pair:
@@ -182,7 +209,10 @@ def _walk_ladder(p, ef, nch, planes_ok, filtered=False):
         assert s["planes"] in ((0, 1) if planes_ok else (0,)) and (s["planes"] == 0 or (s["waves"] == 1 and bs != 0)), (key, ef, B, s)
         assert s["heap_pass"] == 1 and s["heap_nch"] == HEAP_NCH[key], (key, ef, B, s)
         assert (s["heap_hash_words"], s["heap_reg_results"]) == ({16: 2048, 100: 2048, 200: 4096}.get(ef, 0), int(ef == 16)), (key, ef, B, s)
-        seen.add((HASH if s["vis_hash_words"] else BITS, s["waves"]))
+        geometry = (HASH if s["vis_hash_words"] else BITS, s["waves"])
+        # ... with the visited words and the LDS bytes the plan gives that rung of the cell's ladder
+        assert (s["vis_hash_words"], s["lds_bytes"]) == _plan_ladders()[key + (ef,)].get(geometry), (key, ef, B, s, _plan_ladders()[key + (ef,)])
+        seen.add(geometry)
         assert not np.any(cnt & hip.index.COUNT_TIED), (key, ef, B)             # heap order resolved every tie
         for b in list(range(NQ)) + list(range(B - NQ, B)):
             oi, od, (ond, onh) = want[b % NQ]
