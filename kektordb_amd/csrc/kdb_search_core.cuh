@@ -14,26 +14,12 @@
 #include "kdb_device.cuh"
 #include <math.h>
 
-#ifndef KDB_F32_ROWS2
-#define KDB_F32_ROWS2 4 // rows per 16-lane group and trip for rows of up to 128 columns
-#endif
-#ifndef KDB_F32_ROWS6
-#define KDB_F32_ROWS6 2
-#endif
-#ifndef KDB_F32_ROWS
-#define KDB_F32_ROWS 3 // measured at 768-d: 12 rows per trip (224 VGPRs, 2 waves/SIMD) beat 8 by 3-6 %
-#endif
-#ifndef KDB_F32_DUAL
-#define KDB_F32_DUAL 1
-#endif
+// rows per 16-lane group and trip of a helper wave of the four-wave mode (three helpers: 12 rows per trip); every other walk: kdb_trip_rows
 #ifndef KDB_WIDE4_ROWS
 #define KDB_WIDE4_ROWS 1
+#endif
 #ifndef KDB_LDS_MERGE
 #define KDB_LDS_MERGE 1 // one merge per hop into the LDS beam (0: the sequential form, for A/B measurements)
-#endif // rows per 16-lane group and trip of a helper wave of the four-wave mode (three helpers: 12 rows per trip)
-#endif
-#ifndef KDB_F16_ROWS
-#define KDB_F16_ROWS 2
 #endif
 // measurement build (make dbgs): where a walk's time goes
 #ifdef KDB_SEARCH_TIMERS
@@ -292,6 +278,25 @@ __device__ __forceinline__ void kdb_planes_trip(const KdbView &v, const WaveLds 
     KDB_T(if (tc) { const unsigned long long c = __builtin_readcyclecounter(); if (full) tc->t_lo_math += c - tp0; else tc->t_notfull += c - tp0; })
 }
 
+// Rows per 16-lane group and trip (4 * R rows of a hop in one HBM round trip) for rows of 64 * NCH columns (NCH == 0: any width).
+// Every (precision, NCH) a kernel is instantiated for has its line here; anything else does not compile.  RMAX > 0 caps R of the
+// fixed widths (the any-width loaders always take two rows).
+template <int PREC, int NCH, int RMAX>
+constexpr int kdb_trip_rows() {
+    constexpr bool f32 = PREC == KDB_PREC_F32;
+    static_assert(f32 || PREC == KDB_PREC_F16 || PREC == KDB_PREC_I8, "rows are float32, float16 or int8");
+    static_assert(f32 ? (NCH == 0 || NCH == 2 || NCH == 4 || NCH == 6 || NCH == 8 || NCH == 12 || NCH == 16 || NCH == 24) : (NCH == 0 || NCH == 12 || NCH == 24),
+                  "compute_dists: no trip shape for this precision and row width");
+    constexpr int R = !f32        ? 2 // 8 rows per trip; int8: more would cost the fourth wave per SIMD (registers)
+                      : NCH == 0  ? 2 // any other width: 8 rows per pass
+                      : NCH == 2  ? 4 // rows of up to 128 columns
+                      : NCH <= 6  ? 2
+                      : NCH <= 12 ? 3 // measured at 768 columns: 12 rows per trip (224 VGPRs, 2 waves/SIMD) beat 8 by 3-6 %
+                      : NCH == 16 ? 2
+                                  : 1; // 1536 columns: 24 pieces per lane and row, one row per group
+    return (RMAX > 0 && R > RMAX && NCH != 0) ? RMAX : R;
+}
+
 // PL = 1 (planes kernels: float32, cosine, v.ld == 64 * NCH, NCH even): the rows are read from the walk planes -- `full` (wave-uniform:
 // the beam holds ef results) and `worst` say which candidates may be rejected from the high plane alone (kdb_planes_trip)
 template <int PREC, int METRIC, int NCH = 0, int RMAX = 0, int PL = 0>
@@ -322,9 +327,8 @@ __device__ __forceinline__ void compute_dists(const KdbView &v, const WaveLds &s
         wave_lds_fence();
         return;
     }
-    if constexpr (PREC == KDB_PREC_F32 && NCH > 0 && NCH <= 16 && KDB_F32_DUAL) { // 4*R rows per round trip
-        constexpr int R0 = NCH <= 2 ? KDB_F32_ROWS2 : NCH <= 6 ? KDB_F32_ROWS6 : NCH <= 12 ? KDB_F32_ROWS : 2;
-        constexpr int R = (RMAX > 0 && R0 > RMAX) ? RMAX : R0;
+    constexpr int R = kdb_trip_rows<PREC, NCH, RMAX>(); // (the planes trips above have their own)
+    if constexpr (PREC == KDB_PREC_F32 && NCH > 0 && NCH <= 16) { // 4*R rows per round trip
         for (uint32_t base = 0; base < n;) {
             const uint32_t left = n - base;
             if (left > 4u * (R - 1) || R == 1) { // wave-uniform: a full-width trip
@@ -368,7 +372,6 @@ __device__ __forceinline__ void compute_dists(const KdbView &v, const WaveLds &s
         return;
     }
     if constexpr (PREC == KDB_PREC_F16 && NCH > 0 && NCH % 2 == 0 && NCH <= 24) { // ld == 64*NCH: NCH/2 chunks per lane
-        constexpr int R = (RMAX > 0 && KDB_F16_ROWS > RMAX) ? RMAX : KDB_F16_ROWS; // rows per 16-lane group and trip
         for (uint32_t base = 0; base < n; base += 4u * R) {
             const uint16_t *rows[R];
             uint32_t rr[R];
@@ -390,7 +393,6 @@ __device__ __forceinline__ void compute_dists(const KdbView &v, const WaveLds &s
         return;
     }
     if constexpr (PREC == KDB_PREC_I8 && NCH > 0 && NCH % 4 == 0 && NCH <= 24) { // ld == 64*NCH: NCH/4 chunks per lane
-        constexpr int R = (RMAX > 0 && 2 > RMAX) ? RMAX : 2; // 8 rows per trip; more would cost the fourth wave per SIMD (registers)
         for (uint32_t base = 0; base < n; base += 4u * R) {
             const int8_t *rows[R];
             uint32_t rr[R], ids[R];
@@ -418,7 +420,7 @@ __device__ __forceinline__ void compute_dists(const KdbView &v, const WaveLds &s
         return;
     }
     if constexpr (PREC == KDB_PREC_F16 && NCH == 0) { // any other width: 8 rows per pass, 4 pieces per lane and trip
-        constexpr int R = 2, U = 4;
+        constexpr int U = 4;
         for (uint32_t base = 0; base < n; base += 4u * R) {
             const uint16_t *rows[R];
             uint32_t rr[R];
@@ -440,7 +442,7 @@ __device__ __forceinline__ void compute_dists(const KdbView &v, const WaveLds &s
         return;
     }
     if constexpr (PREC == KDB_PREC_I8 && NCH == 0) {
-        constexpr int R = 2, U = 4;
+        constexpr int U = 4;
         for (uint32_t base = 0; base < n; base += 4u * R) {
             const int8_t *rows[R];
             uint32_t rr[R], ids[R];
@@ -468,7 +470,7 @@ __device__ __forceinline__ void compute_dists(const KdbView &v, const WaveLds &s
         return;
     }
     if constexpr (PREC == KDB_PREC_F32 && NCH == 0) { // any other width: 8 rows per pass, 8 pieces per lane and trip
-        constexpr int R = 2, U = 8;
+        constexpr int U = 8;
         {
             for (uint32_t base = 0; base < n; base += 4u * R) {
                 const float *rows[R];
@@ -491,30 +493,18 @@ __device__ __forceinline__ void compute_dists(const KdbView &v, const WaveLds &s
             return;
         }
     }
-    for (uint32_t base = 0; base < n; base += 4) {
-        const uint32_t r = base + (uint32_t)g;
-        const bool act = r < n;
-        const uint32_t id = act ? s.nb_id[r] : 0u; // row 0 is all zero
-        float key;
-        if (PREC == KDB_PREC_F32) {
+    if constexpr (PREC == KDB_PREC_F32 && NCH == 24) { // 1536 columns: one row per group and trip (R == 1)
+        for (uint32_t base = 0; base < n; base += 4) {
+            const uint32_t r = base + (uint32_t)g;
+            const bool act = r < n;
+            const uint32_t id = act ? s.nb_id[r] : 0u; // row 0 is all zero
             const float *row = reinterpret_cast<const float *>(v.rows) + (size_t)id * v.ld;
-            float p = kdb_row_partial_f32<METRIC, NCH>(row, s.q, v.ld, t);
-            key = kdb_key_from_raw<PREC, METRIC>(kdb_reduce16(p));
-        } else if (PREC == KDB_PREC_F16) {
-            const uint16_t *row = reinterpret_cast<const uint16_t *>(v.rows) + (size_t)id * v.ld;
-            float p = kdb_row_partial_f16(row, s.q, v.ld, t);
-            key = kdb_reduce16(p);
-        } else {
-            const int8_t *row = reinterpret_cast<const int8_t *>(v.rows) + (size_t)id * v.ld;
-            int p = kdb_row_partial_i8(row, reinterpret_cast<const int8_t *>(s.q), v.ld, t);
-            p = kdb_reduce16_i(p);
-            uint32_t klo;
-            kdb_i8_key(p, qnorm, v.norms[id], key, klo);
-            if (act && t == 0 && s.nb_lo) s.nb_lo[r] = klo;
+            const float p = kdb_row_partial_f32<METRIC, NCH>(row, s.q, v.ld, t);
+            const float key = kdb_key_from_raw<PREC, METRIC>(kdb_reduce16(p));
+            if (act && t == 0) s.nb_d[r] = kdb_sane_key(key);
         }
-        if (act && t == 0) s.nb_d[r] = kdb_sane_key(key);
+        wave_lds_fence();
     }
-    wave_lds_fence();
 }
 
 // The query of a walk -> LDS, prepared as searchInternal prepares it (hnsw_index.go:404-434); returns the int8 query norm (else 1).
