@@ -48,6 +48,9 @@
  *                           every node of GetAllValidNodeIDs, hnsw_index.go:2884-2900)
  *   kdb_search_filtered     Engine.VSearch(index, query, k, filter, ...) from programs to answers (pkg/engine/ops.go:928-1007): lists,
  *                           routing between walk and exact scan, answers, as one call
+ *   kdb_index_set_text      textIndex[index][field] and TextIndexStats (pkg/core/core.go:944) as posting arrays in HBM
+ *   kdb_text_search_batch   DB.FindIDsByTextSearch (core.go:2069-2190) and the allow list (ops.go:1013-1024), cut at k
+ *   kdb_hybrid_search_batch searchWithFusion (ops.go:897-1209) without time decay: walk, BM25 and the alpha fusion as one call
  *   kdb_merge_topk          the merge step of the id-range shard (no reference
  *                           counterpart -- the reference is single process)
  *   kdb_sharded_search_batch  the same path over every GPU of a node from ONE process: fan-out,
@@ -574,6 +577,84 @@ KDB_API int kdb_search_filtered(kdb_index *idx, const float *queries, uint32_t B
                                 const kdb_filter_term *terms, const uint32_t *prog_offsets, uint32_t P, const uint32_t *prog_of_query,
                                 double flat_selectivity, uint32_t flags, uint32_t *out_ids, float *out_dist, uint32_t *out_count,
                                 uint8_t *out_route, uint32_t *out_card);
+
+/* ---- BM25 text search and hybrid fusion on the device (text.hip; geometry and validation in kdb_text_plan.h) -------------------
+ * The text half of Engine.VSearch: searchWithFusion (pkg/engine/ops.go:897-1209) starts DB.FindIDsByTextSearch
+ * (pkg/core/core.go:2069-2190) beside the vector walk and fuses the two lists (normalizeVectorScores / normalizeTextScores,
+ * pkg/engine/search_utils.go:48-70; the alpha mix, sort and cut at ops.go:1072-1098, :1189-1207).
+ *
+ * THE SNAPSHOT.  kdb_text_view is textIndex[index][field] plus TextIndexStats (core.go:944) in arrays: token t's postings are
+ * entries post_off[t] .. post_off[t+1] of post_doc (internal ids, STRICTLY ASCENDING inside a list) and post_tf (>= 1); doc_len has
+ * n_ids + 1 entries (0 = the document has no entry); idf is NULL or n_tokens doubles.  With idf == NULL the library fills the table
+ * on the host as std::log(1 + (total_docs - df + 0.5) / (df + 0.5)), df = post_off[t+1] - post_off[t], all in double and in that
+ * order (:2178-2179); a host that wants its own math.Log bits passes its own table.  The mirror sorts, and keeps the LAST entry of
+ * a repeated document (`candidateDocs[doc][token] = tf` overwrites, :2133).
+ * kdb_index_set_text is a writer in the sense of "Conventions" and replaces slot `field` (< KDB_MAX_TEXT_FIELDS) wholesale.  Refused
+ * with KDB_ERR_INVALID, nothing written: a list that is not strictly ascending; an id that is 0, above n_ids or above the index's
+ * capacity; a tf of 0; a df above total_docs (the case the comment at core.go:879 fears); an avg_len that is negative or not finite;
+ * an idf that is not finite.  kdb_index_reserve leaves a slot as it is: ids above n_ids have no postings and length 0.
+ * kdb_index_destroy frees it; kdb_index_compress does not carry it; an index that never uploads one allocates nothing.
+ * kdb_index_text_info: zeros for an empty slot.
+ *
+ * kdb_text_search_batch[_dev]: FindIDsByTextSearch and the allow list (ops.go:1013-1024), cut at k.  A query is n_tokens[b] <=
+ * t_stride <= KDB_TEXT_MAX_TOKENS token ids, tokens[b][0 .. n_tokens[b]); the analyzer stays on the host.  KDB_NO_TOKEN is a token
+ * the dictionary does not hold: it contributes nothing (core.go:2161-2164).  A token that appears twice is scored twice (the loop
+ * at :2142-2146).  A CANDIDATE is a document in at least one of the query's lists whose allow bit is set (allow_bits == NULL: every
+ * such document; with a list, ids above count are not allowed; a zero bitmap gives count 0, ops.go:937-939).  Its score is a sum
+ * over the query's tokens IN QUERY ORDER, in double, from 0.0, of
+ *     idf[t] * ((tf * 2.2) / (tf + 1.2 * (0.25 + 0.75 * (doc_len / avg_len))))
+ * for the tokens the document holds (:2182-2189; avg_len == 0 scores every term 0.0, :2173): only + * / on doubles, so the result is
+ * defined to the last bit.  Outputs: the first k candidates by (score descending, id ascending) -- the reference's order among
+ * equal scores comes from map iteration and an unstable sort and is unpinned; ascending id is this library's rule --, positions
+ * beyond the count holding id 0 and score 0.0; out_max: NULL or the largest candidate score (0.0 with none; normalizeTextScores
+ * needs it); out_ncand: NULL or the number of candidates.  1 <= k <= 1024.  The _dev form clamps n_tokens[b] to t_stride.
+ * One workgroup of 256 lanes per query sweeps the id space in tiles of 4096 ids with one cursor per token: a query with very long
+ * lists runs on one CU.
+ *
+ * kdb_hybrid_search_batch (host pointers; a composition like kdb_belief_batch): kdb_search_batch_dev unchanged with (k, ef, allow
+ * list, flags), bm25_topk_kernel with the same k and list, then one wave per query fuses.  With d the reference's distance of a
+ * vector result -- 1.0 - (double)dot on a float32 cosine index, (double)out_dist otherwise ("Conventions") -- its vector score is
+ * v = 1.0 / (1.0 + d); a text score is t = raw / max when max > 0, else raw.  A query with n_tokens[b] == 0 takes the vector-only
+ * rule: fused = v.  Otherwise a document in both lists scores alpha*v + (1-alpha)*t, in that order; one only in the vector list
+ * alpha*v; one only in the text list (1-alpha)*t.  An alpha below 0 or above 1 becomes 0.5 (ops.go:1089); a NaN alpha is
+ * KDB_ERR_INVALID.  The union is sorted by (fused score descending, id ascending) and cut at k; out_score receives the fused scores.
+ * The raw text score of a VECTOR result is not looked up in the text top-k (it may lie outside it): the fuse wave computes it by one
+ * binary search per query token in that token's list, with the same summation routine as the text kernel, so the bits agree.
+ * WHY THE TEXT TOP-K SUFFICES: a text-only document outside the text top-k has k text candidates ahead of it; their fused scores
+ * are at least their own text parts (alpha*v >= 0), and those are at least its own -- so k documents precede it.  The one
+ * exception: two DISTINCT text scores can round to the same product with (1-alpha); then id order and score order may disagree at
+ * the cut, and the reference's own order (an unstable sort over map iteration) is unpinned too.
+ * Out of scope: time decay (ops.go:1100-1187: pow and exp, which no device routine matches bit for bit, and which breaks the
+ * argument above) -- the call is VSearch with the index's MemoryConfig disabled; graph filters; the text-only case (:977-996),
+ * which the mirror serves with kdb_text_search_batch.  KDB_SEARCH_PREPARED, KDB_SEARCH_DIST_F64 and KDB_SEARCH_FAIL_ON_DROP are
+ * refused.  Takes turns on the staging buffer like kdb_search_by_id and is never combined with other callers' queries. */
+#define KDB_MAX_TEXT_FIELDS 4u
+#define KDB_TEXT_MAX_TOKENS 32u
+#define KDB_NO_TOKEN 0xffffffffu
+typedef struct {
+    uint32_t n_tokens;          /* V */
+    uint32_t n_ids;             /* doc_len covers ids 0..n_ids */
+    const uint64_t *post_off;   /* [V + 1] */
+    const uint32_t *post_doc;   /* [post_off[V]] */
+    const uint32_t *post_tf;    /* [post_off[V]] */
+    const uint32_t *doc_len;    /* [n_ids + 1], TextIndexStats.DocLengths */
+    uint64_t total_docs;        /* TextIndexStats.TotalDocs */
+    double avg_len;             /* TextIndexStats.AvgFieldLength */
+    const double *idf;          /* [V] or NULL */
+} kdb_text_view; /* 64 bytes */
+KDB_API int kdb_index_set_text(kdb_index *idx, uint32_t field, const kdb_text_view *v);
+KDB_API int kdb_index_drop_text(kdb_index *idx, uint32_t field);
+KDB_API int kdb_index_text_info(kdb_index *idx, uint32_t field, uint32_t *n_tokens, uint64_t *n_postings, uint64_t *bytes);
+KDB_API int kdb_text_search_batch(kdb_index *idx, uint32_t field, const uint32_t *tokens, const uint32_t *n_tokens, uint32_t B,
+                                  uint32_t t_stride, uint32_t k, const uint64_t *allow_bits, uint32_t *out_ids, double *out_score,
+                                  uint32_t *out_count, double *out_max, uint32_t *out_ncand);
+KDB_API int kdb_text_search_batch_dev(kdb_index *idx, uint32_t field, const uint32_t *d_tokens, const uint32_t *d_n_tokens, uint32_t B,
+                                      uint32_t t_stride, uint32_t k, const uint64_t *d_allow_bits, uint32_t *d_out_ids,
+                                      double *d_out_score, uint32_t *d_out_count, double *d_out_max, uint32_t *d_out_ncand, void *stream);
+KDB_API int kdb_hybrid_search_batch(kdb_index *idx, const float *queries, uint32_t B, uint32_t k, uint32_t ef, uint32_t field,
+                                    const uint32_t *tokens, const uint32_t *n_tokens, uint32_t t_stride, double alpha,
+                                    const uint64_t *allow_bits, uint32_t flags, uint32_t *out_ids, double *out_score,
+                                    uint32_t *out_count);
 
 /* B queries x C candidate ids each (ids[B][C], id 0 = skip -> +inf): raw accumulates out[B][C].   */
 KDB_API int kdb_distance_batch(kdb_index *idx, const float *queries, uint32_t B, const uint32_t *ids, uint32_t C,

@@ -499,6 +499,42 @@ class Index {
         if (cards) *cards = card;
         return out;
     }
+    // ---- BM25 text search and hybrid fusion (kektor_hip.h) ----------------------------------------------------------------
+    // The snapshot of textIndex[index][field] + TextIndexStats, as the caller laid it out (kdb_text_view); throws on a refused view.
+    void SetText(uint32_t field, const kdb_text_view &view) { check(kdb_index_set_text(h_, field, &view), "set_text"); }
+    void DropText(uint32_t field) { check(kdb_index_drop_text(h_, field), "drop_text"); }
+    // FindIDsByTextSearch cut at k for B queries of at most tStride token ids each (tokens[b * tStride + i], nTokens[b]): results[b]
+    // by (score descending, id ascending), Score the raw BM25 sum.  maxScore / nCand: what normalizeTextScores and the caller's
+    // diagnostics need, per query.  Empty lists on any error.
+    std::vector<std::vector<SearchResult>> TextSearch(uint32_t field, const uint32_t *tokens, const uint32_t *nTokens, uint32_t B, uint32_t tStride, int k,
+                                                      const uint64_t *allowBits = nullptr, std::vector<double> *maxScore = nullptr,
+                                                      std::vector<uint32_t> *nCand = nullptr) const {
+        std::vector<std::vector<SearchResult>> out(B);
+        if (!h_ || k <= 0 || B == 0) return out;
+        std::vector<uint32_t> ids((size_t)B * k), cnt(B), nc(B);
+        std::vector<double> score((size_t)B * k), mx(B);
+        if (kdb_text_search_batch(h_, field, tokens, nTokens, B, tStride, (uint32_t)k, allowBits, ids.data(), score.data(), cnt.data(), mx.data(), nc.data()))
+            return out;
+        for (uint32_t b = 0; b < B; b++)
+            for (uint32_t i = 0; i < cnt[b]; i++) out[b].push_back({ids[(size_t)b * k + i], score[(size_t)b * k + i]});
+        if (maxScore) *maxScore = mx;
+        if (nCand) *nCand = nc;
+        return out;
+    }
+    // Engine.VSearch with a text query and MemoryConfig disabled, as ONE call (kdb_hybrid_search_batch): Score is the fused score.
+    std::vector<std::vector<SearchResult>> HybridSearch(const float *queries, uint32_t B, int k, int efSearch, uint32_t field, const uint32_t *tokens,
+                                                        const uint32_t *nTokens, uint32_t tStride, double alpha, const uint64_t *allowBits = nullptr) const {
+        std::vector<std::vector<SearchResult>> out(B);
+        if (!h_ || k <= 0 || B == 0) return out;
+        std::vector<uint32_t> ids((size_t)B * k), cnt(B);
+        std::vector<double> score((size_t)B * k);
+        if (kdb_hybrid_search_batch(h_, queries, B, (uint32_t)k, (uint32_t)(efSearch > 0 ? efSearch : 0), field, tokens, nTokens, tStride, alpha, allowBits,
+                                    flags() & ~(uint32_t)KDB_SEARCH_DIST_F64, ids.data(), score.data(), cnt.data()))
+            return out;
+        for (uint32_t b = 0; b < B; b++)
+            for (uint32_t i = 0; i < cnt[b]; i++) out[b].push_back({ids[(size_t)b * k + i], score[(size_t)b * k + i]});
+        return out;
+    }
     kdb_index *handle() const { return h_; }
     // concurrent kdb_search_batch calls of a few queries share launches inside the library (kektor_hip.h, "Conventions"): a
     // batcher in front of this index passes unfiltered one-query calls through

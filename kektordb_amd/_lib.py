@@ -32,6 +32,8 @@ ABI_SYMBOLS = [
     "kdb_search_batch_mixed", "kdb_search_batch_mixed_dev", "kdb_index_mixed_stats",
     "kdb_index_set_column", "kdb_index_set_column_dev", "kdb_index_drop_column", "kdb_index_column_info",
     "kdb_filter_eval", "kdb_filter_eval_dev", "kdb_filter_parse", "kdb_search_filtered",
+    "kdb_index_set_text", "kdb_index_drop_text", "kdb_index_text_info", "kdb_text_search_batch", "kdb_text_search_batch_dev",
+    "kdb_hybrid_search_batch",
 ]
 
 
@@ -69,6 +71,12 @@ class FilterAtom(C.Structure):  # kdb_filter_atom, 32 bytes
     _fields_ = [("key_off", C.c_uint32), ("key_len", C.c_uint32), ("val_off", C.c_uint32), ("val_len", C.c_uint32),
                 ("op", C.c_uint8), ("flags", C.c_uint8), ("is_numeric", C.c_uint8), ("reserved", C.c_uint8 * 5),
                 ("number", C.c_double)]
+
+
+class TextView(C.Structure):  # kdb_text_view, 64 bytes
+    _fields_ = [("n_tokens", C.c_uint32), ("n_ids", C.c_uint32), ("post_off", C.c_void_p), ("post_doc", C.c_void_p),
+                ("post_tf", C.c_void_p), ("doc_len", C.c_void_p), ("total_docs", C.c_uint64), ("avg_len", C.c_double),
+                ("idf", C.c_void_p)]
 
 
 class BuildParams(C.Structure):
@@ -218,6 +226,12 @@ def load():
     L.kdb_filter_eval_dev.argtypes = [vp, vp, vp, u32, vp, C.c_uint64, vp, vp]
     L.kdb_filter_parse.argtypes = [C.c_char_p, vp, u32, C.POINTER(u32)]
     L.kdb_search_filtered.argtypes = [vp, vp, u32, u32, u32, vp, vp, u32, vp, C.c_double, u32, vp, vp, vp, vp, vp]
+    L.kdb_index_set_text.argtypes = [vp, u32, C.POINTER(TextView)]
+    L.kdb_index_drop_text.argtypes = [vp, u32]
+    L.kdb_index_text_info.argtypes = [vp, u32, C.POINTER(u32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    L.kdb_text_search_batch.argtypes = [vp, u32, vp, vp, u32, u32, u32, vp, vp, vp, vp, vp, vp]
+    L.kdb_text_search_batch_dev.argtypes = [vp, u32, vp, vp, u32, u32, u32, vp, vp, vp, vp, vp, vp, vp]
+    L.kdb_hybrid_search_batch.argtypes = [vp, vp, u32, u32, u32, u32, vp, vp, u32, C.c_double, vp, u32, vp, vp, vp]
     _lib = L
     return L
 

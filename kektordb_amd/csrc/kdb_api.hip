@@ -462,6 +462,8 @@ extern "C" void kdb_index_destroy(kdb_index *idx) {
         if (b) (void)hipFree(b);
     for (void *c : idx->d_col)
         if (c) (void)hipFree(c);
+    for (kdb_text_slot &t : idx->text)
+        if (t.blob) (void)hipFree(t.blob);
     for (kdb_lane &l : idx->lanes) {
         void *lb[] = {l.d_visited, l.d_scratch, l.d_qbuf, l.d_gentry, l.d_work, l.d_tie, l.d_byid};
         for (void *b : lb)

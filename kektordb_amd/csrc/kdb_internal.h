@@ -149,6 +149,21 @@ struct kdb_lane {
     uint64_t last_use = 0;
 };
 
+// Device view of one text snapshot (text.hip; passed by value to its kernels): the arrays of kdb_text_view, in HBM
+struct KdbTextDev {
+    const uint64_t *post_off = nullptr; // [n_tokens + 1]
+    const uint32_t *post_doc = nullptr, *post_tf = nullptr;
+    const uint32_t *doc_len = nullptr;  // [n_ids + 1]
+    const double *idf = nullptr;        // [n_tokens]
+    double avg_len = 0.0;
+    uint32_t n_tokens = 0, n_ids = 0;
+};
+struct kdb_text_slot { // one field's snapshot: ONE allocation that holds every array (blob == null: the slot is empty)
+    void *blob = nullptr;
+    KdbTextDev dev;
+    uint64_t n_postings = 0, bytes = 0;
+};
+
 struct kdb_index {
     kdb_index_desc desc;
     uint32_t ld = 0, deg0 = 0, deg_up = 0, cap = 0;
@@ -191,6 +206,8 @@ struct kdb_index {
     // metadata columns (filter.hip): slot c holds (cap + 1) entries of col_kind[c] (0: the slot is empty, nothing allocated)
     void *d_col[KDB_MAX_COLUMNS] = {};
     uint32_t col_kind[KDB_MAX_COLUMNS] = {};
+    // text snapshots (text.hip, kdb_api_text.hip): independent of cap -- reserve leaves them, compress does not carry them
+    kdb_text_slot text[KDB_MAX_TEXT_FIELDS];
     // scratch that belongs to the index (a call's own scratch: kdb_lane, below)
     void *d_iobuf = nullptr;        // staging of the host-pointer calls that do not fit a slot (big_mu)
     size_t iobuf_bytes = 0;
@@ -404,6 +421,15 @@ int kdb_launch_consensus(const KdbView &v, const uint32_t *d_ids, const uint32_t
 int kdb_launch_col_fill(void *d_col, uint32_t kind, size_t first, size_t n, hipStream_t s);
 int kdb_launch_filter_eval(kdb_index *idx, const kdb_filter_term *terms, const uint32_t *prog_offsets, uint32_t P, uint64_t *d_lists,
                            uint64_t words_per_list, uint32_t *d_card, hipStream_t s);
+// text.hip: FindIDsByTextSearch cut at k for B queries, one workgroup per query (d_max, d_ncand: optional); the fusion of a vector
+// answer (float distances, as kdb_search_batch_dev leaves them) with that text answer, one wave per query
+int kdb_launch_bm25_topk(const KdbTextDev &tx, const uint32_t *d_tokens, const uint32_t *d_n_tokens, uint32_t B, uint32_t t_stride, uint32_t k,
+                         const uint32_t *d_allow, uint32_t count, uint32_t *d_out_ids, double *d_out_score, uint32_t *d_out_count, double *d_max,
+                         uint32_t *d_ncand, hipStream_t s);
+int kdb_launch_hybrid_fuse(const KdbTextDev &tx, const uint32_t *d_tokens, const uint32_t *d_n_tokens, uint32_t B, uint32_t t_stride, uint32_t k,
+                           double alpha, uint32_t one_minus_dot, const uint32_t *d_v_ids, const float *d_v_dist, const uint32_t *d_v_cnt,
+                           const uint32_t *d_t_ids, const double *d_t_score, const uint32_t *d_t_cnt, const double *d_t_max, uint32_t *d_out_ids,
+                           double *d_out_score, uint32_t *d_out_count, hipStream_t s);
 // graph construction (what the three files share: kdb_graph_build.cuh, kdb_walk_lds.h)
 // add.hip: the sequential Add
 int kdb_add_graph(kdb_index *idx, uint32_t first_id, uint32_t n, const uint8_t *levels, uint32_t ef_construction, kdb_add_stats *out);

@@ -42,6 +42,9 @@ FILTER_MAX_TERMS, FILTER_MAX_PROGRAMS = 64, 4096
 FILTER_TILE_IDS, FILTER_CHUNK = 1024, 32  # kdb_filter_plan.h: ids one wave covers per list, programs that share a column fetch
 TERM_DTYPE = np.dtype([("op", "u1"), ("flags", "u1"), ("col", "<u2"), ("code", "<u4"), ("value", "<f8")])  # kdb_filter_term
 ROUTE_WALK, ROUTE_SCAN, ROUTE_EMPTY = 0, 1, 2  # out_route of kdb_search_filtered
+# BM25 text search (kektor_hip.h, "BM25 text search and hybrid fusion")
+MAX_TEXT_FIELDS, TEXT_MAX_TOKENS, TEXT_MAX_K = 4, 32, 1024
+NO_TOKEN = 0xFFFFFFFF  # KDB_NO_TOKEN: a query word the dictionary does not hold
 # kdb_consensus: CalculateConsensus's score, variance and maxVar, len(nodes), len(activeNodes)
 CONSENSUS_DTYPE = np.dtype([("score", "<f8"), ("variance", "<f8"), ("max_pair", "<f8"), ("n_found", "<u4"), ("n_active", "<u4")])
 
@@ -807,6 +810,66 @@ class HipIndex:
                                          _ptr(ids), _ptr(dist), _ptr(cnt), _ptr(route), _ptr(card)), "kdb_search_filtered")
         return ids, dist, cnt, route, card
 
+    # ---- BM25 text search and hybrid fusion on the device (text.hip) ---------------------------------
+    def set_text(self, field: int, text: "TextIndex", idf=None):
+        """Upload the snapshot of a TextIndex into text slot `field` (kdb_index_set_text); idf: None (the library fills the table)
+        or one float64 per token in dictionary order."""
+        self._live()
+        check(self.L.kdb_index_set_text(self.h, field, C.byref(text.view(idf))), "kdb_index_set_text")
+
+    def drop_text(self, field: int):
+        self._live()
+        check(self.L.kdb_index_drop_text(self.h, field), "kdb_index_drop_text")
+
+    def text_info(self, field: int):
+        """(n_tokens, n_postings, bytes) of a text slot; zeros when it is empty"""
+        self._live()
+        nt, npost, nbytes = C.c_uint32(), C.c_uint64(), C.c_uint64()
+        check(self.L.kdb_index_text_info(self.h, field, C.byref(nt), C.byref(npost), C.byref(nbytes)), "kdb_index_text_info")
+        return int(nt.value), int(npost.value), int(nbytes.value)
+
+    def text_search(self, field: int, queries, k: int, allow_bits=None):
+        """DB.FindIDsByTextSearch cut at k for a batch (kdb_text_search_batch).  queries: lists of token ids (TextIndex.tokens makes
+        them; NO_TOKEN for a word the dictionary does not hold).  Returns (ids [B, k], score [B, k] float64, count [B], max [B],
+        ncand [B])."""
+        self._live()
+        tok, nt = pack_token_queries(queries)
+        B = nt.size
+        ids = np.zeros((B, k), dtype=np.uint32)
+        score = np.zeros((B, k), dtype=np.float64)
+        cnt = np.zeros(B, dtype=np.uint32)
+        mx = np.zeros(B, dtype=np.float64)
+        nc = np.zeros(B, dtype=np.uint32)
+        ab = None if allow_bits is None else np.ascontiguousarray(allow_bits, dtype=np.uint64)
+        check(self.L.kdb_text_search_batch(self.h, field, _ptr(tok), _ptr(nt), B, tok.shape[1], k, _ptr(ab), _ptr(ids), _ptr(score), _ptr(cnt),
+                                           _ptr(mx), _ptr(nc)), "kdb_text_search_batch")
+        return ids, score, cnt, mx, nc
+
+    def text_search_dev(self, field: int, d_tokens, d_n_tokens, k: int, d_out_ids, d_out_score, d_out_count, d_out_max=None, d_out_ncand=None,
+                        d_allow=None, stream=None):
+        """torch device tensors in (d_tokens [B, t_stride] int32, d_n_tokens [B] int32), asynchronous on `stream`"""
+        self._live()
+        _ready(stream)
+        check(self.L.kdb_text_search_batch_dev(self.h, field, _tptr(d_tokens), _tptr(d_n_tokens), int(d_tokens.shape[0]), int(d_tokens.shape[1]), k,
+                                               _tptr(d_allow), _tptr(d_out_ids), _tptr(d_out_score), _tptr(d_out_count), _tptr(d_out_max),
+                                               _tptr(d_out_ncand), C.c_void_p(stream) if stream else None), "kdb_text_search_batch_dev")
+
+    def hybrid_search(self, queries, k: int, ef: int, field: int, token_queries, alpha: float = 0.5, allow_bits=None, flags: int = 0):
+        """Engine.VSearch with a text query and no time decay as one call (kdb_hybrid_search_batch): walk, BM25 and the alpha fusion.
+        Returns (ids [B, k], fused score [B, k] float64, count [B])."""
+        self._live()
+        q = np.ascontiguousarray(queries, dtype=np.float32)
+        B = q.shape[0]
+        tok, nt = pack_token_queries(token_queries)
+        assert nt.size == B
+        ids = np.zeros((B, k), dtype=np.uint32)
+        score = np.zeros((B, k), dtype=np.float64)
+        cnt = np.zeros(B, dtype=np.uint32)
+        ab = None if allow_bits is None else np.ascontiguousarray(allow_bits, dtype=np.uint64)
+        check(self.L.kdb_hybrid_search_batch(self.h, _ptr(q), B, k, ef, field, _ptr(tok), _ptr(nt), tok.shape[1], float(alpha), _ptr(ab),
+                                             self._flags(False) | int(flags), _ptr(ids), _ptr(score), _ptr(cnt)), "kdb_hybrid_search_batch")
+        return ids, score, cnt
+
     # ---- the reference's per-query API --------------------------------------------------------------
     def score(self, raw: float) -> float:
         """The reference's f64 epilogue: float64(sum) (distance_go.go:67) / 1.0-float64(dot) (:127)."""
@@ -868,6 +931,56 @@ class HipIndex:
         return {"score": float(rec["score"][0]), "variance": float(rec["variance"][0]), "sources": int(rec["n_found"][0]),
                 "nodes": [SearchResult(int(ids[0, i]), self.score(dist[0, i])) for i in found],
                 "similarities": [float(sim[0, i]) for i in found]}
+
+
+def pack_token_queries(queries):
+    """lists of token ids -> (tokens [B, t_stride] uint32 padded with NO_TOKEN, n_tokens [B] uint32)"""
+    nt = np.array([len(q) for q in queries], dtype=np.uint32)
+    tok = np.full((nt.size, max(1, int(nt.max()) if nt.size else 1)), NO_TOKEN, dtype=np.uint32)
+    for b, q in enumerate(queries):
+        tok[b, :len(q)] = q
+    return tok, nt
+
+
+class TextIndex:
+    """The snapshot kdb_index_set_text takes, built from textIndex[index][field] -- {token: [(doc, tf), ...]} -- and
+    TextIndexStats.DocLengths -- {doc: length}.  Each list is sorted by document; of a repeated document the LAST entry wins
+    (`candidateDocs[doc][token] = tf` overwrites, pkg/core/core.go:2133).  `dictionary` maps a token to its id, in first-seen order.
+    total_docs / avg_len default to the reference's stats: len(doc_lengths) and the mean length."""
+
+    def __init__(self, postings: dict, doc_lengths: dict, n_ids: int = 0, total_docs: Optional[int] = None, avg_len: Optional[float] = None):
+        self.dictionary = {tok: t for t, tok in enumerate(postings)}
+        lists = [sorted(dict(entries).items()) for entries in postings.values()]  # dict(): the last entry of a document wins
+        self.post_off = np.zeros(len(lists) + 1, dtype=np.uint64)
+        self.post_off[1:] = np.cumsum([len(l) for l in lists], dtype=np.uint64)
+        flat = [e for l in lists for e in l]
+        self.post_doc = np.array([d for d, _ in flat], dtype=np.uint32)
+        self.post_tf = np.array([tf for _, tf in flat], dtype=np.uint32)
+        self.n_ids = max([int(n_ids)] + [int(d) for d in doc_lengths] + ([int(self.post_doc.max())] if flat else []))
+        self.doc_len = np.zeros(self.n_ids + 1, dtype=np.uint32)
+        for d, n in doc_lengths.items():
+            self.doc_len[d] = n
+        self.total_docs = len(doc_lengths) if total_docs is None else int(total_docs)
+        self.avg_len = (float(sum(doc_lengths.values())) / len(doc_lengths) if doc_lengths else 0.0) if avg_len is None else float(avg_len)
+
+    @classmethod
+    def from_arrays(cls, post_off, post_doc, post_tf, doc_len, total_docs: int, avg_len: float) -> "TextIndex":
+        """a snapshot already in arrays (token ids are the dictionary): lists sorted by document, no document repeated"""
+        t = cls({}, {})
+        t.dictionary = {i: i for i in range(len(post_off) - 1)}
+        t.post_off, t.post_doc, t.post_tf = (np.ascontiguousarray(a, dtype=d) for a, d in ((post_off, np.uint64), (post_doc, np.uint32), (post_tf, np.uint32)))
+        t.doc_len = np.ascontiguousarray(doc_len, dtype=np.uint32)
+        t.n_ids, t.total_docs, t.avg_len = t.doc_len.size - 1, int(total_docs), float(avg_len)
+        return t
+
+    def tokens(self, words) -> List[int]:
+        """the analyzer's tokens of one query -> token ids (NO_TOKEN for a word the dictionary does not hold)"""
+        return [self.dictionary.get(w, NO_TOKEN) for w in words]
+
+    def view(self, idf=None) -> "_lib.TextView":
+        self._idf = None if idf is None else np.ascontiguousarray(idf, dtype=np.float64)  # (kept alive with the arrays)
+        return _lib.TextView(len(self.dictionary), self.n_ids, _ptr(self.post_off), _ptr(self.post_doc), _ptr(self.post_tf), _ptr(self.doc_len),
+                             self.total_docs, self.avg_len, _ptr(self._idf))
 
 
 def merge_topk(metric: int, ids, dist, count, k: int, id_base=None, precision: int = F32, out=None):
