@@ -608,8 +608,11 @@ KDB_API int kdb_search_filtered(kdb_index *idx, const float *queries, uint32_t B
  * equal scores comes from map iteration and an unstable sort and is unpinned; ascending id is this library's rule --, positions
  * beyond the count holding id 0 and score 0.0; out_max: NULL or the largest candidate score (0.0 with none; normalizeTextScores
  * needs it); out_ncand: NULL or the number of candidates.  1 <= k <= 1024.  The _dev form clamps n_tokens[b] to t_stride.
- * One workgroup of 256 lanes per query sweeps the id space in tiles of 4096 ids with one cursor per token: a query with very long
- * lists runs on one CU.
+ * One workgroup of 256 lanes per query sweeps the id space in tiles of 4096 ids with one cursor per token.  A call of few queries
+ * with long lists gives every query several workgroups, each on its own range of tiles, and merges their lists in a second launch;
+ * the answer is the same to the last bit.  LANES: an unsplit kdb_text_search_batch_dev takes no scratch lane; a
+ * split one takes a lane of its stream for its partial lists, like every other _dev call.  KDB_TEXT_SPLIT (environment, read at
+ * every call): 0 = never split, N = N workgroups per query whatever the size (at most one per tile of ids, at most 512).
  *
  * kdb_hybrid_search_batch (host pointers; a composition like kdb_belief_batch): kdb_search_batch_dev unchanged with (k, ef, allow
  * list, flags), bm25_topk_kernel with the same k and list, then one wave per query fuses.  With d the reference's distance of a
@@ -953,6 +956,14 @@ KDB_API int kdb_probe_launch_shape(kdb_index *idx, uint32_t last_n, uint32_t *ou
  * Launches nothing.  The tests take their thresholds from it: which walks reach the tail, which overflow.                    */
 #define KDB_HEAP_PLAN_WORDS 7u
 KDB_API int kdb_probe_heap_plan(kdb_index *idx, uint32_t k, uint32_t ef, uint32_t B, uint64_t *out);
+/* TEST HOOK: the plan a text search of B queries with this t_stride and k on slot `field` would launch with, KDB_TEXT_SPLIT
+ * honoured.  postings_bound: the most postings one query of the call sweeps (what a host-pointer call sums from its tokens), or
+ * 0 = the bound of the _dev form, the slot's longest list times min(t_stride, 32).  out[KDB_TEXT_PLAN_WORDS]:
+ *   [0] workgroups per query (1 = no split)   [1] bytes of the partial lists   [2] LDS bytes of the merge   [3] the bound used
+ * Launches nothing.  The answers of a split call are those of an unsplit one bit for bit: the tests know from here which they ran. */
+#define KDB_TEXT_PLAN_WORDS 4u
+KDB_API int kdb_probe_text_plan(kdb_index *idx, uint32_t field, uint32_t B, uint32_t t_stride, uint32_t k, uint64_t postings_bound,
+                                uint64_t *out);
 
 KDB_API int kdb_get_counters(kdb_index *idx, kdb_counters *out);
 /* Statistics of the last `last_n` (<= 64) search / flat-scan / distance launches, oldest first: each

@@ -33,7 +33,7 @@ ABI_SYMBOLS = [
     "kdb_index_set_column", "kdb_index_set_column_dev", "kdb_index_drop_column", "kdb_index_column_info",
     "kdb_filter_eval", "kdb_filter_eval_dev", "kdb_filter_parse", "kdb_search_filtered",
     "kdb_index_set_text", "kdb_index_drop_text", "kdb_index_text_info", "kdb_text_search_batch", "kdb_text_search_batch_dev",
-    "kdb_hybrid_search_batch",
+    "kdb_hybrid_search_batch", "kdb_probe_text_plan",
 ]
 
 
@@ -232,6 +232,7 @@ def load():
     L.kdb_text_search_batch.argtypes = [vp, u32, vp, vp, u32, u32, u32, vp, vp, vp, vp, vp, vp]
     L.kdb_text_search_batch_dev.argtypes = [vp, u32, vp, vp, u32, u32, u32, vp, vp, vp, vp, vp, vp, vp]
     L.kdb_hybrid_search_batch.argtypes = [vp, vp, u32, u32, u32, u32, vp, vp, u32, C.c_double, vp, u32, vp, vp, vp]
+    L.kdb_probe_text_plan.argtypes = [vp, u32, u32, u32, u32, C.c_uint64, vp]
     _lib = L
     return L
 

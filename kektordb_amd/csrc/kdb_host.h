@@ -78,7 +78,10 @@ struct DevCall {
     ~DevCall() { if (laned) (void)kdb_lane_release(idx, s); }
     int enter(bool lane) {
         KDB_HIP(hipSetDevice(idx->device));
-        if (!lane) return KDB_OK;
+        return lane ? take_lane() : (int)KDB_OK;
+    }
+    int take_lane() { // also for a call that learns under idx->mu that it needs scratch after all (a split text search)
+        if (laned) return KDB_OK;
         const int r = kdb_lane_acquire(idx, s);
         laned = r == KDB_OK;
         return r;

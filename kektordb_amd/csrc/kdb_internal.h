@@ -162,6 +162,10 @@ struct kdb_text_slot { // one field's snapshot: ONE allocation that holds every 
     void *blob = nullptr;
     KdbTextDev dev;
     uint64_t n_postings = 0, bytes = 0;
+    // what the split plan (kdb_text_split_plan) is fed from: post_off once more on the host (V + 1 words: a host-pointer call sums
+    // its queries' lists exactly) and the longest list (the bound of a _dev call, whose tokens the host does not see)
+    std::vector<uint64_t> h_post_off;
+    uint64_t longest = 0;
 };
 
 struct kdb_index {
@@ -421,11 +425,14 @@ int kdb_launch_consensus(const KdbView &v, const uint32_t *d_ids, const uint32_t
 int kdb_launch_col_fill(void *d_col, uint32_t kind, size_t first, size_t n, hipStream_t s);
 int kdb_launch_filter_eval(kdb_index *idx, const kdb_filter_term *terms, const uint32_t *prog_offsets, uint32_t P, uint64_t *d_lists,
                            uint64_t words_per_list, uint32_t *d_card, hipStream_t s);
-// text.hip: FindIDsByTextSearch cut at k for B queries, one workgroup per query (d_max, d_ncand: optional); the fusion of a vector
-// answer (float distances, as kdb_search_batch_dev leaves them) with that text answer, one wave per query
+// text.hip: FindIDsByTextSearch cut at k for B queries (d_max, d_ncand: optional) -- one workgroup per query, or plan.parts per query
+// with their partial lists in d_parts (plan.scratch_bytes; unused when plan.parts == 1) and a merge launch behind them
+// (kdb_text_plan.h); the fusion of a vector answer (float distances, as kdb_search_batch_dev leaves them) with that text answer, one
+// wave per query
+struct KdbTextSplitPlan;
 int kdb_launch_bm25_topk(const KdbTextDev &tx, const uint32_t *d_tokens, const uint32_t *d_n_tokens, uint32_t B, uint32_t t_stride, uint32_t k,
                          const uint32_t *d_allow, uint32_t count, uint32_t *d_out_ids, double *d_out_score, uint32_t *d_out_count, double *d_max,
-                         uint32_t *d_ncand, hipStream_t s);
+                         uint32_t *d_ncand, const KdbTextSplitPlan &plan, void *d_parts, hipStream_t s);
 int kdb_launch_hybrid_fuse(const KdbTextDev &tx, const uint32_t *d_tokens, const uint32_t *d_n_tokens, uint32_t B, uint32_t t_stride, uint32_t k,
                            double alpha, uint32_t one_minus_dot, const uint32_t *d_v_ids, const float *d_v_dist, const uint32_t *d_v_cnt,
                            const uint32_t *d_t_ids, const double *d_t_score, const uint32_t *d_t_cnt, const double *d_t_max, uint32_t *d_out_ids,

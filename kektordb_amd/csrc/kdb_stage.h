@@ -32,7 +32,7 @@ struct KdbRegion {
 // caller copies piece by piece itself.  copy_in / copy_out make one copy per present region, in declaration order, through
 // copy(dst, src, bytes) -> 0 or an error code that ends the walk (the library: hipMemcpyAsync on the turn's stream; the test: memcpy).
 struct KdbStage {
-    static constexpr int CAP = 8; // (the consensus call has eight regions)
+    static constexpr int CAP = 9; // (the text call has nine regions)
     struct Slot {
         KdbRegion r;
         const void *src;

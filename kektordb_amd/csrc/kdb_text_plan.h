@@ -67,6 +67,99 @@ KDB_TEXT_HD constexpr uint32_t kdb_fuse_sort_n(uint32_t k) { return 2u * kdb_tex
 KDB_TEXT_HD constexpr uint32_t kdb_fuse_lds_bytes(uint32_t k) { return kdb_fuse_sort_n(k) * 12u + 3u * KDB_TEXT_MAX_TOKENS * 8u; }
 static_assert(kdb_fuse_lds_bytes(KDB_TEXT_MAX_K) <= KDB_TEXT_LDS_LIMIT, "hybrid_fuse_kernel fits a CU's LDS at the largest k");
 
+// ---- one query on many workgroups -------------------------------------------------------------------------------------------------
+// bm25_topk_kernel<true> on a grid of (parts, B): workgroup (s, b) sweeps the ids of [bnd(s), bnd(s + 1)) of query b and leaves its
+// own top-k, its count and its candidates in HBM; bm25_merge_kernel, one workgroup per query behind it on the same stream, offers the
+// partial lists to one more top-k array and writes the answer.  The order (key descending, id ascending) is total and every part's
+// list is its own top-k, so the merged answer is the one-workgroup answer bit for bit.
+constexpr uint32_t KDB_TEXT_MAX_PARTS = 512u;
+constexpr uint32_t KDB_TEXT_MIN_TILES_PER_PART = 1u;   // measured: one query over 245 tiles was fastest at a part per tile
+constexpr uint64_t KDB_TEXT_SPLIT_MIN_POSTINGS = 64u;  // measured: from 64 postings up the split was faster in every class; at
+                                                       // 16 and 32 the prologue and the second launch cost more than the few tiles they spread
+constexpr uint32_t KDB_TEXT_WG_PER_CU = 2u;                  // the LDS budget above: two workgroups per CU
+
+struct KdbTextSplitIn {
+    uint32_t B, k, n_ids, n_cus;
+    uint64_t postings_bound; // no query of the call sweeps more postings than this
+    int32_t forced;          // KDB_TEXT_SPLIT: < 0 unset, 0 never split, N >= 1 exactly N parts (capped by the tiles and KDB_TEXT_MAX_PARTS)
+};
+struct KdbTextSplitPlan {
+    uint32_t parts;         // 1: bm25_topk_kernel<false>, one workgroup per query, no scratch and no merge
+    uint64_t scratch_bytes; // the partial lists (0 when parts == 1)
+    uint32_t merge_lds;     // LDS of bm25_merge_kernel
+};
+// LDS of bm25_merge_kernel, the top-k array alone: keys [N] u64 | threshold key u64 | ids [N] u32 | words [16] u32
+struct KdbTextMergeLds {
+    uint32_t o_keys, o_thr, o_ids, o_words, total;
+};
+KDB_TEXT_HD constexpr KdbTextMergeLds kdb_text_merge_lds(uint32_t k) {
+    KdbTextMergeLds L{};
+    const uint32_t n = kdb_text_sort_n(k);
+    L.o_keys = 0;
+    L.o_thr = n * 8u;
+    L.o_ids = L.o_thr + 8u;
+    L.o_words = L.o_ids + n * 4u;
+    L.total = L.o_words + 16u * 4u;
+    return L;
+}
+static_assert(kdb_text_merge_lds(KDB_TEXT_MAX_K).total <= KDB_TEXT_LDS_LIMIT, "bm25_merge_kernel fits a CU's LDS at the largest k");
+// The partial lists, R = B * parts records, record r = b * parts + s: keys [R][k] u64 | (count, candidates) [R][2] u32 | ids [R][k] u32
+// -- 12 k + 8 bytes a record, every array on an 8-byte boundary, the whole rounded up to one.
+struct KdbTextParts {
+    uint64_t o_keys, o_counts, o_ids, total;
+};
+KDB_TEXT_HD constexpr KdbTextParts kdb_text_parts(uint32_t B, uint32_t parts, uint32_t k) {
+    KdbTextParts P{};
+    const uint64_t R = (uint64_t)B * parts;
+    P.o_keys = 0;
+    P.o_counts = R * k * 8u;
+    P.o_ids = P.o_counts + R * 8u;
+    P.total = (P.o_ids + R * k * 4u + 7u) & ~7ull; // = R * (12 k + 8), rounded up
+    return P;
+}
+KDB_TEXT_HD constexpr uint32_t kdb_text_tiles(uint32_t n_ids) { return (uint32_t)(((uint64_t)n_ids + 1u + KDB_TEXT_TILE - 1u) / KDB_TEXT_TILE); }
+KDB_TEXT_HD constexpr KdbTextSplitPlan kdb_text_split_plan(const KdbTextSplitIn &in) {
+    const uint32_t tiles = kdb_text_tiles(in.n_ids);
+    uint32_t parts = 1;
+    if (in.forced > 0) {
+        parts = (uint32_t)in.forced < tiles ? (uint32_t)in.forced : tiles; // one tile per part at least
+    } else if (in.forced < 0 && in.B && in.postings_bound >= KDB_TEXT_SPLIT_MIN_POSTINGS) {
+        parts = (uint32_t)(((uint64_t)KDB_TEXT_WG_PER_CU * in.n_cus + in.B - 1u) / in.B); // about two workgroups per CU for the whole call
+        if (parts > tiles / KDB_TEXT_MIN_TILES_PER_PART) parts = tiles / KDB_TEXT_MIN_TILES_PER_PART;
+    }
+    if (parts > KDB_TEXT_MAX_PARTS) parts = KDB_TEXT_MAX_PARTS;
+    if (parts < 2u || in.B > 65535u) parts = 1; // (the queries are the grid's second dimension)
+    return KdbTextSplitPlan{parts, parts > 1u ? kdb_text_parts(in.B, parts, in.k).total : 0ull, kdb_text_merge_lds(in.k).total};
+}
+// The boundaries balance POSTINGS, not ids (documents arrive in time order and rare words cluster: equal id ranges would leave most
+// parts empty).  They are cut from the query's LONGEST list, postings [a, a + len) -- among equal lengths the earliest token --:
+//   bnd(0) = 0, bnd(parts) = 2^32 (past every id), bnd(s) = post_doc[a + floor(s * len / parts)] rounded down to a tile.
+// Non-decreasing; equal bounds make an empty part; the ranges partition the id space, and a tile lies inside one part.  Every part
+// computes both of its bounds with this routine, so the parts of a query agree.  len == 0 (no list at all): nothing is read.
+struct KdbTextSpan {
+    uint64_t a, len;
+};
+KDB_TEXT_HD inline KdbTextSpan kdb_text_longest(const uint64_t *lo, const uint64_t *hi, uint32_t T) {
+    KdbTextSpan sp{0, 0};
+    for (uint32_t t = 0; t < T; t++)
+        if (hi[t] - lo[t] > sp.len) sp = KdbTextSpan{lo[t], hi[t] - lo[t]};
+    return sp;
+}
+KDB_TEXT_HD inline uint64_t kdb_text_split_bound(const uint32_t *post_doc, KdbTextSpan sp, uint32_t parts, uint32_t s) {
+    if (s == 0u || sp.len == 0u) return s >= parts ? 1ull << 32 : 0ull;
+    if (s >= parts) return 1ull << 32;
+    return post_doc[sp.a + (uint64_t)s * sp.len / parts] & ~(KDB_TEXT_TILE - 1u); // s < 512, len < 2^40: no overflow
+}
+// the first posting of [lo, hi) whose document is not below `bound`
+KDB_TEXT_HD inline uint64_t kdb_text_lower_bound(const uint32_t *post_doc, uint64_t lo, uint64_t hi, uint64_t bound) {
+    while (lo < hi) {
+        const uint64_t m = lo + ((hi - lo) >> 1);
+        if ((uint64_t)post_doc[m] < bound) lo = m + 1u;
+        else hi = m;
+    }
+    return lo;
+}
+
 // ---- the arithmetic ---------------------------------------------------------------------------------------------------------------
 // calculateBM25TermScore (pkg/core/core.go:2159-2190) for a token the document holds (tf >= 1): the operations and their order are
 // the reference's, in double; the library is built with -ffp-contract=off, so no multiply-add is fused.

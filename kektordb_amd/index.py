@@ -845,9 +845,18 @@ class HipIndex:
                                            _ptr(mx), _ptr(nc)), "kdb_text_search_batch")
         return ids, score, cnt, mx, nc
 
+    def text_plan(self, field: int, B: int, t_stride: int, k: int, postings_bound: int = 0):
+        """TEST HOOK: (workgroups per query, bytes of the partial lists, LDS bytes of the merge, the postings bound used) of a text
+        search of B queries (kdb_probe_text_plan); postings_bound 0: the bound of text_search_dev.  Launches nothing."""
+        self._live()
+        arr = np.zeros(4, dtype=np.uint64)
+        check(self.L.kdb_probe_text_plan(self.h, field, int(B), int(t_stride), int(k), int(postings_bound), _ptr(arr)), "kdb_probe_text_plan")
+        return tuple(int(x) for x in arr)
+
     def text_search_dev(self, field: int, d_tokens, d_n_tokens, k: int, d_out_ids, d_out_score, d_out_count, d_out_max=None, d_out_ncand=None,
                         d_allow=None, stream=None):
-        """torch device tensors in (d_tokens [B, t_stride] int32, d_n_tokens [B] int32), asynchronous on `stream`"""
+        """torch device tensors in (d_tokens [B, t_stride] int32, d_n_tokens [B] int32), asynchronous on `stream`.  Takes a scratch lane
+        only when the call is split over several workgroups per query (text_plan)."""
         self._live()
         _ready(stream)
         check(self.L.kdb_text_search_batch_dev(self.h, field, _tptr(d_tokens), _tptr(d_n_tokens), int(d_tokens.shape[0]), int(d_tokens.shape[1]), k,

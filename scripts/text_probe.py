@@ -13,7 +13,10 @@ The legs ALTERNATE in one process, --reps times after --warmup rounds; medians, 
 most --host-queries queries per round (their time per query is what is reported).  Before anything is timed the device call must
 equal host_bm25 bit for bit on the first queries.
 
-usage: python scripts/text_probe.py [--docs N] [--out profiles/text_probe.json]"""
+--split measures one query on many workgroups instead (split_probe, below): this tree against a built checkout of the parent commit,
+call by call, then the forced part counts and the posting counts from which splitting pays.
+
+usage: python scripts/text_probe.py [--docs N] [--out profiles/text_probe.json] [--split [--parent-tree DIR]]"""
 import argparse
 import json
 import os
@@ -64,8 +67,95 @@ def host_bm25(snap, idf, query, k):
     return docs[order], score[order], (score.max() if docs.size else 0.0), docs.size
 
 
+def split_worker(a):
+    """--worker: the corpus on the device of the tree given by --tree; then one timed kdb_text_search_batch per request line
+    {"q": queries, "split": KDB_TEXT_SPLIT or null} -> {"s": seconds, "ncand": candidates, "digest": of the answer}"""
+    import hashlib
+    sys.path.insert(0, a.tree)
+    import kektordb_amd as K
+    post_off, post_doc, post_tf, doc_len, _ = make_corpus(a, np.random.default_rng(5))
+    snap = K.TextIndex.from_arrays(post_off, post_doc, post_tf, doc_len, a.docs, float(a.doc_tokens))
+    df = np.diff(post_off.astype(np.int64)).astype(np.float64)
+    idx = K.HipIndex(16, K.L2, K.F32, capacity=a.docs)
+    idx.upload_rows(np.zeros((a.docs, 16), dtype=np.float32), 1)
+    idx.set_count(a.docs)
+    idx.set_text(0, snap, np.log(1 + (a.docs - df + 0.5) / (df + 0.5)))
+    print(json.dumps({"ready": True, "stream_GBps": round(idx.probe_stream(), 1)}), flush=True)
+    for line in sys.stdin:
+        req = json.loads(line)
+        os.environ.pop("KDB_TEXT_SPLIT", None)
+        if req["split"] is not None:
+            os.environ["KDB_TEXT_SPLIT"] = str(req["split"])
+        t0 = time.perf_counter()
+        out = idx.text_search(0, req["q"], a.k)
+        dt = time.perf_counter() - t0
+        print(json.dumps({"s": dt, "ncand": int(out[4].astype(np.int64).sum()), "digest": hashlib.sha1(b"".join(x.tobytes() for x in out)).hexdigest()[:12]}), flush=True)
+
+
+def split_probe(a):
+    """--split: one query on many workgroups.  Workers of this tree and, with --parent-tree, of a built checkout of the parent commit
+    hold the same corpus; the driver sends ONE call at a time, so legs alternate call by call in one session on one box.
+      table 1  B = 1, 8, 64, 4096: this tree against the parent (or, without one, against KDB_TEXT_SPLIT=0), factors, spreads,
+               posting bytes per second beside the streaming ceiling;
+      table 2  B = 1, the first query, forced 32 / 64 / 128 / 245 / 512 parts;
+      table 3  B = 1, one token per query, lists of growing length: the fastest forced setting of table 2 against KDB_TEXT_SPLIT=0."""
+    import subprocess
+    rng = np.random.default_rng(5)
+    post_off, _, _, _, queries = make_corpus(a, rng)
+    df = np.diff(post_off.astype(np.int64))
+    base = [sys.executable, os.path.abspath(__file__), "--worker", "--docs", str(a.docs), "--doc-tokens", str(a.doc_tokens), "--vocab", str(a.vocab),
+            "--zipf", str(a.zipf), "--queries", str(a.queries), "--k", str(a.k)]
+    trees = {"this": ROOT, **({"parent": a.parent_tree} if a.parent_tree else {})}
+    procs = {n: subprocess.Popen(base + ["--tree", t], stdin=subprocess.PIPE, stdout=subprocess.PIPE, text=True, env={k: v for k, v in os.environ.items() if k != "KDB_TEXT_SPLIT"}) for n, t in trees.items()}
+    ceiling = {n: json.loads(p.stdout.readline())["stream_GBps"] for n, p in procs.items()}
+    log("workers ready, streaming ceilings", ceiling)
+
+    def call(who, q, split=None):
+        procs[who].stdin.write(json.dumps({"q": q, "split": split}) + "\n")
+        procs[who].stdin.flush()
+        return json.loads(procs[who].stdout.readline())
+
+    def race(legs, q):  # legs: {name: (worker, KDB_TEXT_SPLIT)}; alternating; every leg must give the same answer
+        times, last = {n: [] for n in legs}, {}
+        for r in range(a.warmup + a.reps):
+            for n, (who, split) in legs.items():
+                last[n] = call(who, q, split)
+                if r >= a.warmup:
+                    times[n].append(last[n]["s"])
+        assert len({v["digest"] for v in last.values()}) == 1, last
+        return {n: ms(t) for n, t in times.items()}, next(iter(last.values()))["ncand"]
+
+    other = ("parent", None) if a.parent_tree else ("this", 0)
+    out = {"docs": a.docs, "k": a.k, "reps": a.reps, "against": "parent commit" if a.parent_tree else "KDB_TEXT_SPLIT=0", "stream_ceiling_GBps": ceiling["this"], "by_B": {}}
+    for B in (1, 8, 64, a.queries):
+        q = queries[:B]
+        t, ncand = race({"this": ("this", None), "other": other}, q)
+        byts = 8 * int(sum(int(df[tok]) for x in q for tok in x)) + 4 * ncand
+        out["by_B"][f"B{B}"] = {**t, "factor": round(t["other"]["median_ms"] / t["this"]["median_ms"], 3),
+                               "posting_GBps": round(byts / t["this"]["median_ms"] / 1e6, 2), "of_ceiling": round(byts / t["this"]["median_ms"] / 1e6 / ceiling["this"], 4)}
+        log(f"B{B}", out["by_B"][f"B{B}"])
+    t, _ = race({f"parts{n}": ("this", n) for n in (32, 64, 128, 245, 512)}, queries[:1])
+    out["by_parts_B1"] = t
+    best = int(min(t, key=lambda n: t[n]["median_ms"])[5:])
+    log("parts", t, "fastest", best)
+    out["by_postings_B1"] = {}
+    for want in [1 << e for e in range(0, 20)] + [int(df.max())]:
+        tok = int(np.argmin(np.abs(df - want)))
+        t, _ = race({"split": ("this", best), "unsplit": ("this", 0)}, [[tok]])
+        out["by_postings_B1"][str(int(df[tok]))] = {n: v["median_ms"] for n, v in t.items()}
+        log("postings", int(df[tok]), out["by_postings_B1"][str(int(df[tok]))])
+    for p in procs.values():
+        p.stdin.close()
+        p.wait()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--split", action="store_true", help="measure the split sweep only; merged into --out under 'split'")
+    ap.add_argument("--parent-tree", default=None, help="--split: a built checkout of the parent commit to race against")
+    ap.add_argument("--worker", action="store_true", help=argparse.SUPPRESS)
+    ap.add_argument("--tree", default=ROOT, help=argparse.SUPPRESS)
     ap.add_argument("--docs", type=int, default=1_000_000)
     ap.add_argument("--doc-tokens", type=int, default=40)
     ap.add_argument("--vocab", type=int, default=50_000)
@@ -80,6 +170,18 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "text_probe.json"))
     a = ap.parse_args()
+    if a.worker:
+        return split_worker(a)
+    if a.split:
+        old = {}
+        if os.path.exists(a.out):
+            with open(a.out) as f:
+                old = json.load(f)
+        old["split"] = split_probe(a)
+        with open(a.out, "w") as f:
+            json.dump(old, f, indent=1)
+        print(json.dumps(old["split"]))
+        return
     import torch
     import kektordb_amd as K
     from kektordb_amd.index import pack_token_queries
@@ -123,7 +225,7 @@ def main():
         idx.text_search_dev(0, d_tok, d_nt, k, d_ids, d_score, d_cnt, None, d_nc)
         idx.sync()
 
-    sizes = sorted({1, min(64, a.queries), a.queries})
+    sizes = sorted({1, min(8, a.queries), min(64, a.queries), a.queries})
     legs = {f"text_B{B}": (lambda B=B: idx.text_search(0, queries[:B], k)) for B in sizes}
     legs["host_bm25"] = lambda: [host_bm25(snap, idf, q, k) for q in queries[:hq]]
     legs["kernel"] = kernel_only
