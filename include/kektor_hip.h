@@ -628,8 +628,9 @@ KDB_API int kdb_search_filtered(kdb_index *idx, const float *queries, uint32_t B
  * exception: two DISTINCT text scores can round to the same product with (1-alpha); then id order and score order may disagree at
  * the cut, and the reference's own order (an unstable sort over map iteration) is unpinned too.
  * Out of scope: time decay (ops.go:1100-1187: pow and exp, which no device routine matches bit for bit, and which breaks the
- * argument above) -- the call is VSearch with the index's MemoryConfig disabled; graph filters; the text-only case (:977-996),
- * which the mirror serves with kdb_text_search_batch.  KDB_SEARCH_PREPARED, KDB_SEARCH_DIST_F64 and KDB_SEARCH_FAIL_ON_DROP are
+ * argument above) -- the call is VSearch with the index's MemoryConfig disabled; the text-only case (:977-996),
+ * which the mirror serves with kdb_text_search_batch.  A request with a graph_query makes its allow list with
+ * kdb_graph_filter_eval[_dev] (below) and passes it as allow_bits.  KDB_SEARCH_PREPARED, KDB_SEARCH_DIST_F64 and KDB_SEARCH_FAIL_ON_DROP are
  * refused.  Takes turns on the staging buffer like kdb_search_by_id and is never combined with other callers' queries. */
 #define KDB_MAX_TEXT_FIELDS 4u
 #define KDB_TEXT_MAX_TOKENS 32u
@@ -658,6 +659,64 @@ KDB_API int kdb_hybrid_search_batch(kdb_index *idx, const float *queries, uint32
                                     const uint32_t *tokens, const uint32_t *n_tokens, uint32_t t_stride, double alpha,
                                     const uint64_t *allow_bits, uint32_t flags, uint32_t *out_ids, double *out_score,
                                     uint32_t *out_count);
+
+/* ---- graph filters on the device (graph_filter.hip; geometry and validation in kdb_graph_plan.h) -------------------------------
+ * The third allow-list source of Engine.VSearch (pkg/engine/ops.go:927-963): resolveGraphFilter (pkg/engine/graph.go:173-246)
+ * walks the relation graph from a root and allows what it reaches.  Restated, not improved: the root's internal id is allowed if
+ * the index knows it; a FIFO BFS over graph nodes with a visited set; a node popped at depth >= maxDepth is not expanded
+ * (maxDepth <= 0 becomes 1, > 5 becomes 5); direction "out", "both" or "" follows the ACTIVE (DeletedAt == 0,
+ * pkg/core/graph.go:253-310) out-edges of every relation the query names, "in" or "both" the active in-edges, any other string
+ * nothing; an empty relation set follows nothing (the allowed set is the root alone); every newly seen node is enqueued whether
+ * or not the index holds it, only nodes with an internal id are allowed; nothing is ANDed with "not deleted".
+ *
+ * THE SNAPSHOT.  kdb_relations_view is the active out-edges as a CSR over graph nodes 1..n_nodes: node g's edges are entries
+ * off[g] .. off[g+1] of dst (graph nodes) and rel (the mirror's relation code, < KDB_GRAPH_MAX_RELATIONS, so a query's relation set
+ * is one 64-bit mask); off has n_nodes + 2 entries and node 0 has no edges (off[0] = off[1] = 0).  NUMBERING: node g <= capacity IS
+ * internal id g; nodes above it are ids the index does not hold -- traversed, never allowed; the mirror numbers them.  The library
+ * builds the transposed CSR (the in-lists: AddEdge / RemoveEdge keep them in step, graph.go:112-250) on the host at upload and
+ * keeps both in ONE allocation.  kdb_index_set_relations is a writer in the sense of "Conventions" and replaces the slot wholesale.
+ * Refused with KDB_ERR_INVALID, nothing written: offsets that decrease or do not start at 0; a dst that is 0 or above n_nodes; a
+ * rel >= 64; n_nodes of 0 or above 2^31.  Duplicate edges and self loops are legal.  kdb_index_reserve leaves the slot alone,
+ * kdb_index_compress does not carry it, kdb_index_destroy frees it; an index that never uploads one allocates nothing.
+ * kdb_index_relations_info: zeros for an empty slot.  The shim uploads again after VLink / VUnlink / VDelete.
+ *
+ * kdb_graph_filter_eval[_dev]: B queries (1 <= B <= KDB_GRAPH_MAX_QUERIES), a HOST array in both forms, staged by the library as
+ * kdb_filter_eval_dev stages `terms`.  direction: KDB_GDIR_*; NONE = a direction string the reference does not know.  max_depth is
+ * the raw value, the library clamps.  root == 0 (the mirror does not know the id in the graph): the list is empty.  A root above
+ * n_nodes or a direction above 3 is KDB_ERR_INVALID.  Output: B lists back to back, words_per_list >= (max(count, n_nodes)>>6)+1
+ * uint64 words each, in the layout of kdb_filter_eval; EVERY word is written: bit 0 clear, bits above count clear, padding words
+ * zero.  card: NULL or B uint32.  and_lists: NULL, or n_and_lists lists of the same stride (device memory in the _dev form, not
+ * overlapping the output) with and_of_query[b] (host, B entries) = the list query b's result is ANDed with before its cardinality
+ * is taken, KDB_NO_FILTER = none -- allowList.And(graphAllowList), ops.go:950-957: a kdb_filter_eval_dev result on the same stream
+ * joins without leaving the device.  The _dev form is asynchronous on `stream` and takes a scratch lane of it; the host form takes
+ * turns on the staging buffer like kdb_filter_eval (out_lists may be NULL when only out_card is wanted; not both).
+ * The visited set of a query IS its output list; two frontier bitmaps per query live in the lane's scratch.  One launch per BFS
+ * level (at most 5) between an init and a finish launch; a level sweeps every query's frontier bitmap on (parts, B) workgroups,
+ * expands nodes of degree <= 16 lane-privately and heavier ones from a hub queue in LDS with all 256 lanes (kdb_graph_plan.h).
+ * A call whose frontiers would take more than 256 MB runs as consecutive chunks of queries on the same stream.  Environment, read
+ * at every call: KDB_GRAPH_PARTS = N forces the workgroups per query (at most one per frontier word, at most 512);
+ * KDB_GRAPH_SCRATCH_MAX = bytes replaces the 256 MB.
+ * Out of scope: a one-call request (kdb_search_filtered with a graph query); VExtractSubgraph / VTraverse / pathfinding; atTime
+ * snapshots; incremental edge updates; a single-launch LDS-queue variant for tiny frontiers. */
+#define KDB_GRAPH_MAX_RELATIONS 64u
+#define KDB_GRAPH_MAX_QUERIES 4096u
+enum { KDB_GDIR_OUT = 0, KDB_GDIR_IN = 1, KDB_GDIR_BOTH = 2, KDB_GDIR_NONE = 3 };
+typedef struct {
+    uint32_t n_nodes;           /* graph nodes 1..n_nodes */
+    uint32_t reserved;
+    const uint64_t *off;        /* [n_nodes + 2] */
+    const uint32_t *dst;        /* [off[n_nodes + 1]] */
+    const uint8_t *rel;         /* [off[n_nodes + 1]] */
+} kdb_relations_view; /* 32 bytes */
+typedef struct { uint32_t root; int32_t max_depth; uint32_t direction; uint32_t reserved; uint64_t rel_mask; } kdb_graph_query; /* 24 bytes */
+KDB_API int kdb_index_set_relations(kdb_index *idx, const kdb_relations_view *v);
+KDB_API int kdb_index_drop_relations(kdb_index *idx);
+KDB_API int kdb_index_relations_info(kdb_index *idx, uint32_t *n_nodes, uint64_t *n_edges, uint64_t *bytes);
+KDB_API int kdb_graph_filter_eval_dev(kdb_index *idx, const kdb_graph_query *queries, uint32_t B, uint64_t *d_lists, uint64_t words_per_list,
+                                      uint32_t *d_card, const uint64_t *d_and_lists, uint32_t n_and_lists, const uint32_t *and_of_query,
+                                      void *stream);
+KDB_API int kdb_graph_filter_eval(kdb_index *idx, const kdb_graph_query *queries, uint32_t B, uint64_t *out_lists, uint64_t words_per_list,
+                                  uint32_t *out_card, const uint64_t *and_lists, uint32_t n_and_lists, const uint32_t *and_of_query);
 
 /* B queries x C candidate ids each (ids[B][C], id 0 = skip -> +inf): raw accumulates out[B][C].   */
 KDB_API int kdb_distance_batch(kdb_index *idx, const float *queries, uint32_t B, const uint32_t *ids, uint32_t C,

@@ -9,6 +9,7 @@
 // to an empty result exactly like the reference (":356-359 slog.Error + empty slice"); everything else
 // throws kektor::Error carrying kdb_last_error().
 #pragma once
+#include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <climits>
@@ -533,6 +534,38 @@ class Index {
             return out;
         for (uint32_t b = 0; b < B; b++)
             for (uint32_t i = 0; i < cnt[b]; i++) out[b].push_back({ids[(size_t)b * k + i], score[(size_t)b * k + i]});
+        return out;
+    }
+    // ---- graph filters (kektor_hip.h) --------------------------------------------------------------------------------------
+    // The active out-edges as the caller laid them out (kdb_relations_view); throws on a refused view.  Replaces the snapshot before it.
+    void SetRelations(const kdb_relations_view &view) { check(kdb_index_set_relations(h_, &view), "set_relations"); }
+    void DropRelations() { check(kdb_index_drop_relations(h_), "drop_relations"); }
+    void RelationsInfo(uint32_t *nNodes, uint64_t *nEdges, uint64_t *bytes) const { check(kdb_index_relations_info(h_, nNodes, nEdges, bytes), "relations_info"); }
+    // One kdb_graph_query from a GraphQuery's fields: root = the graph node number of RootID (0: unknown), relMask = the OR of
+    // 1 << code over its Relations; the direction strings as graph.go:206-233 reads them.
+    static kdb_graph_query MakeGraphQuery(uint32_t root, uint64_t relMask, const std::string &direction = "out", int maxDepth = 1) {
+        const uint32_t dir = direction == "out" || direction.empty() ? KDB_GDIR_OUT : direction == "in" ? KDB_GDIR_IN : direction == "both" ? KDB_GDIR_BOTH : KDB_GDIR_NONE;
+        return kdb_graph_query{root, (int32_t)maxDepth, dir, 0u, relMask};
+    }
+    // resolveGraphFilter for several GraphQuery records in one call: lists[b] as an AllowList, cards[b] its cardinality.  andLists /
+    // andOfQuery (KDB_NO_FILTER: none): the metadata list each result is ANDed with (allowList.And(graphAllowList)), flat, one list of
+    // (max(Count(), nodes) >> 6) + 1 words behind the other.
+    std::vector<AllowList> GraphFilter(const std::vector<kdb_graph_query> &queries, std::vector<uint32_t> *cards = nullptr,
+                                       const std::vector<uint64_t> *andLists = nullptr, const std::vector<uint32_t> *andOfQuery = nullptr) const {
+        uint32_t nodes = 0;
+        RelationsInfo(&nodes, nullptr, nullptr);
+        const uint32_t B = (uint32_t)queries.size(), count = Count();
+        const uint64_t words = ((uint64_t)std::max(count, nodes) >> 6) + 1;
+        std::vector<uint64_t> flat((size_t)B * words);
+        std::vector<uint32_t> card(B);
+        check(kdb_graph_filter_eval(h_, queries.data(), B, flat.data(), words, card.data(), andLists ? andLists->data() : nullptr,
+                                    andLists ? (uint32_t)(andLists->size() / words) : 0u, andOfQuery ? andOfQuery->data() : nullptr), "graph_filter_eval");
+        std::vector<AllowList> out;
+        for (uint32_t b = 0; b < B; b++) {
+            out.emplace_back(count); // (bits above count are clear: the words a list of `count` ids has are the first ones)
+            std::memcpy(out.back().words.data(), flat.data() + (size_t)b * words, out.back().words.size() * 8);
+        }
+        if (cards) *cards = card;
         return out;
     }
     kdb_index *handle() const { return h_; }

@@ -34,6 +34,7 @@ ABI_SYMBOLS = [
     "kdb_filter_eval", "kdb_filter_eval_dev", "kdb_filter_parse", "kdb_search_filtered",
     "kdb_index_set_text", "kdb_index_drop_text", "kdb_index_text_info", "kdb_text_search_batch", "kdb_text_search_batch_dev",
     "kdb_hybrid_search_batch", "kdb_probe_text_plan",
+    "kdb_index_set_relations", "kdb_index_drop_relations", "kdb_index_relations_info", "kdb_graph_filter_eval", "kdb_graph_filter_eval_dev",
 ]
 
 
@@ -77,6 +78,10 @@ class TextView(C.Structure):  # kdb_text_view, 64 bytes
     _fields_ = [("n_tokens", C.c_uint32), ("n_ids", C.c_uint32), ("post_off", C.c_void_p), ("post_doc", C.c_void_p),
                 ("post_tf", C.c_void_p), ("doc_len", C.c_void_p), ("total_docs", C.c_uint64), ("avg_len", C.c_double),
                 ("idf", C.c_void_p)]
+
+
+class RelationsView(C.Structure):  # kdb_relations_view, 32 bytes
+    _fields_ = [("n_nodes", C.c_uint32), ("reserved", C.c_uint32), ("off", C.c_void_p), ("dst", C.c_void_p), ("rel", C.c_void_p)]
 
 
 class BuildParams(C.Structure):
@@ -233,6 +238,11 @@ def load():
     L.kdb_text_search_batch_dev.argtypes = [vp, u32, vp, vp, u32, u32, u32, vp, vp, vp, vp, vp, vp, vp]
     L.kdb_hybrid_search_batch.argtypes = [vp, vp, u32, u32, u32, u32, vp, vp, u32, C.c_double, vp, u32, vp, vp, vp]
     L.kdb_probe_text_plan.argtypes = [vp, u32, u32, u32, u32, C.c_uint64, vp]
+    L.kdb_index_set_relations.argtypes = [vp, C.POINTER(RelationsView)]
+    L.kdb_index_drop_relations.argtypes = [vp]
+    L.kdb_index_relations_info.argtypes = [vp, C.POINTER(u32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    L.kdb_graph_filter_eval.argtypes = [vp, vp, u32, vp, C.c_uint64, vp, vp, u32, vp]
+    L.kdb_graph_filter_eval_dev.argtypes = [vp, vp, u32, vp, C.c_uint64, vp, vp, u32, vp, vp]
     _lib = L
     return L
 

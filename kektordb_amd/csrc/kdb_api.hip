@@ -464,6 +464,7 @@ extern "C" void kdb_index_destroy(kdb_index *idx) {
         if (c) (void)hipFree(c);
     for (kdb_text_slot &t : idx->text)
         if (t.blob) (void)hipFree(t.blob);
+    if (idx->relations.blob) (void)hipFree(idx->relations.blob);
     for (kdb_lane &l : idx->lanes) {
         void *lb[] = {l.d_visited, l.d_scratch, l.d_qbuf, l.d_gentry, l.d_work, l.d_tie, l.d_byid};
         for (void *b : lb)

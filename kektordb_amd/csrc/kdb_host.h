@@ -1,5 +1,5 @@
 // kdb_host.h -- what the files of the host API share (kdb_api.hip, kdb_api_graph.hip, kdb_api_calls.hip, kdb_api_query.hip,
-// kdb_api_filter.hip, kdb_api_merge.hip): host only, included by them alone.  The kernel files include kdb_internal.h.
+// kdb_api_filter.hip, kdb_api_text.hip, kdb_api_relations.hip, kdb_api_merge.hip): host only, included by them alone.  The kernel files include kdb_internal.h.
 #pragma once
 #include "kdb_internal.h"
 #include "kdb_stage.h"

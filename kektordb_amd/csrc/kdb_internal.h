@@ -168,6 +168,20 @@ struct kdb_text_slot { // one field's snapshot: ONE allocation that holds every 
     uint64_t longest = 0;
 };
 
+// Device view of the relation snapshot (graph_filter.hip; passed by value to its kernels): the CSR of kdb_relations_view and its
+// transpose, [0] = out-edges, [1] = in-edges, in HBM
+struct KdbRelDev {
+    const uint64_t *off[2] = {nullptr, nullptr}; // [n_nodes + 2] each
+    const uint32_t *dst[2] = {nullptr, nullptr}; // [n_edges] each: the other end of the edge
+    const uint8_t *rel[2] = {nullptr, nullptr};  // [n_edges] each: its relation code
+    uint32_t n_nodes = 0;
+};
+struct kdb_rel_slot { // ONE allocation that holds every array (blob == null: the slot is empty)
+    void *blob = nullptr;
+    KdbRelDev dev;
+    uint64_t n_edges = 0, bytes = 0;
+};
+
 struct kdb_index {
     kdb_index_desc desc;
     uint32_t ld = 0, deg0 = 0, deg_up = 0, cap = 0;
@@ -212,6 +226,8 @@ struct kdb_index {
     uint32_t col_kind[KDB_MAX_COLUMNS] = {};
     // text snapshots (text.hip, kdb_api_text.hip): independent of cap -- reserve leaves them, compress does not carry them
     kdb_text_slot text[KDB_MAX_TEXT_FIELDS];
+    // the relation snapshot (graph_filter.hip, kdb_api_relations.hip): like the text snapshots, independent of cap
+    kdb_rel_slot relations;
     // scratch that belongs to the index (a call's own scratch: kdb_lane, below)
     void *d_iobuf = nullptr;        // staging of the host-pointer calls that do not fit a slot (big_mu)
     size_t iobuf_bytes = 0;
@@ -437,6 +453,10 @@ int kdb_launch_hybrid_fuse(const KdbTextDev &tx, const uint32_t *d_tokens, const
                            double alpha, uint32_t one_minus_dot, const uint32_t *d_v_ids, const float *d_v_dist, const uint32_t *d_v_cnt,
                            const uint32_t *d_t_ids, const double *d_t_score, const uint32_t *d_t_cnt, const double *d_t_max, uint32_t *d_out_ids,
                            double *d_out_score, uint32_t *d_out_count, hipStream_t s);
+// graph_filter.hip: resolveGraphFilter for B queries (host array, already validated by kdb_graph_validate_queries; staged through
+// the lane's scratch with the frontier bitmaps) into B lists of words_per_list words; every optional pointer may be null
+int kdb_launch_graph_filter(kdb_index *idx, const kdb_graph_query *queries, uint32_t B, uint64_t *d_lists, uint64_t words_per_list, uint32_t *d_card,
+                            const uint64_t *d_and_lists, const uint32_t *and_of_query, hipStream_t s);
 // graph construction (what the three files share: kdb_graph_build.cuh, kdb_walk_lds.h)
 // add.hip: the sequential Add
 int kdb_add_graph(kdb_index *idx, uint32_t first_id, uint32_t n, const uint8_t *levels, uint32_t ef_construction, kdb_add_stats *out);

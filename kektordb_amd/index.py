@@ -45,6 +45,11 @@ ROUTE_WALK, ROUTE_SCAN, ROUTE_EMPTY = 0, 1, 2  # out_route of kdb_search_filtere
 # BM25 text search (kektor_hip.h, "BM25 text search and hybrid fusion")
 MAX_TEXT_FIELDS, TEXT_MAX_TOKENS, TEXT_MAX_K = 4, 32, 1024
 NO_TOKEN = 0xFFFFFFFF  # KDB_NO_TOKEN: a query word the dictionary does not hold
+# graph filters (kektor_hip.h, "graph filters on the device")
+GRAPH_MAX_RELATIONS, GRAPH_MAX_QUERIES = 64, 4096
+GDIR_OUT, GDIR_IN, GDIR_BOTH, GDIR_NONE = 0, 1, 2, 3
+GRAPH_DIRECTIONS = {"out": GDIR_OUT, "": GDIR_OUT, "in": GDIR_IN, "both": GDIR_BOTH}  # graph.go:206-233; any other string: GDIR_NONE
+GRAPH_QUERY_DTYPE = np.dtype([("root", "<u4"), ("max_depth", "<i4"), ("direction", "<u4"), ("reserved", "<u4"), ("rel_mask", "<u8")])  # kdb_graph_query
 # kdb_consensus: CalculateConsensus's score, variance and maxVar, len(nodes), len(activeNodes)
 CONSENSUS_DTYPE = np.dtype([("score", "<f8"), ("variance", "<f8"), ("max_pair", "<f8"), ("n_found", "<u4"), ("n_active", "<u4")])
 
@@ -879,6 +884,50 @@ class HipIndex:
                                              self._flags(False) | int(flags), _ptr(ids), _ptr(score), _ptr(cnt)), "kdb_hybrid_search_batch")
         return ids, score, cnt
 
+    # ---- graph filters on the device (graph_filter.hip) -----------------------------------------------
+    def set_relations(self, graph: "RelationGraph"):
+        """Upload the snapshot of a RelationGraph (kdb_index_set_relations); replaces the one before it."""
+        self._live()
+        check(self.L.kdb_index_set_relations(self.h, C.byref(graph.view())), "kdb_index_set_relations")
+
+    def drop_relations(self):
+        self._live()
+        check(self.L.kdb_index_drop_relations(self.h), "kdb_index_drop_relations")
+
+    def relations_info(self):
+        """(n_nodes, n_edges, bytes) of the relation snapshot; zeros when there is none"""
+        self._live()
+        nn, ne, nbytes = C.c_uint32(), C.c_uint64(), C.c_uint64()
+        check(self.L.kdb_index_relations_info(self.h, C.byref(nn), C.byref(ne), C.byref(nbytes)), "kdb_index_relations_info")
+        return int(nn.value), int(ne.value), int(nbytes.value)
+
+    def graph_filter(self, queries, words_per_list: int = 0, want_lists: bool = True, and_lists=None, and_of_query=None):
+        """resolveGraphFilter for a batch (kdb_graph_filter_eval).  queries: a GRAPH_QUERY_DTYPE array (RelationGraph.query makes its
+        records).  and_lists [n, words] uint64 with and_of_query [B] (NO_FILTER: none): the list each result is ANDed with.
+        Returns (lists [B, words] uint64 or None, card [B])."""
+        self._live()
+        q = np.ascontiguousarray(queries, dtype=GRAPH_QUERY_DTYPE).ravel()
+        words = int(words_per_list) if words_per_list else (max(self.graph_info()[0], self.relations_info()[0]) >> 6) + 1
+        lists = np.zeros((q.size, words), dtype=np.uint64) if want_lists else None
+        card = np.zeros(q.size, dtype=np.uint32)
+        al = None if and_lists is None else np.ascontiguousarray(and_lists, dtype=np.uint64)
+        ao = None if and_of_query is None else np.ascontiguousarray(np.asarray(and_of_query, dtype=np.int64) & 0xFFFFFFFF, dtype=np.uint32)
+        check(self.L.kdb_graph_filter_eval(self.h, _ptr(q), q.size, _ptr(lists), words, _ptr(card), _ptr(al), 0 if al is None else al.shape[0], _ptr(ao)),
+              "kdb_graph_filter_eval")
+        return lists, card
+
+    def graph_filter_dev(self, queries, d_lists, d_card=None, d_and_lists=None, and_of_query=None, stream=None):
+        """the same into device tensors: d_lists [B, words] int64 / uint64, d_card [B] int32 or None, d_and_lists [n, words] or None
+        (and_of_query stays a host array); asynchronous on `stream`"""
+        self._live()
+        _ready(stream)
+        q = np.ascontiguousarray(queries, dtype=GRAPH_QUERY_DTYPE).ravel()
+        assert int(d_lists.shape[0]) == q.size
+        ao = None if and_of_query is None else np.ascontiguousarray(np.asarray(and_of_query, dtype=np.int64) & 0xFFFFFFFF, dtype=np.uint32)
+        check(self.L.kdb_graph_filter_eval_dev(self.h, _ptr(q), q.size, _tptr(d_lists), int(d_lists.shape[1]), _tptr(d_card), _tptr(d_and_lists),
+                                               0 if d_and_lists is None else int(d_and_lists.shape[0]), _ptr(ao), C.c_void_p(stream) if stream else None),
+              "kdb_graph_filter_eval_dev")
+
     # ---- the reference's per-query API --------------------------------------------------------------
     def score(self, raw: float) -> float:
         """The reference's f64 epilogue: float64(sum) (distance_go.go:67) / 1.0-float64(dot) (:127)."""
@@ -990,6 +1039,45 @@ class TextIndex:
         self._idf = None if idf is None else np.ascontiguousarray(idf, dtype=np.float64)  # (kept alive with the arrays)
         return _lib.TextView(len(self.dictionary), self.n_ids, _ptr(self.post_off), _ptr(self.post_doc), _ptr(self.post_tf), _ptr(self.doc_len),
                              self.total_docs, self.avg_len, _ptr(self._idf))
+
+
+class RelationGraph:
+    """The snapshot kdb_index_set_relations takes, built from the ACTIVE out-edges as (source, relation name, target) triples over
+    graph node numbers: node g <= the index's capacity IS internal id g, higher numbers are ids the index does not hold (the caller
+    numbers them).  `relations` maps a relation name to its code, in first-seen order (at most 64).  Edges keep their order inside
+    a node; duplicates and self loops stay."""
+
+    def __init__(self, edges, n_nodes: int = 0, relations: Optional[dict] = None):
+        self.relations = dict(relations or {})
+        src = np.array([e[0] for e in edges], dtype=np.uint32)
+        dst = np.array([e[2] for e in edges], dtype=np.uint32)
+        rel = np.array([self.relations.setdefault(e[1], len(self.relations)) for e in edges], dtype=np.uint8)
+        if len(self.relations) > GRAPH_MAX_RELATIONS:
+            raise ValueError("more than 64 relation names")
+        self.n_nodes = max(int(n_nodes), int(src.max()) if src.size else 0, int(dst.max()) if dst.size else 0)
+        order = np.argsort(src, kind="stable")
+        self.off = np.zeros(self.n_nodes + 2, dtype=np.uint64)
+        self.off[1:] = np.cumsum(np.bincount(src, minlength=self.n_nodes + 1), dtype=np.uint64)
+        self.dst, self.rel = np.ascontiguousarray(dst[order]), np.ascontiguousarray(rel[order])
+
+    @classmethod
+    def from_arrays(cls, off, dst, rel, relations: Optional[dict] = None) -> "RelationGraph":
+        """a snapshot already in arrays: off [n_nodes + 2] by node, dst and rel by edge (relation codes are the dictionary)"""
+        g = cls([])
+        g.off, g.dst, g.rel = (np.ascontiguousarray(a, dtype=d) for a, d in ((off, np.uint64), (dst, np.uint32), (rel, np.uint8)))
+        g.n_nodes, g.relations = g.off.size - 2, dict(relations or {})
+        return g
+
+    def rel_mask(self, names) -> int:
+        """the 64-bit mask of a query's relation names; a name no edge carries contributes nothing"""
+        return sum({1 << self.relations[n] for n in names if n in self.relations})
+
+    def query(self, root: int, names, direction: str = "out", max_depth: int = 1):
+        """one kdb_graph_query record from a GraphQuery's fields (root: its graph node number, 0 = unknown)"""
+        return (int(root), int(max_depth), GRAPH_DIRECTIONS.get(direction, GDIR_NONE), 0, self.rel_mask(names))
+
+    def view(self) -> "_lib.RelationsView":
+        return _lib.RelationsView(self.n_nodes, 0, _ptr(self.off), _ptr(self.dst), _ptr(self.rel))
 
 
 def merge_topk(metric: int, ids, dist, count, k: int, id_base=None, precision: int = F32, out=None):

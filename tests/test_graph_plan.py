@@ -1,0 +1,16 @@
+"""The plan of the graph-filter kernels without a GPU (kdb_graph_plan.h): a stand-alone C++ program built with ASan and UBSan."""
+import os
+import subprocess
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def test_graph_plan_under_address_and_ub_sanitizers(tmp_path):
+    exe = str(tmp_path / "graph_plan_test")
+    cmd = ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-Wall", "-Werror",
+           "-I", os.path.join(ROOT, "kektordb_amd", "csrc"), os.path.join(ROOT, "tests", "cpp", "graph_plan_test.cpp"), "-o", exe]
+    p = subprocess.run(cmd, capture_output=True, text=True)
+    assert p.returncode == 0, p.stderr
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
+    assert r.stdout.strip() == "ok" and not r.stderr, (r.stdout, r.stderr[-4000:])
