@@ -696,7 +696,7 @@ KDB_API int kdb_hybrid_search_batch(kdb_index *idx, const float *queries, uint32
  * A call whose frontiers would take more than 256 MB runs as consecutive chunks of queries on the same stream.  Environment, read
  * at every call: KDB_GRAPH_PARTS = N forces the workgroups per query (at most one per frontier word, at most 512);
  * KDB_GRAPH_SCRATCH_MAX = bytes replaces the 256 MB.
- * Out of scope: a one-call request (kdb_search_filtered with a graph query); VExtractSubgraph / VTraverse / pathfinding; atTime
+ * Out of scope: a one-call request (kdb_search_filtered with a graph query); VTraverse / pathfinding; atTime
  * snapshots; incremental edge updates; a single-launch LDS-queue variant for tiny frontiers. */
 #define KDB_GRAPH_MAX_RELATIONS 64u
 #define KDB_GRAPH_MAX_QUERIES 4096u
@@ -717,6 +717,43 @@ KDB_API int kdb_graph_filter_eval_dev(kdb_index *idx, const kdb_graph_query *que
                                       void *stream);
 KDB_API int kdb_graph_filter_eval(kdb_index *idx, const kdb_graph_query *queries, uint32_t B, uint64_t *out_lists, uint64_t words_per_list,
                                   uint32_t *out_card, const uint64_t *and_lists, uint32_t n_and_lists, const uint32_t *and_of_query);
+
+/* ---- subgraph extraction on the device (subgraph.hip; geometry and validation in kdb_subgraph_plan.h) ----------------------------
+ * Engine.VExtractSubgraph (pkg/engine/graph.go:296-386) over the relation snapshot above, for B queries.  Restated, not improved:
+ * maxDepth <= 0 becomes 1, > 5 becomes 5; out- AND in-edges of every relation in rel_mask are followed (an empty mask follows
+ * nothing); only the active edges of the snapshot (atTime == 0).  The root is in the node set ungated; root 0 gives an empty
+ * result; a root above n_nodes is KDB_ERR_INVALID.  A node first reached at depth d < maxDepth is expanded: every CSR entry of it,
+ * out and in, whose relation is in the mask and whose far end t passes the gate contributes ONE edge record -- also when t was
+ * visited before (the reference appends to `edges` before it looks at `visited`), also when t is the root -- and puts t into the
+ * node set at depth d + 1 unless it is there already.
+ * THE GATE.  flags bit 0 clear (len(guideQuery) == 0): everything passes.  Set: dist(t) <= threshold as float64, a NaN fails.
+ * dist(t) = 999999.0 for a node above count, a deleted id or an id never written (computeDistance, ops.go:1774-1781); else
+ * hnsw.Index.ComputeDistanceToVector (hnsw_index.go:3381-3468) of guides[b] and row t: float32 cosine 1.0 - (double)dot with the
+ * guide normalised, float32 / float16 squared L2 as (double)sum with the float16 guide rounded to half, int8 the float64 cosine
+ * distance of :3436-3464 with the guide quantised WITHOUT normalising and its norm rounded to float32.  dot and sum are the bits
+ * kdb_search_batch reports for the pair (same accumulation order).  A guide with a component that is not finite: nothing to be
+ * exact with -- no live node passes.
+ * NOT carried over: the per-query FIFO order.  The result is a node SET and an edge MULTISET.
+ *
+ * queries: a HOST array in both forms.  guides: [B][dim] float32 (device memory in the _dev form), NULL allowed when no query is
+ * guided; rows of unguided queries are not read (guided rows are copied and prepared run by run).  Outputs: nodes = B bitmaps over graph nodes 0..n_nodes,
+ * words_per_list >= (n_nodes>>6)+1 words each, EVERY word written, bit 0 and the bits above n_nodes clear (nodes above count stay
+ * set: they are part of the subgraph); n_nodes[B]; n_edges[B] = the edges found, even beyond edge_cap; edges[B][edge_cap]: records
+ * past the cap are dropped (the slots then hold an unspecified subset), otherwise the multiset in an unspecified order; edge_cap 0
+ * or NULL edges: counts only.  kdb_subgraph_edge.info = relation code | direction << 8 (0: src -> dst is an out-edge of the
+ * expanded node src, 1: an in-edge of the expanded node dst) | level << 16 (the depth of the expanded node).
+ * The _dev form is asynchronous on `stream` and takes a scratch lane of it; the host form takes turns on the staging buffer like
+ * kdb_graph_filter_eval.  Chunked by scratch bytes like the graph filter; KDB_GRAPH_PARTS and KDB_GRAPH_SCRATCH_MAX apply.
+ * KDB_ERR_UNSUPPORTED, nothing queued, for a guided call on an index whose prepared guide exceeds 48 KB (more than 12288 float32
+ * columns): the gate holds it in LDS.
+ * Out of scope: atTime snapshots; node metadata (the shim reads it from its own store); a quantizer that is not ready. */
+typedef struct { uint32_t root; int32_t max_depth; uint32_t flags; uint32_t reserved; uint64_t rel_mask; double threshold; } kdb_subgraph_query; /* 32 bytes */
+typedef struct { uint32_t src, dst, info; } kdb_subgraph_edge; /* 12 bytes */
+KDB_API int kdb_subgraph_extract_dev(kdb_index *idx, const kdb_subgraph_query *queries, uint32_t B, const float *d_guides, uint64_t *d_nodes,
+                                     uint64_t words_per_list, uint32_t *d_n_nodes, uint32_t *d_n_edges, kdb_subgraph_edge *d_edges, uint32_t edge_cap,
+                                     void *stream);
+KDB_API int kdb_subgraph_extract(kdb_index *idx, const kdb_subgraph_query *queries, uint32_t B, const float *guides, uint64_t *out_nodes,
+                                 uint64_t words_per_list, uint32_t *out_n_nodes, uint32_t *out_n_edges, kdb_subgraph_edge *out_edges, uint32_t edge_cap);
 
 /* B queries x C candidate ids each (ids[B][C], id 0 = skip -> +inf): raw accumulates out[B][C].   */
 KDB_API int kdb_distance_batch(kdb_index *idx, const float *queries, uint32_t B, const uint32_t *ids, uint32_t C,

@@ -568,6 +568,39 @@ class Index {
         if (cards) *cards = card;
         return out;
     }
+    // Engine.VExtractSubgraph for several requests in one call (kdb_subgraph_extract): per request the graph nodes of its subgraph,
+    // ascending, and its edge records (a multiset, in no particular order).  guides: null (no request is guided) or
+    // queries.size() x Dim() floats.  A second call with a larger cap follows when a request found more edges than edgeCap.
+    struct Subgraph {
+        std::vector<uint32_t> nodes;
+        std::vector<kdb_subgraph_edge> edges;
+    };
+    std::vector<Subgraph> ExtractSubgraph(const std::vector<kdb_subgraph_query> &queries, const float *guides = nullptr, uint32_t edgeCap = 4096) const {
+        uint32_t nodes = 0;
+        RelationsInfo(&nodes, nullptr, nullptr);
+        const uint32_t B = (uint32_t)queries.size();
+        const uint64_t words = ((uint64_t)nodes >> 6) + 1;
+        std::vector<uint64_t> bits((size_t)B * words);
+        std::vector<uint32_t> nNodes(B), nEdges(B);
+        std::vector<kdb_subgraph_edge> flat;
+        for (uint32_t cap = edgeCap ? edgeCap : 1u;;) {
+            flat.assign((size_t)B * cap, kdb_subgraph_edge{0u, 0u, 0u});
+            check(kdb_subgraph_extract(h_, queries.data(), B, guides, bits.data(), words, nNodes.data(), nEdges.data(), flat.data(), cap), "subgraph_extract");
+            const uint32_t most = B ? *std::max_element(nEdges.begin(), nEdges.end()) : 0u;
+            if (most <= cap) {
+                edgeCap = cap;
+                break;
+            }
+            cap = most;
+        }
+        std::vector<Subgraph> out(B);
+        for (uint32_t b = 0; b < B; b++) {
+            for (uint64_t w = 0; w < words; w++)
+                for (uint64_t x = bits[(size_t)b * words + w]; x; x &= x - 1) out[b].nodes.push_back((uint32_t)(w * 64 + (uint64_t)__builtin_ctzll(x)));
+            out[b].edges.assign(flat.begin() + (size_t)b * edgeCap, flat.begin() + (size_t)b * edgeCap + nEdges[b]);
+        }
+        return out;
+    }
     kdb_index *handle() const { return h_; }
     // concurrent kdb_search_batch calls of a few queries share launches inside the library (kektor_hip.h, "Conventions"): a
     // batcher in front of this index passes unfiltered one-query calls through

@@ -35,6 +35,7 @@ ABI_SYMBOLS = [
     "kdb_index_set_text", "kdb_index_drop_text", "kdb_index_text_info", "kdb_text_search_batch", "kdb_text_search_batch_dev",
     "kdb_hybrid_search_batch", "kdb_probe_text_plan",
     "kdb_index_set_relations", "kdb_index_drop_relations", "kdb_index_relations_info", "kdb_graph_filter_eval", "kdb_graph_filter_eval_dev",
+    "kdb_subgraph_extract", "kdb_subgraph_extract_dev",
 ]
 
 
@@ -243,6 +244,8 @@ def load():
     L.kdb_index_relations_info.argtypes = [vp, C.POINTER(u32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.kdb_graph_filter_eval.argtypes = [vp, vp, u32, vp, C.c_uint64, vp, vp, u32, vp]
     L.kdb_graph_filter_eval_dev.argtypes = [vp, vp, u32, vp, C.c_uint64, vp, vp, u32, vp, vp]
+    L.kdb_subgraph_extract.argtypes = [vp, vp, u32, vp, vp, C.c_uint64, vp, vp, vp, u32]
+    L.kdb_subgraph_extract_dev.argtypes = [vp, vp, u32, vp, vp, C.c_uint64, vp, vp, vp, u32, vp]
     _lib = L
     return L
 

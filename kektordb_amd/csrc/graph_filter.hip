@@ -170,13 +170,6 @@ graph_finish_kernel(const KdbGraphStaged *__restrict__ queries, unsigned long lo
     if (card && (threadIdx.x & (KDB_GRAPH_WAVE - 1u)) == 0u && n) atomicAdd(card + b, n);
 }
 
-// an environment override read per call (tests toggle it inside one process); unset or not a positive number: `unset`
-long long graph_env(const char *name, long long unset) {
-    const char *e = getenv(name);
-    const long long v = e ? atoll(e) : 0;
-    return v > 0 ? v : unset;
-}
-
 } // namespace
 
 int kdb_launch_graph_filter(kdb_index *idx, const kdb_graph_query *queries, uint32_t B, uint64_t *d_lists, uint64_t words_per_list, uint32_t *d_card,
@@ -185,8 +178,8 @@ int kdb_launch_graph_filter(kdb_index *idx, const kdb_graph_query *queries, uint
     const uint64_t wpn = kdb_graph_wpn(g.n_nodes), wpl = words_per_list;
     std::vector<KdbGraphStaged> staged(B);
     for (uint32_t b = 0; b < B; b++) staged[b] = kdb_graph_stage_query(queries[b], d_and_lists && and_of_query ? and_of_query[b] : KDB_NO_FILTER);
-    const uint32_t Bc = kdb_graph_chunk_queries(B, wpn, (uint64_t)graph_env("KDB_GRAPH_SCRATCH_MAX", (long long)KDB_GRAPH_SCRATCH_MAX));
-    const int32_t forced = (int32_t)std::min<long long>(graph_env("KDB_GRAPH_PARTS", 0), KDB_GRAPH_MAX_PARTS);
+    const uint32_t Bc = kdb_graph_chunk_queries(B, wpn, (uint64_t)kdb_graph_env("KDB_GRAPH_SCRATCH_MAX", (long long)KDB_GRAPH_SCRATCH_MAX));
+    const int32_t forced = (int32_t)std::min<long long>(kdb_graph_env("KDB_GRAPH_PARTS", 0), KDB_GRAPH_MAX_PARTS);
     const KdbGraphScratch L = kdb_graph_scratch(B, Bc, wpn);
     const int rc = kdb_ensure_scratch(idx, (size_t)L.total);
     if (rc) return rc;

@@ -1,7 +1,7 @@
-// kdb_api_relations.hip -- host side of the C ABI (include/kektor_hip.h): the relation snapshot and graph filters.
+// kdb_api_relations.hip -- host side of the C ABI (include/kektor_hip.h): the relation snapshot, graph filters and subgraph extraction.
 #include "kdb_internal.h"
 #include "kdb_host.h"
-#include "kdb_graph_plan.h"
+#include "kdb_subgraph_plan.h"
 #include <algorithm>
 #include <vector>
 
@@ -167,5 +167,78 @@ extern "C" int kdb_graph_filter_eval(kdb_index *idx, const kdb_graph_query *quer
         [&](unsigned char *d, hipStream_t s) {
             return kdb_launch_graph_filter(idx, queries, B, r_lists.at<uint64_t>(d), words_per_list, r_card.at<uint32_t>(d), r_and.at<uint64_t>(d),
                                            and_of_query, s);
+        });
+}
+
+// ---------------------------------------------------------------------------------------------
+// VExtractSubgraph for B queries (subgraph.hip).  The queries are a host array in both forms, staged by the launcher with the prepared
+// guides and the bitmaps in the scratch of the call's lane.
+// ---------------------------------------------------------------------------------------------
+// n_nodes = 0xffffffff: what needs no index; under idx->mu with the snapshot's n_nodes: the roots and the least words too
+static int subgraph_check(const kdb_subgraph_query *queries, uint32_t B, uint32_t n_nodes, const void *guides, uint64_t words_per_list) {
+    uint32_t bad = 0;
+    const int vrc = kdb_subgraph_validate(queries, B, n_nodes, guides != nullptr, words_per_list, &bad);
+    if (vrc) {
+        kdb_set_error("subgraph_extract: %s (query %u)", kdb_subgraph_strerror(vrc), bad);
+        return KDB_ERR_INVALID;
+    }
+    return KDB_OK;
+}
+static int subgraph_call_check(const kdb_index *idx, const kdb_subgraph_query *queries, uint32_t B, const void *guides, uint64_t words_per_list) {
+    if (!idx->relations.blob) {
+        kdb_set_error("subgraph_extract: the index holds no relation snapshot (kdb_index_set_relations)");
+        return KDB_ERR_INVALID;
+    }
+    return subgraph_check(queries, B, idx->relations.dev.n_nodes, guides, words_per_list);
+}
+
+extern "C" int kdb_subgraph_extract_dev(kdb_index *idx, const kdb_subgraph_query *queries, uint32_t B, const float *d_guides, uint64_t *d_nodes,
+                                        uint64_t words_per_list, uint32_t *d_n_nodes, uint32_t *d_n_edges, kdb_subgraph_edge *d_edges, uint32_t edge_cap,
+                                        void *stream) {
+    int rc = subgraph_check(queries, B, 0xffffffffu, d_guides, words_per_list);
+    if (rc) return rc;
+    if (!d_nodes || !d_n_nodes || !d_n_edges) {
+        kdb_set_error("subgraph_extract: null d_nodes, d_n_nodes or d_n_edges");
+        return KDB_ERR_INVALID;
+    }
+    KDB_CHECK_IDX(idx);
+    DevCall call(idx, stream);
+    if (call.rc) return call.rc;
+    rc = subgraph_call_check(idx, queries, B, d_guides, words_per_list);
+    if (rc) return rc;
+    return kdb_launch_subgraph(idx, queries, B, d_guides, d_nodes, words_per_list, d_n_nodes, d_n_edges, d_edges, edge_cap, call.s);
+}
+
+extern "C" int kdb_subgraph_extract(kdb_index *idx, const kdb_subgraph_query *queries, uint32_t B, const float *guides, uint64_t *out_nodes,
+                                    uint64_t words_per_list, uint32_t *out_n_nodes, uint32_t *out_n_edges, kdb_subgraph_edge *out_edges, uint32_t edge_cap) {
+    int rc = subgraph_check(queries, B, 0xffffffffu, guides, words_per_list);
+    if (rc) return rc;
+    if (!out_nodes && !out_n_nodes && !out_n_edges && !(out_edges && edge_cap)) {
+        kdb_set_error("subgraph_extract: every output is null");
+        return KDB_ERR_INVALID;
+    }
+    KDB_CHECK_IDX(idx);
+    KDB_HIP(hipSetDevice(idx->device));
+    KdbRegion r_guides, r_nodes, r_nn, r_ne, r_edges;
+    KdbTurnOpt opt;
+    opt.launch_first = true; // (queries and guides are copied by the launcher and by run() below: the stage copies nothing in)
+    return kdb_turn_call(
+        idx, opt,
+        [&](KdbStage &st) { // the kernels write bitmaps and counts whatever the caller asked for: an output nobody wants stays on the device
+            if (const int crc = subgraph_call_check(idx, queries, B, guides, words_per_list)) return crc;
+            const size_t lb = (size_t)words_per_list * 8;
+            r_guides = st.dev(guides ? (size_t)B * idx->desc.dim * 4 : 0); // filled in run(): the rows of guided queries only
+            r_nodes = out_nodes ? st.out(out_nodes, (size_t)B * lb) : st.dev((size_t)B * lb);
+            r_nn = out_n_nodes ? st.out(out_n_nodes, (size_t)B * 4) : st.dev((size_t)B * 4);
+            r_ne = out_n_edges ? st.out(out_n_edges, (size_t)B * 4) : st.dev((size_t)B * 4);
+            r_edges = st.out(out_edges, (size_t)B * edge_cap * sizeof(kdb_subgraph_edge));
+            return (int)KDB_OK;
+        },
+        [&](unsigned char *d, hipStream_t s) -> int {
+            const size_t row = (size_t)idx->desc.dim * 4; // (pageable memory: consumed before hipMemcpyAsync returns)
+            for (uint32_t b0 = 0, b1 = 0; guides && kdb_subgraph_guided_run(queries, B, b1, &b0, &b1);)
+                KDB_HIP(hipMemcpyAsync(r_guides.at<unsigned char>(d) + b0 * row, guides + (size_t)b0 * idx->desc.dim, (b1 - b0) * row, hipMemcpyHostToDevice, s));
+            return kdb_launch_subgraph(idx, queries, B, r_guides.at<float>(d), r_nodes.at<uint64_t>(d), words_per_list, r_nn.at<uint32_t>(d),
+                                       r_ne.at<uint32_t>(d), r_edges.at<kdb_subgraph_edge>(d), edge_cap, s);
         });
 }

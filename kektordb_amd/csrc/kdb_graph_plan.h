@@ -14,6 +14,7 @@
 #define KDB_GRAPH_PLAN_H
 #include <stddef.h>
 #include <stdint.h>
+#include <stdlib.h>
 #include "../../include/kektor_hip.h"
 
 #if defined(__HIPCC__)
@@ -70,6 +71,13 @@ KDB_GRAPH_HD constexpr uint64_t kdb_graph_live_mask(uint64_t w, uint32_t count) 
     const uint64_t last = (uint64_t)count >> 6;
     const uint64_t m = w > last ? 0ull : w < last ? ~0ull : (2ull << (count & 63u)) - 1ull; // (2 << 63 wraps to 0: all ones)
     return w == 0u ? m & ~1ull : m;
+}
+
+// an environment override read per call (tests toggle it inside one process); unset or not a positive number: `unset`
+inline long long kdb_graph_env(const char *name, long long unset) {
+    const char *e = getenv(name);
+    const long long v = e ? atoll(e) : 0;
+    return v > 0 ? v : unset;
 }
 
 // ---- parts: the workgroups that share one query's sweep ---------------------------------------------------------------------------

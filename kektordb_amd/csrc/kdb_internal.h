@@ -457,6 +457,10 @@ int kdb_launch_hybrid_fuse(const KdbTextDev &tx, const uint32_t *d_tokens, const
 // the lane's scratch with the frontier bitmaps) into B lists of words_per_list words; every optional pointer may be null
 int kdb_launch_graph_filter(kdb_index *idx, const kdb_graph_query *queries, uint32_t B, uint64_t *d_lists, uint64_t words_per_list, uint32_t *d_card,
                             const uint64_t *d_and_lists, const uint32_t *and_of_query, hipStream_t s);
+// subgraph.hip: VExtractSubgraph for B queries (host array, already validated by kdb_subgraph_validate; staged through the lane's
+// scratch with the prepared guides and the five bitmaps per query); d_guides: [B][dim] float32 or null; d_edges may be null
+int kdb_launch_subgraph(kdb_index *idx, const kdb_subgraph_query *queries, uint32_t B, const float *d_guides, uint64_t *d_nodes, uint64_t words_per_list,
+                        uint32_t *d_n_nodes, uint32_t *d_n_edges, kdb_subgraph_edge *d_edges, uint32_t edge_cap, hipStream_t s);
 // graph construction (what the three files share: kdb_graph_build.cuh, kdb_walk_lds.h)
 // add.hip: the sequential Add
 int kdb_add_graph(kdb_index *idx, uint32_t first_id, uint32_t n, const uint8_t *levels, uint32_t ef_construction, kdb_add_stats *out);

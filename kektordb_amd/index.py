@@ -50,6 +50,9 @@ GRAPH_MAX_RELATIONS, GRAPH_MAX_QUERIES = 64, 4096
 GDIR_OUT, GDIR_IN, GDIR_BOTH, GDIR_NONE = 0, 1, 2, 3
 GRAPH_DIRECTIONS = {"out": GDIR_OUT, "": GDIR_OUT, "in": GDIR_IN, "both": GDIR_BOTH}  # graph.go:206-233; any other string: GDIR_NONE
 GRAPH_QUERY_DTYPE = np.dtype([("root", "<u4"), ("max_depth", "<i4"), ("direction", "<u4"), ("reserved", "<u4"), ("rel_mask", "<u8")])  # kdb_graph_query
+SUBGRAPH_QUERY_DTYPE = np.dtype([("root", "<u4"), ("max_depth", "<i4"), ("flags", "<u4"), ("reserved", "<u4"), ("rel_mask", "<u8"),
+                                 ("threshold", "<f8")])  # kdb_subgraph_query; flags bit 0: guided
+SUBGRAPH_EDGE_DTYPE = np.dtype([("src", "<u4"), ("dst", "<u4"), ("info", "<u4")])  # kdb_subgraph_edge; info = rel | dir << 8 | level << 16
 # kdb_consensus: CalculateConsensus's score, variance and maxVar, len(nodes), len(activeNodes)
 CONSENSUS_DTYPE = np.dtype([("score", "<f8"), ("variance", "<f8"), ("max_pair", "<f8"), ("n_found", "<u4"), ("n_active", "<u4")])
 
@@ -928,6 +931,33 @@ class HipIndex:
                                                0 if d_and_lists is None else int(d_and_lists.shape[0]), _ptr(ao), C.c_void_p(stream) if stream else None),
               "kdb_graph_filter_eval_dev")
 
+    # ---- subgraph extraction on the device (subgraph.hip) -------------------------------------------
+    def extract_subgraph(self, queries, guides=None, edge_cap: int = 0, words_per_list: int = 0):
+        """Engine.VExtractSubgraph for a batch (kdb_subgraph_extract).  queries: a SUBGRAPH_QUERY_DTYPE array (RelationGraph.subgraph_query
+        makes its records); guides [B, dim] float32, needed when a query is guided.  Returns (nodes [B, words] uint64 bitmaps over
+        graph nodes, n_nodes [B], n_edges [B] -- the edges found, even beyond edge_cap --, edges [B, edge_cap] SUBGRAPH_EDGE_DTYPE)."""
+        self._live()
+        q = np.ascontiguousarray(queries, dtype=SUBGRAPH_QUERY_DTYPE).ravel()
+        gd = None if guides is None else np.ascontiguousarray(guides, dtype=np.float32).reshape(q.size, self.dim)
+        words = int(words_per_list) if words_per_list else (self.relations_info()[0] >> 6) + 1
+        nodes = np.zeros((q.size, words), dtype=np.uint64)
+        nn, ne = np.zeros(q.size, dtype=np.uint32), np.zeros(q.size, dtype=np.uint32)
+        edges = np.zeros((q.size, int(edge_cap)), dtype=SUBGRAPH_EDGE_DTYPE)
+        check(self.L.kdb_subgraph_extract(self.h, _ptr(q), q.size, _ptr(gd), _ptr(nodes), words, _ptr(nn), _ptr(ne), _ptr(edges) if edge_cap else None,
+                                          int(edge_cap)), "kdb_subgraph_extract")
+        return nodes, nn, ne, edges
+
+    def extract_subgraph_dev(self, queries, d_nodes, d_n_nodes, d_n_edges, d_edges=None, d_guides=None, stream=None):
+        """the same into device tensors: d_nodes [B, words] int64 / uint64, d_n_nodes and d_n_edges [B] int32, d_edges [B, edge_cap, 3]
+        int32 or None (counts only), d_guides [B, dim] float32 or None; asynchronous on `stream`"""
+        self._live()
+        _ready(stream)
+        q = np.ascontiguousarray(queries, dtype=SUBGRAPH_QUERY_DTYPE).ravel()
+        assert int(d_nodes.shape[0]) == q.size and (d_guides is None or tuple(d_guides.shape) == (q.size, self.dim))
+        check(self.L.kdb_subgraph_extract_dev(self.h, _ptr(q), q.size, _tptr(d_guides), _tptr(d_nodes), int(d_nodes.shape[1]), _tptr(d_n_nodes),
+                                              _tptr(d_n_edges), _tptr(d_edges), 0 if d_edges is None else int(d_edges.shape[1]),
+                                              C.c_void_p(stream) if stream else None), "kdb_subgraph_extract_dev")
+
     # ---- the reference's per-query API --------------------------------------------------------------
     def score(self, raw: float) -> float:
         """The reference's f64 epilogue: float64(sum) (distance_go.go:67) / 1.0-float64(dot) (:127)."""
@@ -1075,6 +1105,10 @@ class RelationGraph:
     def query(self, root: int, names, direction: str = "out", max_depth: int = 1):
         """one kdb_graph_query record from a GraphQuery's fields (root: its graph node number, 0 = unknown)"""
         return (int(root), int(max_depth), GRAPH_DIRECTIONS.get(direction, GDIR_NONE), 0, self.rel_mask(names))
+
+    def subgraph_query(self, root: int, names, max_depth: int = 1, threshold: Optional[float] = None):
+        """one kdb_subgraph_query record (root: its graph node number, 0 = unknown); threshold None: no guide, nothing is gated"""
+        return (int(root), int(max_depth), 0 if threshold is None else 1, 0, self.rel_mask(names), 0.0 if threshold is None else float(threshold))
 
     def view(self) -> "_lib.RelationsView":
         return _lib.RelationsView(self.n_nodes, 0, _ptr(self.off), _ptr(self.dst), _ptr(self.rel))
