@@ -11,14 +11,15 @@
 //                           take the batch 4 * R rows at a time against the guide in LDS, passes go into P
 //   subgraph_finish_kernel  one lane per word of V: bit 0 and the bits above n_nodes cleared, the node count
 //
-// Semantics, chunking, validation and the scratch layout are kdb_subgraph_plan.h's.  The sweep is graph_filter.hip's -- words
-// coalesced, light nodes lane-privately, heavier ones through the hub queue in LDS -- restated here with what extraction adds:
-// both directions always, the source of a hub (an edge record names it), and wave-converged visits, because EXPAND reserves edge
-// slots with ONE atomic per wave and trip.  The result is a node SET and an edge MULTISET: V and P only ever gain bits, a node
-// enters the next frontier exactly once, an edge record is written by the one lane that visits its CSR entry, so nothing depends
-// on the order in which the atomics land.
+// Semantics, chunking, validation and the scratch layout are kdb_subgraph_plan.h's.  The sweep of a bitmap -- the rounds, the queue
+// in LDS, the barriers -- and the expansion of a frontier over the CSR are kdb_graph_sweep.cuh's, shared with graph_filter.hip.
+// Extraction's own: both directions always; sub_visit, which uses that the sweep's visits are wave-converged (EXPAND reserves edge
+// slots with ONE atomic per wave and trip) and the source the hub queue keeps (an edge record names it); the gate's policy.  The
+// result is a node SET and an edge MULTISET: V and P only ever gain bits, a node enters the next frontier exactly once, an edge
+// record is written by the one lane that visits its CSR entry, so nothing depends on the order in which the atomics land.
 #include "kdb_search_core.cuh" // kdb_trip_rows: the rows-per-trip table of compute_dists; kdb_device.cuh: the accumulate steps
 #include "kdb_decode.cuh"      // kdb_row_found
+#include "kdb_graph_sweep.cuh"
 #include "kdb_subgraph_plan.h"
 #include <algorithm>
 #include <vector>
@@ -43,8 +44,7 @@ subgraph_init_kernel(const KdbSubStaged *__restrict__ queries, unsigned long lon
                      unsigned long long *__restrict__ bc, uint64_t wpn, uint32_t *__restrict__ n_nodes, uint32_t *__restrict__ n_edges) {
     const uint32_t b = blockIdx.y;
     const uint64_t w = (uint64_t)blockIdx.x * KDB_GRAPH_BLOCK + threadIdx.x;
-    const uint32_t root = queries[b].root; // (<= n_nodes: its word is below wpn <= wpl)
-    const unsigned long long seed = root && w == (uint64_t)(root >> 6) ? 1ull << (root & 63u) : 0ull;
+    const unsigned long long seed = kdb_graph_seed_word(queries[b].root, w);
     if (w < wpl) nodes[(uint64_t)b * wpl + w] = seed;
     if (w < wpn) {
         const uint64_t at = (uint64_t)b * wpn + w;
@@ -85,25 +85,22 @@ __device__ __forceinline__ void sub_visit(const SubCtx &c, bool act, uint32_t no
     if (*vw & bit) return;
     if (!(atomicOr(vw, bit) & bit) && !c.last) atomicOr(c.Fn + fw, bit);
 }
+template <int MODE>
+struct SubVisitor { // the sweep's visitor
+    static constexpr bool converged = true;
+    const SubCtx &c;
+    __device__ __forceinline__ void operator()(bool act, uint32_t node, uint32_t far, uint32_t r, uint32_t dir) const { sub_visit<MODE>(c, act, node, far, r, dir); }
+};
 
-// Workgroup (s, b): words [first(s), first(s + 1)) of the current frontier of query b.  graph_level_kernel's sweep (graph_filter.hip):
-// the four waves take the slice in groups of 64 consecutive words, one word per lane; the ballot of the non-zero words is walked
-// word by word, lane i owns node 64 j + i; a node of degree <= KDB_GRAPH_LIGHT_DEG (per direction) is expanded by its lane, in a loop
-// that runs as long as ANY lane has an entry left so that the wave stays converged; heavier ones go to the hub queue in LDS as
-// (begin | direction << 63, end, source) with one compare-and-swap reservation per wave and word.  A wave whose reservation does not
-// fit stops where it is -- (group, pending words, direction) are wave-uniform registers -- and every wave meets at the drain, where
-// all 256 lanes go through the queued ranges in whole trips of 256 entries.  Everything that decides a barrier is wave-uniform and
-// the loop's exit is __syncthreads_or's common verdict.
+// Workgroup (s, b): words [first(s), first(s + 1)) of the current frontier of query b, zeroed as they are read in EXPAND only:
+// kdb_csr_sweep (kdb_graph_sweep.cuh) in both directions, every CSR entry to sub_visit.
 template <int MODE>
 __global__ void __launch_bounds__(KDB_GRAPH_BLOCK)
 subgraph_level_kernel(const KdbRelDev g, const KdbSubStaged *__restrict__ queries, uint32_t level, uint32_t parts, unsigned long long *nodes, uint64_t wpl,
                       unsigned long long *f_cur, unsigned long long *f_next, unsigned long long *bt, unsigned long long *bp, unsigned long long *bc,
                       uint64_t wpn, uint32_t *n_edges, kdb_subgraph_edge *edges, uint32_t edge_cap) {
-    __shared__ unsigned long long s_begin[KDB_GRAPH_HUB_CAP], s_end[KDB_GRAPH_HUB_CAP];
-    __shared__ uint32_t s_src[KDB_GRAPH_HUB_CAP];
-    __shared__ uint32_t s_n;
-    const uint32_t b = blockIdx.y, tid = threadIdx.x, lane = tid & (KDB_GRAPH_WAVE - 1u), wave = tid / KDB_GRAPH_WAVE;
-    const uint32_t depth = queries[b].depth;
+    __shared__ KdbHubQueue s_hubs;
+    const uint32_t b = blockIdx.y, depth = queries[b].depth;
     if (level >= depth || (MODE == SUB_COLLECT && !queries[b].guided)) return; // (the whole workgroup)
     SubCtx c;
     c.rel_mask = queries[b].rel_mask;
@@ -113,96 +110,7 @@ subgraph_level_kernel(const KdbRelDev g, const KdbSubStaged *__restrict__ querie
     c.edges = edges && edge_cap ? edges + (uint64_t)b * edge_cap : nullptr;
     c.edge_cap = edge_cap, c.level = level;
     c.guided = queries[b].guided != 0u, c.last = level + 1u >= depth;
-    unsigned long long *const Fc = f_cur + (uint64_t)b * wpn;
-    const uint64_t hi = kdb_graph_part_first(wpn, parts, blockIdx.x + 1u);
-    uint64_t next = kdb_graph_part_first(wpn, parts, blockIdx.x) + (uint64_t)wave * KDB_GRAPH_WAVE; // the wave's next group
-    uint64_t group = 0;                // first word of the group in hand
-    unsigned long long word = 0ull;    // the lane's word of it
-    unsigned long long pending = 0ull; // its non-zero words not yet expanded (wave-uniform)
-    uint32_t dir = 0;                  // the direction the first pending word goes on with (wave-uniform)
-    bool done = false;                 // (wave-uniform)
-    if (tid == 0u) s_n = 0u;
-    __syncthreads();
-    for (;;) {
-        while (!done) {
-            if (!pending) {
-                if (next >= hi) {
-                    done = true;
-                    break;
-                }
-                group = next;
-                next += (uint64_t)KDB_GRAPH_BLOCK;
-                const uint64_t w = group + lane;
-                word = w < hi ? Fc[w] : 0ull;
-                if (MODE == SUB_EXPAND && word) Fc[w] = 0ull;
-                pending = __ballot(word != 0ull);
-                dir = 0;
-                continue;
-            }
-            const uint32_t j = (uint32_t)__ffsll((long long)pending) - 1u;
-            const unsigned long long fw = __shfl(word, (int)j, (int)KDB_GRAPH_WAVE);
-            const uint64_t node = (group + j) * KDB_GRAPH_WAVE + lane;
-            const bool mine = ((fw >> lane) & 1ull) && node >= 1u && node <= (uint64_t)g.n_nodes;
-            bool full = false;
-            for (; dir < 2u; dir++) {
-                const uint64_t *const off = dir ? g.off[1] : g.off[0];
-                const uint32_t *const dst = dir ? g.dst[1] : g.dst[0];
-                const uint8_t *const rel = dir ? g.rel[1] : g.rel[0];
-                const uint64_t e0 = mine ? off[node] : 0ull, e1 = mine ? off[node + 1u] : 0ull;
-                const bool heavy = e1 - e0 > (uint64_t)KDB_GRAPH_LIGHT_DEG;
-                const unsigned long long hb = __ballot(heavy);
-                if (hb) {
-                    const uint32_t n = (uint32_t)__popcll(hb);
-                    uint32_t slot = KDB_GRAPH_HUB_CAP;
-                    if (lane == 0u) {
-                        uint32_t seen = *(volatile uint32_t *)&s_n;
-                        while (seen + n <= KDB_GRAPH_HUB_CAP) {
-                            const uint32_t was = atomicCAS(&s_n, seen, seen + n);
-                            if (was == seen) {
-                                slot = seen;
-                                break;
-                            }
-                            seen = was;
-                        }
-                    }
-                    slot = (uint32_t)__shfl((int)slot, 0, (int)KDB_GRAPH_WAVE);
-                    if (slot == KDB_GRAPH_HUB_CAP) { // no room: the drain first, then this word and direction again
-                        full = true;
-                        break;
-                    }
-                    if (heavy) {
-                        const uint32_t at = slot + (uint32_t)__popcll(hb & ((1ull << lane) - 1ull));
-                        s_begin[at] = e0 | ((unsigned long long)dir << 63);
-                        s_end[at] = e1;
-                        s_src[at] = (uint32_t)node;
-                    }
-                }
-                for (uint64_t e = e0; __ballot(!heavy && e < e1) != 0ull; e++) { // (every lane goes round while any lane has an entry)
-                    const bool a = !heavy && e < e1;
-                    sub_visit<MODE>(c, a, (uint32_t)node, a ? dst[e] : 0u, a ? (uint32_t)rel[e] : 0u, dir);
-                }
-            }
-            if (full) break;
-            pending &= pending - 1ull;
-            dir = 0;
-        }
-        __syncthreads(); // the queue's records are visible
-        const uint32_t n_hubs = s_n;
-        for (uint32_t i = 0; i < n_hubs; i++) {
-            const unsigned long long rec = s_begin[i], e1 = s_end[i];
-            const uint32_t src = s_src[i], in = (uint32_t)(rec >> 63);
-            const uint32_t *const dst = in ? g.dst[1] : g.dst[0];
-            const uint8_t *const rel = in ? g.rel[1] : g.rel[0];
-            for (uint64_t t0 = rec & ~(1ull << 63); t0 < e1; t0 += KDB_GRAPH_BLOCK) { // whole trips: the waves stay converged
-                const uint64_t e = t0 + tid;
-                const bool a = e < e1;
-                sub_visit<MODE>(c, a, src, a ? dst[e] : 0u, a ? (uint32_t)rel[e] : 0u, in);
-            }
-        }
-        if (!__syncthreads_or(!done)) break; // (also: every lane has read the queue)
-        if (tid == 0u) s_n = 0u;
-        __syncthreads();
-    }
+    kdb_csr_sweep<MODE == SUB_EXPAND>(g, f_cur + (uint64_t)b * wpn, wpn, parts, 3u, s_hubs, SubVisitor<MODE>{c});
 }
 
 // ---- the gate ---------------------------------------------------------------------------------------------------------------------
@@ -270,14 +178,44 @@ __device__ __forceinline__ void gate_trip(const KdbView &v, const float *q, floa
     }
 }
 
-// Workgroup (s, b): words [first(s), first(s + 1)) of the candidate bitmap C of query b, level `level`.
-//   guide   the prepared guide of the query, once per workgroup, in LDS (ld floats, or ld packed int8 values)
-//   sweep   as the level kernel sweeps a frontier: one word per lane; the lane that reads a non-zero word ORs it into T and writes
-//           zero over it (only this workgroup touches these words of T and C in this launch).  The non-zero words are walked one by
-//           one: the wave reserves popcount(word) places of the batch with one compare-and-swap and lane i writes node 64 j + i
-//           behind the set bits below it.  A wave whose word does not fit stops where it is and every wave meets at the drain
+// The gate's policy for kdb_sweep_rounds (kdb_graph_sweep.cuh): the queue is a batch of node ids in LDS.
+//   load    the lane that reads a non-zero word of C ORs it into T and writes zero over it (only this workgroup touches these words
+//           of T and C in this launch)
+//   take    the wave reserves popcount(word) places of the batch and lane i writes node 64 j + i behind the set bits below it
 //   drain   wave w takes trips w, w + 4, ... of the batch, 4 * R rows each (gate_trip): with R rows of every 16-lane group in
-//           flight, a CU holds 16 * R row gathers per resident workgroup.  The batch is empty after a drain and takes any one word
+//           flight, a CU holds 16 * R row gathers per resident workgroup
+template <int PREC, int METRIC, int NCH>
+struct GateSweep {
+    const KdbView &v;
+    const float *guide; // in LDS
+    float qnorm;
+    double threshold;
+    unsigned long long *T, *P, *C;
+    uint32_t *s_batch, *s_n;
+
+    __device__ __forceinline__ unsigned long long load(uint64_t w) const {
+        const unsigned long long word = C[w];
+        if (word) {
+            T[w] |= word;
+            C[w] = 0ull;
+        }
+        return word;
+    }
+    __device__ __forceinline__ bool take(uint64_t j, unsigned long long cw) const {
+        const uint32_t slot = kdb_sweep_reserve(*s_n, (uint32_t)__popcll(cw), KDB_SUBGRAPH_GATE_BATCH);
+        if (slot == KDB_SUBGRAPH_GATE_BATCH) return false;
+        if ((cw >> kdb_lane()) & 1ull) s_batch[slot + kdb_mbcnt(cw)] = (uint32_t)(j * KDB_GRAPH_WAVE + (uint32_t)kdb_lane());
+        return true;
+    }
+    __device__ __forceinline__ void drain(uint32_t nb) const {
+        constexpr uint32_t TRIP = 4u * (uint32_t)kdbcore::kdb_trip_rows<PREC, NCH, 0>();
+        for (uint32_t base = threadIdx.x / KDB_GRAPH_WAVE * TRIP; base < nb; base += 4u * TRIP)
+            gate_trip<PREC, METRIC, NCH>(v, guide, qnorm, threshold, s_batch, base, nb, P);
+    }
+};
+
+// Workgroup (s, b): words [first(s), first(s + 1)) of the candidate bitmap C of query b, level `level`: the prepared guide of the
+// query, once per workgroup, into LDS (ld floats, or ld packed int8 values), then the sweep with GateSweep.
 // A gather bound by HBM latency: no matrix instruction fits, every query has its own single guide.
 template <int PREC, int METRIC, int NCH>
 __global__ void __launch_bounds__(KDB_GRAPH_BLOCK)
@@ -286,84 +224,20 @@ subgraph_gate_kernel(const KdbView v, const KdbSubStaged *__restrict__ queries, 
     extern __shared__ __attribute__((aligned(16))) unsigned char s_guide[];
     __shared__ uint32_t s_batch[KDB_SUBGRAPH_GATE_BATCH];
     __shared__ uint32_t s_n;
-    const uint32_t b = blockIdx.y, tid = threadIdx.x, lane = tid & (KDB_GRAPH_WAVE - 1u), wave = tid / KDB_GRAPH_WAVE;
+    const uint32_t b = blockIdx.y;
     if (level >= queries[b].depth || !queries[b].guided) return; // (the whole workgroup)
-    constexpr uint32_t TRIP = 4u * (uint32_t)kdbcore::kdb_trip_rows<PREC, NCH, 0>();
-    const double threshold = queries[b].threshold;
-    const float qnorm = qnorms[b];
-    unsigned long long *const T = bt + (uint64_t)b * wpn, *const P = bp + (uint64_t)b * wpn, *const Cb = bc + (uint64_t)b * wpn;
     {
         const uint4 *const src = reinterpret_cast<const uint4 *>(guides + (size_t)b * guide_row); // (rows of 16-byte pieces on 256-byte regions)
-        for (uint32_t i = tid; i < (guide_row >> 4); i += KDB_GRAPH_BLOCK) reinterpret_cast<uint4 *>(s_guide)[i] = src[i];
-    }
-    const uint64_t hi = kdb_graph_part_first(wpn, parts, blockIdx.x + 1u);
-    uint64_t next = kdb_graph_part_first(wpn, parts, blockIdx.x) + (uint64_t)wave * KDB_GRAPH_WAVE;
-    uint64_t group = 0;
-    unsigned long long word = 0ull, pending = 0ull; // (pending: wave-uniform)
-    bool done = false;                              // (wave-uniform)
-    if (tid == 0u) s_n = 0u;
-    __syncthreads();
-    for (;;) {
-        while (!done) {
-            if (!pending) {
-                if (next >= hi) {
-                    done = true;
-                    break;
-                }
-                group = next;
-                next += (uint64_t)KDB_GRAPH_BLOCK;
-                const uint64_t w = group + lane;
-                word = w < hi ? Cb[w] : 0ull;
-                if (word) {
-                    T[w] |= word;
-                    Cb[w] = 0ull;
-                }
-                pending = __ballot(word != 0ull);
-                continue;
-            }
-            const uint32_t j = (uint32_t)__ffsll((long long)pending) - 1u;
-            const unsigned long long cw = __shfl(word, (int)j, (int)KDB_GRAPH_WAVE);
-            const uint32_t n = (uint32_t)__popcll(cw);
-            uint32_t slot = KDB_SUBGRAPH_GATE_BATCH;
-            if (lane == 0u) {
-                uint32_t seen = *(volatile uint32_t *)&s_n;
-                while (seen + n <= KDB_SUBGRAPH_GATE_BATCH) {
-                    const uint32_t was = atomicCAS(&s_n, seen, seen + n);
-                    if (was == seen) {
-                        slot = seen;
-                        break;
-                    }
-                    seen = was;
-                }
-            }
-            slot = (uint32_t)__shfl((int)slot, 0, (int)KDB_GRAPH_WAVE);
-            if (slot == KDB_SUBGRAPH_GATE_BATCH) break; // no room: the drain first, then this word again
-            if ((cw >> lane) & 1ull) s_batch[slot + (uint32_t)__popcll(cw & ((1ull << lane) - 1ull))] = (uint32_t)((group + j) * KDB_GRAPH_WAVE + lane);
-            pending &= pending - 1ull;
-        }
-        __syncthreads(); // the batch is visible
-        const uint32_t nb = s_n;
-        for (uint32_t base = wave * TRIP; base < nb; base += 4u * TRIP)
-            gate_trip<PREC, METRIC, NCH>(v, reinterpret_cast<const float *>(s_guide), qnorm, threshold, s_batch, base, nb, P);
-        if (!__syncthreads_or(!done)) break; // (also: every wave has read the batch)
-        if (tid == 0u) s_n = 0u;
-        __syncthreads();
-    }
+        for (uint32_t i = threadIdx.x; i < (guide_row >> 4); i += KDB_GRAPH_BLOCK) reinterpret_cast<uint4 *>(s_guide)[i] = src[i];
+    } // (visible behind the barrier the rounds open with)
+    GateSweep<PREC, METRIC, NCH> p{v, reinterpret_cast<const float *>(s_guide), qnorms[b], queries[b].threshold, bt + (uint64_t)b * wpn,
+                                   bp + (uint64_t)b * wpn, bc + (uint64_t)b * wpn, s_batch, &s_n};
+    kdb_sweep_rounds(kdb_graph_part_first(wpn, parts, blockIdx.x), kdb_graph_part_first(wpn, parts, blockIdx.x + 1u), &s_n, p);
 }
 
 __global__ void __launch_bounds__(KDB_GRAPH_BLOCK)
 subgraph_finish_kernel(unsigned long long *__restrict__ nodes, uint64_t wpl, uint32_t n_graph_nodes, uint32_t *__restrict__ n_nodes) {
-    const uint32_t b = blockIdx.y;
-    const uint64_t w = (uint64_t)blockIdx.x * KDB_GRAPH_BLOCK + threadIdx.x;
-    unsigned long long v = 0ull;
-    if (w < wpl) {
-        v = nodes[(uint64_t)b * wpl + w] & kdb_graph_live_mask(w, n_graph_nodes);
-        nodes[(uint64_t)b * wpl + w] = v;
-    }
-    uint32_t n = (uint32_t)__popcll(v);
-#pragma unroll
-    for (int o = (int)KDB_GRAPH_WAVE / 2; o >= 1; o >>= 1) n += (uint32_t)__shfl_xor((int)n, o, (int)KDB_GRAPH_WAVE);
-    if ((threadIdx.x & (KDB_GRAPH_WAVE - 1u)) == 0u && n) atomicAdd(n_nodes + b, n);
+    kdb_graph_finish_word(nodes + (uint64_t)blockIdx.y * wpl, wpl, n_graph_nodes, nullptr, n_nodes + blockIdx.y);
 }
 
 struct GateArgs {

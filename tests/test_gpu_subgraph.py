@@ -158,6 +158,34 @@ def test_hubs_and_a_second_call_on_the_stream(hip):
         same(run_dev(idx, q, (n >> 6) + 1, int(want[2].max()), np.tile(guide, (q.size, 1)), stream=st.cuda_stream), want)
 
 
+def test_hub_queue_fills_in_the_second_direction(hip, monkeypatch):
+    """root 1 -> 400 consecutive middle nodes, each light outwards (1..16 edges) and heavy inwards (18 distinct sources): with one
+    workgroup the hub queue fills while a word's in-edges are queued, after that word's out-edges were visited by their lanes.  A sweep
+    that took such a word up again at the first direction would write those records twice: n_edges and the sorted records show it."""
+    import test_gpu_graph_filter as F
+    hub_cap, light = 256, 16  # KDB_GRAPH_HUB_CAP, KDB_GRAPH_LIGHT_DEG (kdb_graph_plan.h)
+    middle, count, n = range(100, 500), 2000, 2000
+    edges = [(1, 0, m) for m in middle]
+    edges += [(m, 1, 600 + (m * 5 + i * 3) % 1400) for m in middle for i in range(1 + m % 16)]
+    edges += [(600 + (m * 17 + i) % 1400, 2, m) for m in middle for i in range(17)]
+    outs, ins = {}, {}
+    for s, _, t in edges:
+        outs.setdefault(s, set()).add(t)
+        ins.setdefault(t, set()).add(s)
+    level1 = outs[1] | ins.get(1, set())
+    assert sum(1 <= len(outs.get(m, ())) <= light and len(ins[m]) > light for m in level1) > hub_cap + 64
+    idx, rows, live, _, _ = make(hip, edges, count, n)
+    words = (n >> 6) + 1
+    q = queries([(1, 2, 7, None), (1, 2, 7, 1e6)])
+    guides = np.tile(rows[7] + 0.5, (2, 1))
+    want = R.results(edges, q, words, [R.distances(rows, live, guides[0], 0, 0)] * 2)
+    assert want[2][0] == want[2][1] == len(edges) + len(middle)  # every edge once, the root's also from their far ends
+    gq = F.queries([(1, 2, GR.BOTH, 7)])
+    monkeypatch.setenv("KDB_GRAPH_PARTS", "1")
+    same(run_dev(idx, q, words, int(want[2][0]), guides), want)
+    F.same(F.run_dev(idx, gq, words), GR.lists_of(edges, count, gq, words))
+
+
 def test_edge_cap_and_the_host_form(hip):
     count = 128
     edges, n = random_graph(count)
